@@ -7,7 +7,8 @@ One step = one pass of uwie_enhance_u8 (strategy 2, cast correction on: the cano
 over one batch of synthetic "underwater" uint8 frames per GPU.  Default workload: BASELINE.json configs[2], the
 configuration the target metric is quoted on -- 4K (3840x2160) RGB, batch 64 per GPU.  Batches shard across ranks
 with no data-path collective (frames are independent), so scaling is weak; the only collectives are the barriers
-and the MAX of the elapsed time.  Prints ONE JSON line on rank 0.
+and the MAX of the elapsed time.  Prints ONE JSON line on rank 0.  `--dump-outputs DIR` also writes rank 0's result of the
+last timed step to DIR/enhanced.npy (float32), to compare two builds output for output on the same seeded frames.
 
 `roofline`    : the dominant kernel of the timed region (HIP events on the launch stream, recorded inside libuwie),
                 its algorithmic bytes (table below) over its measured time, against 8 TB/s HBM.
@@ -151,6 +152,29 @@ def measured_traffic(kernel, H, W, B, strategy, launches_per_step, dist="underwa
     if key not in table:
         return None
     return table[key]["hbm_bytes_per_px_per_step"] * B * H * W / max(launches_per_step, 1)
+
+
+DUMP_PIXELS = 1 << 22  # --dump-outputs: at most this many [3]-pixels, 48 MiB of float32
+
+
+def dump_outputs(dirname, name, out):
+    """--dump-outputs: the uint8 result `out` ([..., 3]) of the last timed step as DIR/<name>.npy in float32.  Whole when it
+    holds at most DUMP_PIXELS pixels; otherwise those pixels of the flattened [N, 3] view whose indices are
+    np.sort(np.random.default_rng(0).choice(N, DUMP_PIXELS, replace=False)) -- the same sample for the same arguments, so the
+    files of two builds compare value for value."""
+    import numpy as np
+    import torch
+
+    px = out.reshape(-1, out.shape[-1])
+    note = "whole"
+    if px.shape[0] > DUMP_PIXELS:
+        idx = np.sort(np.random.default_rng(0).choice(px.shape[0], DUMP_PIXELS, replace=False))
+        out = px[torch.from_numpy(idx).to(px.device)]
+        note = f"seeded sample of {DUMP_PIXELS} of {px.shape[0]} pixels"
+    os.makedirs(dirname, exist_ok=True)
+    path = os.path.join(dirname, name + ".npy")
+    np.save(path, out.cpu().numpy().astype(np.float32))
+    print(f"bench.py: wrote {path} ({note})", file=sys.stderr)
 
 
 def timed_enhance(dev, _lib, torch, frames, strategy, steps, **overrides):
@@ -337,6 +361,8 @@ def main_scatter(args, uw, _lib, torch, world, rank, local, rehearsal):
         dist.barrier()
     if rank == 0:
         assert res.shape[0] == total
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, "enhanced", res)
         print(json.dumps({
             "metric": "megapixels/sec enhanced", "value": round(total * H * W * args.steps / elapsed / 1e6, 2),
             "unit": "megapixels/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -447,7 +473,15 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kernel-table", action="store_true", help="print the per-kernel times of the recorded warm-up step to stderr")
     ap.add_argument("--no-extras", action="store_true", help="skip the other input distributions and the 1080p batch=1 case")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write rank 0's result of the last one as DIR/enhanced.npy (float32; a fixed "
+                         f"seeded sample of {DUMP_PIXELS} pixels when larger).  --mode local and scatter")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mode == "stream":
+        # the stream consumes each chunk's result in the ring's pinned buffers: no step's whole output exists to be written
+        ap.error("--dump-outputs: --mode stream keeps no step's whole output")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Not under torchrun: start one fresh process per GPU ourselves, BEFORE anything here touches the GPU (a process
@@ -529,6 +563,8 @@ def main():
         dist.barrier()
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, "enhanced", out)
         px_step = B * H * W
         value = world * px_step * args.steps / elapsed / 1e6
         ms, calls = rows[name]  # the dominant kernel, measured inside the timed region

@@ -166,3 +166,36 @@ def test_bench_refuses_a_world_size_that_differs_from_gpus(monkeypatch):
     with pytest.raises(SystemExit) as exc:
         bench.main()
     assert exc.value.code not in (0, None) and "WORLD_SIZE=1" in str(exc.value.code)
+
+
+def test_bench_refuses_zero_steps_and_a_stream_dump(monkeypatch, tmp_path):
+    """`ms_per_step` divides by --steps; --mode stream consumes each chunk's result in the ring, so there is nothing to dump."""
+    import sys
+
+    bench = _load_bench()
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    for argv in (["--steps", "0"], ["--mode", "stream", "--dump-outputs", str(tmp_path)]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit) as exc:
+            bench.main()
+        assert exc.value.code == 2
+    assert not torch.cuda.is_initialized() and not any(tmp_path.iterdir())
+
+
+def test_bench_dump_outputs_whole_or_a_fixed_sample(monkeypatch, tmp_path):
+    """--dump-outputs writes float32 values of the uint8 result: the whole array when it is small, otherwise the same
+    seeded sample of whole pixels on every run (so two builds compare file for file)."""
+    bench = _load_bench()
+    small = torch.randint(0, 256, (2, 5, 6, 3), dtype=torch.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), "enhanced", small)
+    got = np.load(tmp_path / "a" / "enhanced.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy())
+    monkeypatch.setattr(bench, "DUMP_PIXELS", 16)
+    big = torch.randint(0, 256, (3, 7, 9, 3), dtype=torch.uint8)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), "enhanced", big)
+    got = np.load(tmp_path / "b" / "enhanced.npy")
+    idx = np.sort(np.random.default_rng(0).choice(3 * 7 * 9, 16, replace=False))
+    assert got.dtype == np.float32 and got.shape == (16, 3)
+    assert np.array_equal(got, big.reshape(-1, 3).numpy()[idx])
+    assert np.array_equal(got, np.load(tmp_path / "c" / "enhanced.npy"))

@@ -264,3 +264,35 @@ def test_bench_two_ranks_under_the_drivers_launcher_rehearsal(mode):
         assert d["roofline"]["kernel"] and d["config"]["parallelism"] == "batch-shard x2"
     else:
         assert d["config"]["parallelism"] == "scatter/gather x2" and "gloo rehearsal" in d["config"]["workload"]
+
+
+@pytest.mark.parametrize("mode,seed", [("local", 2000), ("scatter", 3000)])
+def test_bench_dump_outputs_is_the_timed_result(uw, tmp_path, mode, seed):
+    """`bench.py --dump-outputs DIR`: DIR/enhanced.npy holds, as float32, exactly what enhance() returns for the bench's own
+    seeded frames (the timed path's result, not a re-run of another path), and the line times exactly --steps steps."""
+    import importlib.util
+    import json
+    import subprocess
+    import sys
+
+    import torch
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    H, W, B, K = 96, 128, 3, 3
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", "1", "--mode", mode,
+           "--height", str(H), "--width", str(W), "--batch", str(B), "--no-cpu-baseline", "--no-extras",
+           "--dump-outputs", str(tmp_path)]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == K and d["ms_per_step"] > 0
+    spec = importlib.util.spec_from_file_location("uwie_bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    frames = bench.synth_frames("underwater", B, H, W, torch.device("cuda", 0), seed=seed)
+    want = uw.enhance(frames).cpu().numpy()
+    got = np.load(tmp_path / "enhanced.npy")
+    assert got.dtype == np.float32 and got.shape == (B, H, W, 3)
+    assert np.array_equal(got, want.astype(np.float32))
