@@ -242,6 +242,28 @@ int uwie_diff_enhance_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int b
                           const float *d_params, int flags, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Its gradient (vgg_16_UIE.DifferentiableEnhancement under torch autograd; the contract: DESIGN.md section 8).
+ *   uwie_diff_enhance_save_f32: uwie_diff_enhance_f32 (the same output bytes, the same workspace) that also writes
+ *     d_saved [batch][3][2] float32 = {p_lo, p_hi} of every plane, the two sorted values the stretch used.
+ *   uwie_diff_enhance_bwd_f32: given the forward's inputs (d_img, d_params, flags, planar), its d_saved and
+ *     d_grad_out = dL/d(out) in the image's layout, writes
+ *       d_grad_img (NULL: skipped, parameter gradients only) = dL/d(img), same layout; the gradient of p_lo / p_hi
+ *         goes to the element torch's stable CPU sort took it from;
+ *       d_grad_params [batch][4] float32 = {0, 0, dL/d(omega), dL/d(gamma)} (L_low / L_high get no gradient: the
+ *         reference reads them with .item()).
+ *     Sums over pixels are float64 in a fixed order, without atomics: the same inputs give the same bits on every run.
+ *     Two kernel launches.  Reads nothing the forward left in the workspace.  Workspace:
+ *     uwie_diff_enhance_bwd_workspace_bytes(batch, H, W) (about 112 bytes per 2048 pixels, at most 57 KB per image).
+ */
+int uwie_diff_enhance_save_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, int planar,
+                               const float *d_params, int flags, float *d_saved, void *d_workspace, size_t workspace_bytes,
+                               void *stream);
+size_t uwie_diff_enhance_bwd_workspace_bytes(int batch, int H, int W);
+int uwie_diff_enhance_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_params, int flags, int planar, int batch,
+                              int H, int W, const float *d_saved, const float *d_grad_out, float *d_grad_img,
+                              float *d_grad_params, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
  * vgg_16_UIE.extract_all_features (vgg_16_UIE.py:435-466) for uint8 frames: d_features [batch][79] float32 =
  * {mean, std, min, max, median} of each channel of img = u8/255, then mean(img), std(img), mean(img**2), zeros.
  * NumPy float32 arithmetic (pairwise sums over 8192-element buffers) reproduced bit for bit.

@@ -82,6 +82,9 @@ SIGNATURES = {
     "uwie_workspace_bytes_select": [_I, _I, _I, _VP, _I, _I],
     "uwie_select_best_u8": [_VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP],
     "uwie_diff_enhance_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _SZ, _VP],
+    "uwie_diff_enhance_save_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _SZ, _VP],
+    "uwie_diff_enhance_bwd_workspace_bytes": [_I, _I, _I],
+    "uwie_diff_enhance_bwd_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP],
     "uwie_extract_features_u8": [_VP, _VP, _VP, _I, _I, _I, _VP, _SZ, _VP],
     "uwie_quality_scores": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _SZ, _VP],
     "uwie_cast_classify": [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _SZ, _VP],
@@ -111,6 +114,7 @@ _RESTYPES = {
     "uwie_workspace_bytes_all": ctypes.c_size_t,
     "uwie_workspace_bytes_float": ctypes.c_size_t,
     "uwie_workspace_bytes_select": ctypes.c_size_t,
+    "uwie_diff_enhance_bwd_workspace_bytes": ctypes.c_size_t,
 }
 
 _lib = None

@@ -203,18 +203,81 @@ def process_batch(frames, filenames=None, device: int | None = None, compute=Non
 
 
 # ------------------------------------------------------------------ vgg_16_UIE.DifferentiableEnhancement (N3)
+class DiffEnhanceFunction(torch.autograd.Function):
+    """``out = DiffEnhanceFunction.apply(img, params, flags, planar, dev)``: the device forward with its backward.
+
+    ``img``: float32 ``[B,3,H,W]`` (planar) or ``[B,H,W,3]`` on ``dev``; ``params``: float32 ``[B,4]`` =
+    ``L_low, L_high, omega, gamma``; ``flags``: ``UWIE_DIFF_OMEGA (1) | UWIE_DIFF_GAMMA (2)``.  The gradient is the one
+    torch autograd gives the reference module on the CPU: ``params`` gets ``0, 0, d omega,
+    d gamma``; ``img`` gets its gradient only when it requires one (otherwise the kernel skips that write).
+    """
+
+    @staticmethod
+    def forward(ctx, img, params, flags, planar, dev):
+        out, saved = dev.diff_enhance_save_f32(img, params, planar, flags)
+        ctx.save_for_backward(img, params, saved)
+        ctx.flags, ctx.planar, ctx.dev = flags, planar, dev
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        img, params, saved = ctx.saved_tensors
+        grad_img, grad_params = ctx.dev.diff_enhance_bwd_f32(img, params, saved, grad_out.float().contiguous(), ctx.planar,
+                                                             ctx.flags, want_img=ctx.needs_input_grad[0])
+        return grad_img, (grad_params if ctx.needs_input_grad[1] else None), None, None, None
+
+
 class DifferentiableEnhancement:
-    """Forward pass of ``vgg_16_UIE.DifferentiableEnhancement`` (vgg_16_UIE.py:24-128) on the device.
+    """``vgg_16_UIE.DifferentiableEnhancement`` (vgg_16_UIE.py:24-128) on the device, forward and backward.
 
     ``forward(img, params)``: ``img`` is ``(B, 3, H, W)`` float32 (NumPy or torch ROCm tensor), ``params`` a dict of
     ``(B, 1)``-shaped values with the reference's keys: ``L_low`` and ``L_high`` are required, ``omega`` and ``gamma``
-    optional (a missing key skips that stage, vgg_16_UIE.py:48,52).  Not differentiable: inference only.
+    optional (a missing key skips that stage, vgg_16_UIE.py:48,52).
+
+    Differentiable: with grad mode on and ``img`` or a parameter tensor requiring grad, the output carries a ``grad_fn``
+    and ``loss.backward()`` runs the gradient kernels (``DiffEnhanceFunction``).  ``omega`` and ``gamma`` get the
+    gradient torch autograd gives the reference on the CPU, in their own dtype and device (float16 / bfloat16 values
+    from an autocast head are cast to float32 first, as torch's type promotion does in the reference); ``L_low`` and
+    ``L_high`` get none (the reference reads them with ``.item()``); ``img`` gets one when it requires it.  Otherwise
+    the forward alone runs, as for inference.
     """
 
     device: int | None = None
 
+    @staticmethod
+    def _wants_grad(img, params) -> bool:
+        if not torch.is_grad_enabled():
+            return False
+        vals = [img] + [params[k] for k in ("L_low", "L_high", "omega", "gamma") if k in params]
+        return any(isinstance(v, torch.Tensor) and v.requires_grad for v in vals)
+
+    def _forward_grad(self, dev: Device, img, params):
+        x = img.to(dev.torch_device)
+        if x.dtype != torch.float32:
+            raise ValueError(f"expected a float32 image batch, got {x.dtype}")
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"expected a (B, 3, H, W) image batch, got {tuple(x.shape)}")
+        B = x.shape[0]
+        cols = []
+        for key, default in (("L_low", None), ("L_high", None), ("omega", 0.0), ("gamma", 1.0)):
+            if key in params:
+                v = params[key]
+                v = (v.to(device=dev.torch_device, dtype=torch.float32) if isinstance(v, torch.Tensor)
+                     else torch.as_tensor(np.asarray(v, dtype=np.float32), device=dev.torch_device))
+                if key in ("L_low", "L_high"):
+                    v = v.detach()  # sorted positions: no gradient (vgg_16_UIE.py:78-79 reads them with .item())
+                cols.append(torch.broadcast_to(v.reshape(-1), (B,)))
+            elif default is None:
+                raise KeyError(key)
+            else:
+                cols.append(torch.full((B,), default, dtype=torch.float32, device=dev.torch_device))
+        flags = (1 if "omega" in params else 0) | (2 if "gamma" in params else 0)
+        return DiffEnhanceFunction.apply(x, torch.stack(cols, dim=1).contiguous(), flags, True, dev)
+
     def forward(self, img, params):
         dev = get_device(self.device)
+        if self._wants_grad(img, params):
+            return self._forward_grad(dev, img, params)
         was_numpy = not hasattr(img, "data_ptr")
         x = dev.tensor(np.ascontiguousarray(img, dtype=np.float32)) if was_numpy else img
         if x.dim() != 4 or x.shape[1] != 3:

@@ -1061,6 +1061,45 @@ int uwie_diff_enhance_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int b
     return launch_diff_enhance(d_img, planar ? 1 : 0, s, d_params, flags, (const float *)plan.os, d_out, st);
 }
 
+int uwie_diff_enhance_save_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, int planar,
+                               const float *d_params, int flags, float *d_saved, void *d_workspace, size_t workspace_bytes,
+                               void *stream)
+{
+    UWIE_REQUIRE(ctx && d_img && d_out && d_params && d_saved, "diff_enhance_save: NULL pointer");
+    UWIE_SCOPE(ctx);
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_REQUIRE((flags & ~3) == 0, "diff_enhance_save: flags are UWIE_DIFF_OMEGA | UWIE_DIFF_GAMMA");
+    const Shape s{batch, H, W};
+    UWIE_CHECK_WS(select_ws_bytes(s));
+    hipStream_t st = (hipStream_t)stream;
+    SelectPlan plan;
+    UWIE_TRY(select_begin_stretch_ranks(s, d_params, 4, d_workspace, st, &plan));
+    UWIE_TRY(select_run(plan, d_img, planar ? 1 : 0, s, false, st));
+    return launch_diff_enhance(d_img, planar ? 1 : 0, s, d_params, flags, (const float *)plan.os, d_out, st, d_saved);
+}
+
+size_t uwie_diff_enhance_bwd_workspace_bytes(int batch, int H, int W)
+{
+    if (!shape_ok(batch, H, W)) return 0;
+    return diff_enhance_bwd_ws_bytes(Shape{batch, H, W});
+}
+
+int uwie_diff_enhance_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_params, int flags, int planar, int batch,
+                              int H, int W, const float *d_saved, const float *d_grad_out, float *d_grad_img,
+                              float *d_grad_params, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE(ctx && d_img && d_params && d_saved && d_grad_out && d_grad_params, "diff_enhance_bwd: NULL pointer");
+    UWIE_SCOPE(ctx);
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_REQUIRE((flags & ~3) == 0, "diff_enhance_bwd: flags are UWIE_DIFF_OMEGA | UWIE_DIFF_GAMMA");
+    UWIE_REQUIRE((const void *)d_grad_img != (const void *)d_img && (const void *)d_grad_img != (const void *)d_grad_out,
+                 "diff_enhance_bwd: d_grad_img must not alias d_img or d_grad_out");
+    const Shape s{batch, H, W};
+    UWIE_CHECK_WS(diff_enhance_bwd_ws_bytes(s));
+    return launch_diff_enhance_bwd(d_img, planar ? 1 : 0, s, d_params, flags, d_saved, d_grad_out, d_grad_img, d_grad_params,
+                                   d_workspace, (hipStream_t)stream);
+}
+
 int uwie_extract_features_u8(uwie_ctx *ctx, const uint8_t *d_in, float *d_features, int batch, int H, int W,
                              void *d_workspace, size_t workspace_bytes, void *stream)
 {

@@ -7,6 +7,12 @@
 //   gamma    pow(img + 1e-8, gamma)                                                       vgg_16_UIE.py:127
 // pow is evaluated in float64 and rounded once; torch's float32 pow (Sleef, 1 ulp) may differ by one ulp: stated
 // tolerance of the gamma stage.
+//
+// Backward (the gradient torch autograd gives the module on the CPU): k_diff_enhance_bwd recomputes
+// the forward per pixel from x and the saved order statistics, writes grad_img (optional) and per-block float64 partial
+// sums of grad omega, grad gamma, grad p_lo / p_hi plus the counts of x < p and x == p that locate the element torch's
+// stable sort routes each order statistic's gradient to; k_diff_enhance_bwd_finish reduces the partials in a fixed order
+// (no atomics: bit-identical runs) and scatters the two scalar terms per plane.
 #include "common.h"
 #include "devutil.h"
 
@@ -19,9 +25,14 @@ __device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.0f),
 // planar: img/out [B][3][n];  interleaved: [B][n][3].  os: [B*3][kSelOsStride] floats, entries 0/1 = p_low, p_high.
 __global__ void __launch_bounds__(256) k_diff_enhance(const float *__restrict__ img, int planar, int n,
                                                       const float *__restrict__ params, int flags,
-                                                      const float *__restrict__ os, float *__restrict__ out)
+                                                      const float *__restrict__ os, float *__restrict__ out,
+                                                      float *__restrict__ saved)
 {
     const int b = blockIdx.y;
+    if (saved && blockIdx.x == 0 && threadIdx.x < 6) {  // {p_lo, p_hi} of the three planes, for the backward
+        const int c = threadIdx.x >> 1, q = threadIdx.x & 1;
+        saved[(b * 3 + c) * 2 + q] = os[(size_t)(b * 3 + c) * kSelOsStride + q];
+    }
     const float *pr = params + b * 4;
     float lo[3], rng[3];
 #pragma unroll
@@ -58,14 +69,334 @@ __global__ void __launch_bounds__(256) k_diff_enhance(const float *__restrict__ 
     }
 }
 
+// torch.sort position int((L / 100.0) * n) clamped to [0, n - 1] (vgg_16_UIE.py:78-82; k_sel_init_stretch_ranks)
+__device__ __forceinline__ long long stretch_rank(float L, int n)
+{
+    const double pos = ((double)L / 100.0) * (double)n;
+    if (!(pos > 0.0)) return 0;
+    if (pos >= (double)(n - 1)) return n - 1;
+    return (long long)pos;
+}
+
+// Per-block partials: kPartD float64 sums and kPartU counts per (image, block).
+//   sums:   0 grad omega, 1 grad gamma, 2 + c: sum of grad_x over plane c (the stretch's dL/dx before the scatter),
+//           5 + c: dL/dr of plane c (r = p_hi - p_lo + 1e-8)
+//   counts: c * 4 + {0: x < p_lo, 1: x == p_lo, 2: x < p_hi, 3: x == p_hi}
+constexpr int kPartD = 8, kPartU = 12;
+
+// One contiguous chunk of `chunk` pixels of one image per block, so that the equal counts of the blocks, in block order,
+// are the equal counts of the plane in linear index order (what the finish kernel scans for the stable-sort position).
+// Every pointwise term follows torch's backward formulas in operation order (clamp: pass where lo <= v <= hi; a / b:
+// grad / b and -grad * ((a / b) / b); min(dim): the first minimal channel; pow: grad * (g * y^(g - 1)) and
+// grad * (z * log(y))).  y^(g - 1) is z / y in float64, rounded once (z: the forward's pow, <= 1 ulp).
+template <int FLAGS>
+__global__ void __launch_bounds__(256) k_diff_enhance_bwd(const float *__restrict__ img, int planar, int n, int chunk,
+                                                          const float *__restrict__ params, const float *__restrict__ saved,
+                                                          const float *__restrict__ gout, float *__restrict__ gimg,
+                                                          double *__restrict__ part, uint32_t *__restrict__ cnt)
+{
+    const int b = blockIdx.y;
+    float lo[3], hi[3], rng[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        lo[c] = saved[(b * 3 + c) * 2];
+        hi[c] = saved[(b * 3 + c) * 2 + 1];
+        rng[c] = (hi[c] - lo[c]) + 1e-8f;
+    }
+    const float omega = params[b * 4 + 2], gamma = params[b * 4 + 3];
+    double s_om = 0.0, s_ga = 0.0, s_x[3] = {0.0, 0.0, 0.0}, s_r[3] = {0.0, 0.0, 0.0};
+    uint32_t k[kPartU];
+#pragma unroll
+    for (int i = 0; i < kPartU; ++i) k[i] = 0;
+    const size_t base = (size_t)b * 3 * n;
+    const int p0 = blockIdx.x * chunk;
+    const int p1 = min(p0 + chunk, n);
+    for (int p = p0 + (int)threadIdx.x; p < p1; p += 256) {
+        float x[3], g[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const size_t i = planar ? base + (size_t)c * n + p : base + (size_t)p * 3 + c;
+            x[c] = img[i];
+            g[c] = gout[i];
+        }
+        float s0[3], s[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            k[c * 4 + 0] += x[c] < lo[c];
+            k[c * 4 + 1] += x[c] == lo[c];
+            k[c * 4 + 2] += x[c] < hi[c];
+            k[c * 4 + 3] += x[c] == hi[c];
+            s0[c] = (x[c] - lo[c]) / rng[c];
+            s[c] = clamp01(s0[c]);
+        }
+        // forward: dehaze, gamma
+        float y[3], d1[3], d2[3], dark = 0.0f, t0 = 1.0f, t = 1.0f;
+        int am = 0;
+        if (FLAGS & 1) {
+            dark = s[0];
+            if (s[1] < dark) { dark = s[1]; am = 1; }
+            if (s[2] < dark) { dark = s[2]; am = 2; }
+            t0 = 1.0f - omega * dark;
+            t = fminf(fmaxf(t0, 0.1f), 1.0f);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                d1[c] = (s[c] - 0.6f) / t;
+                d2[c] = d1[c] + 0.6f;
+                y[c] = clamp01(d2[c]);
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) y[c] = s[c];
+        }
+        // backward: final clamp, gamma
+        float gy[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (FLAGS & 2) {
+                const float ye = y[c] + 1e-8f;
+                const float z = pow_f32_fast(ye, gamma);
+                const float gz = (z >= 0.0f && z <= 1.0f) ? g[c] : 0.0f;
+                const float dz = gamma * (float)((double)z / (double)ye);
+                gy[c] = gamma == 0.0f ? 0.0f : gz * dz;
+                s_ga += (double)(gz * (z * logf(ye)));
+            } else {
+                gy[c] = (y[c] >= 0.0f && y[c] <= 1.0f) ? g[c] : 0.0f;
+            }
+        }
+        // dehaze: the clamp, (s - 0.6) / t, t = clamp(1 - omega * dark), dark = min_c s
+        float gs[3];
+        if (FLAGS & 1) {
+            float gt = 0.0f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float gd = (d2[c] >= 0.0f && d2[c] <= 1.0f) ? gy[c] : 0.0f;
+                gs[c] = gd / t;
+                const float term = -gd * (d1[c] / t);
+                gt = c == 0 ? term : gt + term;
+            }
+            const float gm = -((t0 >= 0.1f && t0 <= 1.0f) ? gt : 0.0f);
+            s_om += (double)(gm * dark);
+            const float gdark = gm * omega;
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                if (c == am) gs[c] = gs[c] + gdark;
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) gs[c] = gy[c];
+        }
+        // stretch: the clamp, (x - p_lo) / r
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float g0 = (s0[c] >= 0.0f && s0[c] <= 1.0f) ? gs[c] : 0.0f;
+            const float gx = g0 / rng[c];
+            s_x[c] += (double)gx;
+            s_r[c] += (double)(-g0 * (s0[c] / rng[c]));
+            if (gimg) gimg[planar ? base + (size_t)c * n + p : base + (size_t)p * 3 + c] = gx;
+        }
+    }
+    // block totals: wave sums, then the four waves in order (fixed order: the same bits every run)
+    __shared__ double sd[4][kPartD];
+    __shared__ uint32_t su[4][kPartU];
+    double v[kPartD] = {s_om, s_ga, s_x[0], s_x[1], s_x[2], s_r[0], s_r[1], s_r[2]};
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < kPartD; ++i) {
+        double a = v[i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+        if (lane == 0) sd[wid][i] = a;
+    }
+#pragma unroll
+    for (int i = 0; i < kPartU; ++i) {
+        const uint32_t a = wave_sum_u32(k[i]);
+        if (lane == 0) su[wid][i] = a;
+    }
+    __syncthreads();
+    const size_t slot = (size_t)b * gridDim.x + blockIdx.x;
+    if (threadIdx.x < kPartD) {
+        const int i = threadIdx.x;
+        part[slot * kPartD + i] = ((sd[0][i] + sd[1][i]) + sd[2][i]) + sd[3][i];
+    } else if (threadIdx.x >= 64 && threadIdx.x < 64 + kPartU) {
+        const int i = threadIdx.x - 64;
+        cnt[slot * kPartU + i] = su[0][i] + su[1][i] + su[2][i] + su[3][i];
+    }
+}
+
+// One block per (plane c, image b): the plane's partials in block order, then the element each order statistic's gradient
+// goes to.  torch.sort is stable on the CPU, so sorted position k of value p is the (k - #{x < p})-th element equal to p
+// in linear index order: the block's equal counts find the chunk, one pass over that chunk finds the element.
+// grad_params[b] = {0, 0, grad omega, grad gamma} (plane 0's block).
+__global__ void __launch_bounds__(256) k_diff_enhance_bwd_finish(const float *__restrict__ img, int planar, int n, int chunk,
+                                                                 int gx, const float *__restrict__ params,
+                                                                 const float *__restrict__ saved,
+                                                                 const double *__restrict__ part,
+                                                                 const uint32_t *__restrict__ cnt, float *__restrict__ gimg,
+                                                                 float *__restrict__ gparams)
+{
+    const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    __shared__ double rd[4][256];
+    __shared__ uint32_t ru[4][256];
+    double v[4] = {0.0, 0.0, 0.0, 0.0};  // grad omega, grad gamma, sum grad_x, dL/dr
+    uint32_t u[4] = {0, 0, 0, 0};        // x < p_lo, x == p_lo, x < p_hi, x == p_hi
+    for (int i = tid; i < gx; i += 256) {
+        const double *pp = part + ((size_t)b * gx + i) * kPartD;
+        const uint32_t *cc = cnt + ((size_t)b * gx + i) * kPartU + c * 4;
+        v[0] += pp[0];
+        v[1] += pp[1];
+        v[2] += pp[2 + c];
+        v[3] += pp[5 + c];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) u[q] += cc[q];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        rd[q][tid] = v[q];
+        ru[q][tid] = u[q];
+    }
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                rd[q][tid] += rd[q][tid + w];
+                ru[q][tid] += ru[q][tid + w];
+            }
+        }
+        __syncthreads();
+    }
+    if (c == 0 && tid == 0) {
+        gparams[b * 4 + 0] = 0.0f;
+        gparams[b * 4 + 1] = 0.0f;
+        gparams[b * 4 + 2] = (float)rd[0][0];
+        gparams[b * 4 + 3] = (float)rd[1][0];
+    }
+    if (!gimg) return;
+    // grad p_lo = -sum grad_x - dL/dr, grad p_hi = dL/dr (r = p_hi - p_lo + 1e-8)
+    const float g_lo = (float)(-rd[2][0] - rd[3][0]), g_hi = (float)rd[3][0];
+    const long long k_lo = stretch_rank(params[b * 4 + 0], n), k_hi = stretch_rank(params[b * 4 + 1], n);
+    const size_t base = (size_t)b * 3 * n;
+    __shared__ int s_blk, s_pos;
+    __shared__ long long s_j;
+    __shared__ uint32_t s_wave[4];
+    int pos[2] = {-1, -1};
+    for (int q = 0; q < 2; ++q) {
+        if (q == 1 && k_hi == k_lo) {
+            pos[1] = pos[0];
+            break;
+        }
+        const float pv = saved[(b * 3 + c) * 2 + q];
+        const long long j = (q ? k_hi : k_lo) - (long long)ru[2 * q][0];  // rank among the elements equal to pv
+        if (tid == 0) {
+            s_blk = -1;
+            s_pos = -1;
+            long long acc = 0;
+            for (int i = 0; i < gx && j >= 0; ++i) {
+                const uint32_t e = cnt[((size_t)b * gx + i) * kPartU + c * 4 + 2 * q + 1];
+                if (j < acc + e) {
+                    s_blk = i;
+                    s_j = j - acc;
+                    break;
+                }
+                acc += e;
+            }
+        }
+        __syncthreads();
+        const int blk = s_blk;
+        if (blk >= 0) {
+            const int p0 = blk * chunk, p1 = min(p0 + chunk, n);
+            long long left = s_j;  // equal elements still to pass
+            for (int t0 = p0; t0 < p1; t0 += 256) {
+                const int p = t0 + tid;
+                const bool eq = p < p1 && img[planar ? base + (size_t)c * n + p : base + (size_t)p * 3 + c] == pv;
+                const uint64_t m = __ballot(eq);
+                const uint32_t before = __popcll(m & ((1ull << (tid & 63)) - 1ull));
+                if ((tid & 63) == 0) s_wave[tid >> 6] = (uint32_t)__popcll(m);
+                __syncthreads();
+                uint32_t wbefore = 0, total = 0;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    wbefore += w < (tid >> 6) ? s_wave[w] : 0;
+                    total += s_wave[w];
+                }
+                if (eq && (long long)(wbefore + before) == left) s_pos = p;
+                __syncthreads();
+                if (s_pos >= 0 || left < (long long)total) break;  // uniform: every thread reads the same values
+                left -= total;
+            }
+        }
+        pos[q] = s_pos;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        if (k_lo == k_hi) {
+            if (pos[0] >= 0) {
+                const size_t i = planar ? base + (size_t)c * n + pos[0] : base + (size_t)pos[0] * 3 + c;
+                gimg[i] = gimg[i] + (g_lo + g_hi);
+            }
+        } else {
+            for (int q = 0; q < 2; ++q) {
+                if (pos[q] < 0) continue;
+                const size_t i = planar ? base + (size_t)c * n + pos[q] : base + (size_t)pos[q] * 3 + c;
+                gimg[i] = gimg[i] + (q ? g_hi : g_lo);
+            }
+        }
+    }
+}
+
+// pixels per block of the backward sweep and the cap on blocks per image (the partials' size)
+constexpr int kBwdPxPerBlock = 2048, kBwdMaxBlocks = 512;
+struct BwdGeom {
+    int gx, chunk;
+};
+BwdGeom bwd_geom(Shape s)
+{
+    const long long n = (long long)s.npx();
+    int gx = cdiv(n, kBwdPxPerBlock);
+    if (gx > kBwdMaxBlocks) gx = kBwdMaxBlocks;
+    int chunk = cdiv(n, gx);
+    chunk = (chunk + 255) & ~255;  // whole 256-pixel tiles
+    return {cdiv(n, chunk), chunk};
+}
+
 }  // namespace
 
 int launch_diff_enhance(const float *d_img, int planar, Shape s, const float *d_params, int flags, const float *d_os,
-                        float *d_out, hipStream_t st)
+                        float *d_out, hipStream_t st, float *d_saved)
 {
     const int n = (int)s.npx();
     UWIE_LAUNCH(k_diff_enhance, dim3(grid_for(n, 4096), s.B), dim3(256), 0, st, d_img, planar, n, d_params, flags, d_os,
-                d_out);
+                d_out, d_saved);
+    UWIE_LAUNCH_CHECK();
+    return UWIE_OK;
+}
+
+size_t diff_enhance_bwd_ws_bytes(Shape s)
+{
+    const BwdGeom g = bwd_geom(s);
+    Carver c(nullptr);
+    c.take<double>((size_t)s.B * g.gx * kPartD);
+    c.take<uint32_t>((size_t)s.B * g.gx * kPartU);
+    return c.total();
+}
+
+int launch_diff_enhance_bwd(const float *d_img, int planar, Shape s, const float *d_params, int flags, const float *d_saved,
+                            const float *d_grad_out, float *d_grad_img, float *d_grad_params, void *ws, hipStream_t st)
+{
+    const int n = (int)s.npx();
+    const BwdGeom g = bwd_geom(s);
+    Carver c(ws);
+    double *part = c.take<double>((size_t)s.B * g.gx * kPartD);
+    uint32_t *cnt = c.take<uint32_t>((size_t)s.B * g.gx * kPartU);
+    const dim3 grid(g.gx, s.B);
+    switch (flags & 3) {
+    case 0: UWIE_LAUNCH(k_diff_enhance_bwd<0>, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_grad_img, part, cnt); break;
+    case 1: UWIE_LAUNCH(k_diff_enhance_bwd<1>, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_grad_img, part, cnt); break;
+    case 2: UWIE_LAUNCH(k_diff_enhance_bwd<2>, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_grad_img, part, cnt); break;
+    default: UWIE_LAUNCH(k_diff_enhance_bwd<3>, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_grad_img, part, cnt); break;
+    }
+    UWIE_LAUNCH_CHECK();
+    UWIE_LAUNCH(k_diff_enhance_bwd_finish, dim3(3, s.B), dim3(256), 0, st, d_img, planar, n, g.chunk, g.gx, d_params, d_saved,
+                part, cnt, d_grad_img, d_grad_params);
     UWIE_LAUNCH_CHECK();
     return UWIE_OK;
 }

@@ -226,6 +226,35 @@ class Device:
                                              self.stream()))
         return out
 
+    def diff_enhance_save_f32(self, img, params, planar: bool, flags: int):
+        """diff_enhance_f32 that also returns what the backward needs: (out, saved float32 [B,3,2] = p_lo, p_hi per plane)."""
+        assert img.dtype == torch.float32 and params.dtype == torch.float32 and img.dim() == 4
+        B = img.shape[0]
+        H, W = (img.shape[2], img.shape[3]) if planar else (img.shape[1], img.shape[2])
+        assert img.shape[1 if planar else 3] == 3 and tuple(params.shape) == (B, 4)
+        img, params = img.contiguous(), params.contiguous()
+        ws = self.workspace_for(B, H, W)
+        out = self.empty(tuple(img.shape), torch.float32)
+        saved = self.empty((B, 3, 2), torch.float32)
+        check(self.lib.uwie_diff_enhance_save_f32(self._ctx, _ptr(img), _ptr(out), B, H, W, int(planar), _ptr(params), int(flags),
+                                                  _ptr(saved), _ptr(ws), ws.numel(), self.stream()))
+        return out, saved
+
+    def diff_enhance_bwd_f32(self, img, params, saved, grad_out, planar: bool, flags: int, want_img: bool = True):
+        """Gradient of diff_enhance: (grad_img in img's layout or None when not wanted, grad_params float32 [B,4] =
+        0, 0, d omega, d gamma)."""
+        assert img.dtype == torch.float32 and grad_out.dtype == torch.float32 and tuple(grad_out.shape) == tuple(img.shape)
+        B = img.shape[0]
+        H, W = (img.shape[2], img.shape[3]) if planar else (img.shape[1], img.shape[2])
+        img, params, saved, grad_out = img.contiguous(), params.contiguous(), saved.contiguous(), grad_out.contiguous()
+        ws = self.workspace(self.lib.uwie_diff_enhance_bwd_workspace_bytes(B, H, W))
+        grad_img = self.empty(tuple(img.shape), torch.float32) if want_img else None
+        grad_params = self.empty((B, 4), torch.float32)
+        check(self.lib.uwie_diff_enhance_bwd_f32(self._ctx, _ptr(img), _ptr(params), int(flags), int(planar), B, H, W, _ptr(saved),
+                                                 _ptr(grad_out), _ptr(grad_img), _ptr(grad_params), _ptr(ws), ws.numel(),
+                                                 self.stream()))
+        return grad_img, grad_params
+
     def extract_features_u8(self, frames):
         """frames: uint8 cuda tensor [B,H,W,3] -> float32 [B,79] (vgg_16_UIE.extract_all_features per frame)."""
         B, H, W = self._bhw(frames)
