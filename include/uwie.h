@@ -127,6 +127,9 @@ void uwie_destroy(uwie_ctx *ctx);
  *                              fell outside the interval derived from its byte histogram, or the histogram route's decision
  *                              differs from the reference-order argmax: the rounding bounds of k_q_decide / k_q_tail are too tight. */
 #define UWIE_STATUS_QTREE_BOUNDS 4u
+/*   UWIE_STATUS_FEATURE_COUNTS  uwie_feature_extractor_u8 (k_extractor.hip k_fx_finish): the gray or the LBP histogram of a frame
+ *                               does not hold every pixel once: that frame's features are not valid. */
+#define UWIE_STATUS_FEATURE_COUNTS 8u
 int uwie_device_status(uwie_ctx *ctx, void *stream, uint32_t *bits);
 
 /* Per-kernel timing for benchmarks (no reference counterpart; the reference only has a per-image wall clock,
@@ -282,6 +285,28 @@ int uwie_extract_features_u8(uwie_ctx *ctx, const uint8_t *d_in, float *d_featur
  */
 int uwie_quality_scores(uwie_ctx *ctx, const uint8_t *d_u8, const float *d_f32, int batch, int H, int W, int gray_shift,
                         const double *weights8, double *d_scores, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * feature_extraction.FeatureExtractor.extract_all_features (feature_extraction.py:252-295; main.py:116 builds the classifier's
+ * training rows with it, main.py:420 predicts with it).  d_u8: the quantised frames (img * 255).astype(uint8), [batch][H][W][3];
+ * d_f32 (optional): the float image itself, [batch][H][W][3] float32, read by the RGB block only (feature_extraction.py:69-76;
+ * NULL: u8 / 255).  d_features: [batch][uwie_feature_extractor_count(H, W)] float64 in the reference's order:
+ *   0-34  extract_color_features (:17-79): LAB L, a, b mean / std / skew / kurtosis (SciPy's NaN when m2 <= (eps32 * mean)^2),
+ *         HSV mean / std, colour cast factor, M, D, mean a, mean b, then R, G, B mean / std / min / max
+ *   35-56 extract_texture_features (:81-126): uniform LBP (P = 8, R = 1) histogram, GLCM props of the 128x128 resize
+ *   57-61 extract_frequency_features (:128-165): DCT energy fractions, mean and std of |dct|; absent when H or W is odd and
+ *         greater than 1 (cv2.dct refuses; the reference's try / except drops the block): 74 values then
+ *   ...   extract_edge_features (:167-206): Sobel, Canny (50, 150) density, Laplacian (ksize 3); extract_quality_features
+ *         (:208-250): contrast, entropy, mean, median, p25, p75, range, saturation mean / std, RMS contrast.
+ * gray_shift: RGB2GRAY coefficients (15: OpenCV 4.x; 14: older).  Histogram- and integer-derived values are exact; the float
+ * statistics are evaluated in float64 (NumPy: float32); the DCT is float32 MFMA.  Results do not depend on the batch.
+ * A frame's histograms that do not count every pixel set UWIE_STATUS_FEATURE_COUNTS.
+ * Workspace: uwie_workspace_bytes_feature_extractor(batch, H, W) (about 6 bytes per pixel with the DCT, 1 without).
+ */
+int uwie_feature_extractor_count(int H, int W);
+size_t uwie_workspace_bytes_feature_extractor(int batch, int H, int W);
+int uwie_feature_extractor_u8(uwie_ctx *ctx, const uint8_t *d_u8, const float *d_f32, int batch, int H, int W, int gray_shift,
+                              double *d_features, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /*
  * The labelling loop of main.py:118-146 for a batch: every parameter set ps[0 .. n-1] (Config.STRATEGIES, config.py:28-75:

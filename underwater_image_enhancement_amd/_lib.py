@@ -86,6 +86,9 @@ SIGNATURES = {
     "uwie_diff_enhance_bwd_workspace_bytes": [_I, _I, _I],
     "uwie_diff_enhance_bwd_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP],
     "uwie_extract_features_u8": [_VP, _VP, _VP, _I, _I, _I, _VP, _SZ, _VP],
+    "uwie_feature_extractor_count": [_I, _I],
+    "uwie_workspace_bytes_feature_extractor": [_I, _I, _I],
+    "uwie_feature_extractor_u8": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _SZ, _VP],
     "uwie_quality_scores": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _SZ, _VP],
     "uwie_cast_classify": [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _SZ, _VP],
     "uwie_normalise_correct": [_VP, _VP, _VP, _VP, _I, _I, _I, _VP],
@@ -115,6 +118,7 @@ _RESTYPES = {
     "uwie_workspace_bytes_float": ctypes.c_size_t,
     "uwie_workspace_bytes_select": ctypes.c_size_t,
     "uwie_diff_enhance_bwd_workspace_bytes": ctypes.c_size_t,
+    "uwie_workspace_bytes_feature_extractor": ctypes.c_size_t,
 }
 
 _lib = None

@@ -421,6 +421,107 @@ def extract_all_features(img, device: int | None = None):
     return _finish(dev.extract_features_u8(batch), was_numpy, single)
 
 
+# feature_extraction.FeatureExtractor (feature_extraction.py:13-295): the classifier input of main.py:116,420
+FEATURE_EXTRACTOR_KEYS = (
+    [f"lab_{c}_{s}" for c in "Lab" for s in ("mean", "std", "skew", "kurtosis")]
+    + [f"hsv_{c}_{s}" for c in "HSV" for s in ("mean", "std")]
+    + ["ccf", "ccf_M", "ccf_D", "lab_a_mean_ccf", "lab_b_mean_ccf"]
+    + [f"rgb_{c}_{s}" for c in "RGB" for s in ("mean", "std", "min", "max")]
+    + [f"lbp_{i}" for i in range(10)]
+    + [f"glcm_{p}_{s}" for p in ("contrast", "dissimilarity", "homogeneity", "energy", "correlation", "ASM") for s in ("mean", "std")]
+    + ["dct_low", "dct_mid", "dct_high", "dct_abs_mean", "dct_abs_std"]
+    + ["sobel_mean", "sobel_std", "sobel_max", "canny_density", "laplacian_abs_mean", "laplacian_std", "laplacian_var"]
+    + ["gray_std", "gray_entropy", "gray_mean", "gray_median", "gray_p25", "gray_p75", "gray_range", "sat_mean", "sat_std",
+       "rms_contrast"])
+_FX_GROUPS = {"color": (0, 35), "texture": (35, 57), "frequency": (57, 62), "edge": (62, 69), "quality": (69, 79)}
+
+
+def feature_extractor_keys(H: int, W: int):
+    """Names of the values ``extract_all_features`` returns for an HxW frame (the DCT block is absent when H or W is odd > 1)."""
+    if _lib.load().uwie_feature_extractor_count(int(H), int(W)) == 79:
+        return list(FEATURE_EXTRACTOR_KEYS)
+    return FEATURE_EXTRACTOR_KEYS[:57] + FEATURE_EXTRACTOR_KEYS[62:]
+
+
+def feature_extractor_rows(frames, frames_f32=None, device: int | None = None):
+    """``FeatureExtractor.extract_all_features`` for a batch in one device call: ``[B,H,W,3]`` uint8 (NumPy or a ROCm tensor)
+    -> ``[B,79]`` float64 (``[B,74]`` when H or W is odd and > 1); a single ``[H,W,3]`` frame gives one row.  ``frames_f32``
+    (optional, float32, same shape): the float images the frames were quantised from, read by the RGB block (indices 23-34)."""
+    dev = get_device(device)
+    batch, was_numpy, single = _as_batch_u8(frames, dev)
+    f32 = None
+    if frames_f32 is not None:
+        f32 = frames_f32 if hasattr(frames_f32, "data_ptr") else dev.tensor(np.ascontiguousarray(frames_f32, dtype=np.float32))
+        if f32.dim() == 3:
+            f32 = f32[None]
+    out = dev.feature_extractor(batch, f32)
+    dev.check_status()
+    return _finish(out, was_numpy, single)
+
+
+class FeatureExtractor:
+    """Mirror of ``feature_extraction.FeatureExtractor`` (feature_extraction.py:13-295) on the device.  Every method takes an
+    HxWx3 RGB image, float in [0, 1] like the reference, or a uint8 frame (then the float image is ``u8 / 255``), and
+    returns a float64 vector; ``extract_all_features`` has 79 values (74 when H or W is odd and > 1: the reference's
+    ``cv2.dct`` refuses odd sizes and its ``try`` drops that block).  The group methods are slices of the same device call;
+    ``extract_frequency_features`` raises ``ValueError`` for odd sizes, as the reference's does."""
+
+    device: int | None = None
+
+    @classmethod
+    def _row(cls, img):
+        x = np.asarray(img)
+        if x.ndim != 3 or x.shape[2] != 3:
+            raise ValueError(f"expected an HxWx3 image, got {x.shape}")
+        if x.size == 0:
+            raise ValueError("empty image")
+        if x.dtype == np.uint8:
+            return feature_extractor_rows(x, device=cls.device)
+        if x.dtype.kind != "f":
+            raise TypeError(f"expected a float image in [0, 1] or uint8, got {x.dtype}")
+        if not (np.all(x >= 0) and np.all(x <= 1)):  # (NaN fails both)
+            raise ValueError("float image values must lie in [0, 1]")
+        u8 = (x * 255).astype(np.uint8)  # feature_extraction.py:30,89,134,176,215
+        if x.dtype == np.float32 and np.array_equal(u8.astype(np.float32) / _F255, x):
+            return feature_extractor_rows(u8, device=cls.device)  # u8-derived: its RGB block is the u8 frame's, exactly
+        return feature_extractor_rows(u8, np.ascontiguousarray(x, dtype=np.float32), device=cls.device)
+
+    @classmethod
+    def _group(cls, img, name):
+        row = cls._row(img)
+        lo, hi = _FX_GROUPS[name]
+        if row.size == 74:
+            if name == "frequency":
+                raise ValueError("Odd-size DCT's are not implemented")
+            if lo >= 62:
+                lo, hi = lo - 5, hi - 5
+        return row[lo:hi]
+
+    @classmethod
+    def extract_color_features(cls, img):
+        return cls._group(img, "color")
+
+    @classmethod
+    def extract_texture_features(cls, img):
+        return cls._group(img, "texture")
+
+    @classmethod
+    def extract_frequency_features(cls, img):
+        return cls._group(img, "frequency")
+
+    @classmethod
+    def extract_edge_features(cls, img):
+        return cls._group(img, "edge")
+
+    @classmethod
+    def extract_quality_features(cls, img):
+        return cls._group(img, "quality")
+
+    @classmethod
+    def extract_all_features(cls, img):
+        return cls._row(img)
+
+
 # ------------------------------------------------------------------ float <-> u8 bridging
 def _recover_u8(img):
     """Invert ``u8.astype(float32)/255`` [+ ``color_correction``] exactly; returns (u8 frame, cast kind)."""

@@ -626,7 +626,8 @@ int uwie_device_status(uwie_ctx *ctx, void *stream, uint32_t *bits)
         set_error("device status 0x%x:%s the results of the calls since the last check are not valid", v,
                   (v & UWIE_STATUS_CANNY_LABEL) ? " Canny hysteresis met a component label that this launch did not write (k_canny.hip);"
                   : (v & UWIE_STATUS_FALLBACK_SYNC) ? " the percentile fallback's blocks gave up waiting for each other (k_select.hip);"
-                  : (v & UWIE_STATUS_QTREE_BOUNDS) ? " a quadtree score fell outside its histogram interval (k_airlight.hip, tuning q_hist = 3);" : "");
+                  : (v & UWIE_STATUS_QTREE_BOUNDS) ? " a quadtree score fell outside its histogram interval (k_airlight.hip, tuning q_hist = 3);"
+                  : (v & UWIE_STATUS_FEATURE_COUNTS) ? " a frame's feature histograms do not count every pixel (k_extractor.hip);" : "");
         return UWIE_E_DEVICE;
     }
     return UWIE_OK;
@@ -1123,6 +1124,31 @@ int uwie_quality_scores(uwie_ctx *ctx, const uint8_t *d_u8, const float *d_f32, 
     UWIE_CHECK_WS(quality_ws_bytes(s));
     return launch_quality_scores(ctx, d_u8, d_f32, s, gray_shift, weights8 ? weights8 : kDefault, d_scores, d_workspace,
                                  (hipStream_t)stream);
+}
+
+int uwie_feature_extractor_count(int H, int W)
+{
+    UWIE_REQUIRE(H >= 1 && W >= 1, "feature_extractor_count: H and W must be >= 1");
+    return feature_extractor_count(H, W);
+}
+
+size_t uwie_workspace_bytes_feature_extractor(int batch, int H, int W)
+{
+    if (!shape_ok(batch, H, W) || batch > 65535) return 0;
+    return feature_extractor_ws_bytes(Shape{batch, H, W});
+}
+
+int uwie_feature_extractor_u8(uwie_ctx *ctx, const uint8_t *d_u8, const float *d_f32, int batch, int H, int W, int gray_shift,
+                              double *d_features, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE(ctx && d_u8 && d_features, "feature_extractor: NULL pointer");
+    UWIE_SCOPE(ctx);
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_REQUIRE(batch <= 65535, "feature_extractor: batch must be <= 65535");
+    UWIE_REQUIRE(gray_shift == 14 || gray_shift == 15, "gray_shift must be 14 or 15");
+    const Shape s{batch, H, W};
+    UWIE_CHECK_WS(feature_extractor_ws_bytes(s));
+    return launch_feature_extractor(ctx, d_u8, d_f32, s, gray_shift, d_features, d_workspace, (hipStream_t)stream);
 }
 
 /* ---------------------------------------------------------------- stage entry points */

@@ -219,6 +219,13 @@ size_t quality_ws_bytes(Shape s);
 int launch_quality_scores(uwie_ctx *ctx, const uint8_t *d_u8, const float *d_f32, Shape s, int gray_shift,
                           const double *weights8, double *d_scores, void *ws, hipStream_t st);
 
+// k_extractor.hip: feature_extraction.FeatureExtractor.extract_all_features, [B][79] float64 ([B][74]: odd dimension > 1, no DCT)
+bool feature_extractor_has_dct(int H, int W);
+int feature_extractor_count(int H, int W);
+size_t feature_extractor_ws_bytes(Shape s);
+int launch_feature_extractor(uwie_ctx *ctx, const uint8_t *d_u8, const float *d_f32, Shape s, int gray_shift, double *d_out,
+                             void *ws, hipStream_t st);
+
 // best[b] = first argmax over the n strategies of scores[k][b][8]; d_out (optional) [B][H][W][3] = d_all[best[b]][b]
 int launch_pick_best(const double *d_scores, int n, Shape s, const uint8_t *d_all, int32_t *d_best, uint8_t *d_out, hipStream_t st);
 

@@ -265,6 +265,24 @@ class Device:
                                                 self.stream()))
         return out
 
+    def feature_extractor(self, frames_u8, frames_f32=None, gray_shift: int = 15):
+        """feature_extraction.FeatureExtractor.extract_all_features per frame (uwie_feature_extractor_u8): frames_u8 uint8 cuda
+        [B,H,W,3] (the quantised image), frames_f32 optional float32 cuda [B,H,W,3] (read by the RGB block only).  Returns
+        float64 [B,79], or [B,74] when H or W is odd and > 1 (no DCT block, as the reference)."""
+        B, H, W = self._bhw(frames_u8)
+        assert frames_u8.dtype == torch.uint8
+        if frames_f32 is not None:
+            assert frames_f32.dtype == torch.float32 and tuple(frames_f32.shape) == (B, H, W, 3)
+            frames_f32 = frames_f32.contiguous()
+        nbytes = self.lib.uwie_workspace_bytes_feature_extractor(B, H, W)
+        if nbytes == 0:
+            raise _lib.UwieError("feature_extractor: batch/H/W out of range")
+        ws = self.workspace(nbytes)
+        out = self.empty((B, self.lib.uwie_feature_extractor_count(H, W)), torch.float64)
+        check(self.lib.uwie_feature_extractor_u8(self._ctx, _ptr(frames_u8), _ptr(frames_f32), B, H, W, int(gray_shift), _ptr(out),
+                                                 _ptr(ws), ws.numel(), self.stream()))
+        return out
+
     def quality_scores(self, frames_u8, frames_f32=None, weights=None, gray_shift: int = 15):
         """frames_u8: uint8 cuda [B,H,W,3] (the quantised image); frames_f32: optional float32 cuda [B,H,W,3];
         weights: optional 8 floats.  Returns float64 [B,9]: the eight scores (QUALITY_KEYS order) and the total."""
