@@ -130,6 +130,10 @@ void uwie_destroy(uwie_ctx *ctx);
 /*   UWIE_STATUS_FEATURE_COUNTS  uwie_feature_extractor_u8 (k_extractor.hip k_fx_finish): the gray or the LBP histogram of a frame
  *                               does not hold every pixel once: that frame's features are not valid. */
 #define UWIE_STATUS_FEATURE_COUNTS 8u
+/*   UWIE_STATUS_DIFF_RANK  uwie_diff_gated_f32 / _save_f32 (k_select.hip k_sel_init_gated_ranks): an image's L_low or L_high gives
+ *                          no valid sorted position by Python's rules (int(L / 100.0 * n) outside [-n, n - 1]: IndexError;
+ *                          L NaN: ValueError; L infinite: OverflowError).  That image's output and gradients are NaN. */
+#define UWIE_STATUS_DIFF_RANK 16u
 int uwie_device_status(uwie_ctx *ctx, void *stream, uint32_t *bits);
 
 /* Per-kernel timing for benchmarks (no reference counterpart; the reference only has a per-image wall clock,
@@ -265,6 +269,28 @@ size_t uwie_diff_enhance_bwd_workspace_bytes(int batch, int H, int W);
 int uwie_diff_enhance_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_params, int flags, int planar, int batch,
                               int H, int W, const float *d_saved, const float *d_grad_out, float *d_grad_img,
                               float *d_grad_params, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * deep_learning_parameters.DifferentiableEnhancement (deep_learning_parameters.py:24-90), the module EndToEndTrainer trains
+ * through (the contract: DESIGN.md section 10).  Per plane: stretch between the sorted positions k = int(L_low / 100.0 * n)
+ * and int(L_high / 100.0 * n) with Python's indexing rules (no clamp: a negative k counts from the end; an image whose k is
+ * outside [-n, n - 1] or whose L is not finite sets UWIE_STATUS_DIFF_RANK and gets NaN) -> e = 1.0 / gamma (float32,
+ * correctly rounded) -> z = pow(s + 1e-8, e) -> clamp(use_gamma * z + (1 - use_gamma) * s, 0, 1).
+ * d_params: [batch][4] float32 = {L_low, L_high, use_gamma, gamma}; flags: reserved, 0.  Other arguments, layouts, d_saved
+ * and the workspaces are those of the uwie_diff_enhance_* family above (forward workspace: uwie_workspace_bytes).
+ *   uwie_diff_gated_bwd_f32: d_grad_params [batch][4] = {0, 0, dL/d(use_gamma), dL/d(gamma)}; d_grad_img optional (NULL:
+ *     skipped); the same fixed-order float64 sums and stable-sort scatter, two kernel launches.
+ * Bit-exact against torch on the CPU except pow (<= 1 float32 ulp; with use_gamma == 0 the output is exact).
+ */
+int uwie_diff_gated_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, int planar,
+                        const float *d_params, int flags, void *d_workspace, size_t workspace_bytes, void *stream);
+int uwie_diff_gated_save_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, int planar,
+                             const float *d_params, int flags, float *d_saved, void *d_workspace, size_t workspace_bytes,
+                             void *stream);
+size_t uwie_diff_gated_bwd_workspace_bytes(int batch, int H, int W);
+int uwie_diff_gated_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_params, int flags, int planar, int batch, int H,
+                            int W, const float *d_saved, const float *d_grad_out, float *d_grad_img, float *d_grad_params,
+                            void *d_workspace, size_t workspace_bytes, void *stream);
 
 /*
  * vgg_16_UIE.extract_all_features (vgg_16_UIE.py:435-466) for uint8 frames: d_features [batch][79] float32 =

@@ -10,6 +10,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libuwie.so")
 CSRC = os.path.join(_HERE, "csrc")
 
 SURFACE_SIX, SURFACE_DICT = 0, 1
+STATUS_DIFF_RANK = 16  # include/uwie.h UWIE_STATUS_DIFF_RANK
 INTER_F64, INTER_FX32, INTER_F32T = 0, 1, 2  # uwie_params.inter_dtype
 DICT_STRATEGIES = {
     "strong_dehazing": 0,
@@ -85,6 +86,10 @@ SIGNATURES = {
     "uwie_diff_enhance_save_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _SZ, _VP],
     "uwie_diff_enhance_bwd_workspace_bytes": [_I, _I, _I],
     "uwie_diff_enhance_bwd_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP],
+    "uwie_diff_gated_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _SZ, _VP],
+    "uwie_diff_gated_save_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _SZ, _VP],
+    "uwie_diff_gated_bwd_workspace_bytes": [_I, _I, _I],
+    "uwie_diff_gated_bwd_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP],
     "uwie_extract_features_u8": [_VP, _VP, _VP, _I, _I, _I, _VP, _SZ, _VP],
     "uwie_feature_extractor_count": [_I, _I],
     "uwie_workspace_bytes_feature_extractor": [_I, _I, _I],
@@ -118,6 +123,7 @@ _RESTYPES = {
     "uwie_workspace_bytes_float": ctypes.c_size_t,
     "uwie_workspace_bytes_select": ctypes.c_size_t,
     "uwie_diff_enhance_bwd_workspace_bytes": ctypes.c_size_t,
+    "uwie_diff_gated_bwd_workspace_bytes": ctypes.c_size_t,
     "uwie_workspace_bytes_feature_extractor": ctypes.c_size_t,
 }
 

@@ -311,6 +311,111 @@ class DifferentiableEnhancement:
         return np.clip(out, 0.0, 1.0)
 
 
+# ------------------------------------------------------------------ deep_learning_parameters.DifferentiableEnhancement
+class GatedDiffEnhanceFunction(torch.autograd.Function):
+    """``out = GatedDiffEnhanceFunction.apply(img, params, planar, dev)``: the gated module's device forward with its backward.
+
+    ``img``: float32 ``[B,3,H,W]`` (planar) or ``[B,H,W,3]`` on ``dev``; ``params``: float32 ``[B,4]`` =
+    ``L_low, L_high, use_gamma, gamma``.  The gradient is the one torch autograd gives the reference module on the CPU
+    (DESIGN.md section 10): ``params`` gets ``0, 0, d use_gamma, d gamma``; ``img`` gets its gradient only when it requires
+    one.  An image without a valid sorted position gets NaN and sets UWIE_STATUS_DIFF_RANK: this function does not check
+    it (``GatedDifferentiableEnhancement`` does).
+    """
+
+    @staticmethod
+    def forward(ctx, img, params, planar, dev):
+        out, saved = dev.diff_gated_save_f32(img, params, planar)
+        ctx.save_for_backward(img, params, saved)
+        ctx.planar, ctx.dev = planar, dev
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        img, params, saved = ctx.saved_tensors
+        grad_img, grad_params = ctx.dev.diff_gated_bwd_f32(img, params, saved, grad_out.float().contiguous(), ctx.planar,
+                                                           want_img=ctx.needs_input_grad[0])
+        return grad_img, (grad_params if ctx.needs_input_grad[1] else None), None, None
+
+
+def _raise_rank_error(L, n: int):
+    """Raise what ``color_stretch`` (deep_learning_parameters.py:73-77) raises first for ``L`` float32 ``[B,2]``: per image
+    ``int(L_low / 100.0 * n)``, ``int(L_high / 100.0 * n)`` (ValueError for NaN, OverflowError for inf), then the two
+    indexings (IndexError outside ``[-n, n - 1]``, ValueError beyond int64: torch's messages)."""
+    for lo, hi in np.asarray(L, dtype=np.float32).reshape(-1, 2):
+        ks = [int(float(v) / 100.0 * n) for v in (lo, hi)]
+        for k in ks:
+            if not -2**63 <= k < 2**63:
+                raise ValueError("Overflow when unpacking long long")
+            if not -n <= k < n:
+                raise IndexError(f"index {k} is out of bounds for dimension 0 with size {n}")
+
+
+class GatedDifferentiableEnhancement:
+    """``deep_learning_parameters.DifferentiableEnhancement`` (deep_learning_parameters.py:24-90) on the device, forward and
+    backward: the module ``EndToEndTrainer`` trains through.
+
+    ``forward(img, params)``: ``img`` is ``(B, 3, H, W)`` float32 (NumPy or torch ROCm tensor), ``params`` a dict of
+    ``(B, 1)``-shaped values with all four of the reference's keys, ``L_low``, ``L_high``, ``use_gamma`` and ``gamma`` (a
+    missing one raises ``KeyError``).  Per plane: stretch between the sorted positions ``int(L / 100.0 * n)`` (Python's
+    indexing rules, no clamp), then ``clamp(use_gamma * pow(s + 1e-8, 1.0 / gamma) + (1 - use_gamma) * s, 0, 1)``.
+
+    Differentiable: with grad mode on and ``img`` or a parameter tensor requiring grad, the output carries a ``grad_fn``
+    and ``loss.backward()`` runs the gradient kernels (``GatedDiffEnhanceFunction``).  ``use_gamma`` and ``gamma`` get the
+    gradient torch autograd gives the reference on the CPU, in their own dtype and device; ``L_low`` and ``L_high`` get none
+    (the reference reads them with ``.item()``); ``img`` gets one when it requires it.  Otherwise the forward alone runs,
+    with the same output bytes.
+
+    Errors: each call waits for the device once, after the forward.  A sorted position the reference could not index raises
+    the exception the reference raises there: ``IndexError`` (outside ``[-n, n - 1]``), ``ValueError`` (NaN ``L``, or a
+    position beyond int64), ``OverflowError`` (infinite ``L``).  Every other device status bit still raises ``UwieError``.
+    """
+
+    device: int | None = None
+    KEYS = ("L_low", "L_high", "use_gamma", "gamma")
+
+    @staticmethod
+    def _wants_grad(img, params) -> bool:
+        if not torch.is_grad_enabled():
+            return False
+        vals = [img] + [params[k] for k in GatedDifferentiableEnhancement.KEYS]
+        return any(isinstance(v, torch.Tensor) and v.requires_grad for v in vals)
+
+    @staticmethod
+    def _image(dev: Device, img):
+        x = img.to(dev.torch_device) if isinstance(img, torch.Tensor) else dev.tensor(np.ascontiguousarray(img, dtype=np.float32))
+        if x.dtype != torch.float32:
+            raise ValueError(f"expected a float32 image batch, got {x.dtype}")
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"expected a (B, 3, H, W) image batch, got {tuple(x.shape)}")
+        return x
+
+    def forward(self, img, params):
+        vals = [params[k] for k in self.KEYS]  # KeyError in the reference's order
+        dev = get_device(self.device)
+        was_numpy = not isinstance(img, torch.Tensor)
+        grad = self._wants_grad(img, params)
+        x = self._image(dev, img)
+        B = x.shape[0]
+        cols = []
+        for key, v in zip(self.KEYS, vals):
+            v = (v.to(device=dev.torch_device, dtype=torch.float32) if isinstance(v, torch.Tensor)
+                 else torch.as_tensor(np.asarray(v, dtype=np.float32), device=dev.torch_device))
+            if key in ("L_low", "L_high") or not grad:
+                v = v.detach()  # sorted positions: no gradient (deep_learning_parameters.py:73-74 reads them with .item())
+            cols.append(torch.broadcast_to(v.reshape(-1), (B,)))
+        pt = torch.stack(cols, dim=1).contiguous()
+        if grad:
+            out = GatedDiffEnhanceFunction.apply(x, pt, True, dev)
+        else:
+            out = dev.diff_gated_f32(x, pt, planar=True)
+        if dev.check_status(allow=_lib.STATUS_DIFF_RANK) & _lib.STATUS_DIFF_RANK:
+            _raise_rank_error(pt[:, :2].detach().cpu().numpy(), x.shape[2] * x.shape[3])
+            raise _lib.UwieError("diff_gated: the device flagged a sorted position that the host finds valid")
+        return out.detach().cpu().numpy() if was_numpy and not grad else out
+
+    __call__ = forward
+
+
 QUALITY_KEYS = ("contrast", "sharpness", "entropy", "saturation", "brightness", "edge_density", "colorfulness", "naturalness")
 
 

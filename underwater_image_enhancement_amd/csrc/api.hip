@@ -627,7 +627,8 @@ int uwie_device_status(uwie_ctx *ctx, void *stream, uint32_t *bits)
                   (v & UWIE_STATUS_CANNY_LABEL) ? " Canny hysteresis met a component label that this launch did not write (k_canny.hip);"
                   : (v & UWIE_STATUS_FALLBACK_SYNC) ? " the percentile fallback's blocks gave up waiting for each other (k_select.hip);"
                   : (v & UWIE_STATUS_QTREE_BOUNDS) ? " a quadtree score fell outside its histogram interval (k_airlight.hip, tuning q_hist = 3);"
-                  : (v & UWIE_STATUS_FEATURE_COUNTS) ? " a frame's feature histograms do not count every pixel (k_extractor.hip);" : "");
+                  : (v & UWIE_STATUS_FEATURE_COUNTS) ? " a frame's feature histograms do not count every pixel (k_extractor.hip);"
+                  : (v & UWIE_STATUS_DIFF_RANK) ? " a gated DifferentiableEnhancement image has no valid sorted position (an IndexError, ValueError or OverflowError in Python);" : "");
         return UWIE_E_DEVICE;
     }
     return UWIE_OK;
@@ -1099,6 +1100,62 @@ int uwie_diff_enhance_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_
     UWIE_CHECK_WS(diff_enhance_bwd_ws_bytes(s));
     return launch_diff_enhance_bwd(d_img, planar ? 1 : 0, s, d_params, flags, d_saved, d_grad_out, d_grad_img, d_grad_params,
                                    d_workspace, (hipStream_t)stream);
+}
+
+// deep_learning_parameters.DifferentiableEnhancement: flags is reserved (0)
+static int diff_gated_fwd(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, int planar,
+                          const float *d_params, float *d_saved, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    const Shape s{batch, H, W};
+    UWIE_CHECK_WS(select_ws_bytes(s));
+    hipStream_t st = (hipStream_t)stream;
+    SelectPlan plan;
+    UWIE_TRY(select_begin_gated_ranks(s, d_params, 4, ctx->d_status, d_workspace, st, &plan));
+    UWIE_TRY(select_run(plan, d_img, planar ? 1 : 0, s, false, st));
+    return launch_diff_gated(d_img, planar ? 1 : 0, s, d_params, (const float *)plan.os, d_out, st, d_saved);
+}
+
+int uwie_diff_gated_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, int planar,
+                        const float *d_params, int flags, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE(ctx && d_img && d_out && d_params, "diff_gated: NULL pointer");
+    UWIE_SCOPE(ctx);
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_REQUIRE(flags == 0, "diff_gated: flags are reserved (0)");
+    return diff_gated_fwd(ctx, d_img, d_out, batch, H, W, planar, d_params, nullptr, d_workspace, workspace_bytes, stream);
+}
+
+int uwie_diff_gated_save_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, int planar,
+                             const float *d_params, int flags, float *d_saved, void *d_workspace, size_t workspace_bytes,
+                             void *stream)
+{
+    UWIE_REQUIRE(ctx && d_img && d_out && d_params && d_saved, "diff_gated_save: NULL pointer");
+    UWIE_SCOPE(ctx);
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_REQUIRE(flags == 0, "diff_gated_save: flags are reserved (0)");
+    return diff_gated_fwd(ctx, d_img, d_out, batch, H, W, planar, d_params, d_saved, d_workspace, workspace_bytes, stream);
+}
+
+size_t uwie_diff_gated_bwd_workspace_bytes(int batch, int H, int W)
+{
+    if (!shape_ok(batch, H, W)) return 0;
+    return diff_enhance_bwd_ws_bytes(Shape{batch, H, W});
+}
+
+int uwie_diff_gated_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_params, int flags, int planar, int batch, int H,
+                            int W, const float *d_saved, const float *d_grad_out, float *d_grad_img, float *d_grad_params,
+                            void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE(ctx && d_img && d_params && d_saved && d_grad_out && d_grad_params, "diff_gated_bwd: NULL pointer");
+    UWIE_SCOPE(ctx);
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_REQUIRE(flags == 0, "diff_gated_bwd: flags are reserved (0)");
+    UWIE_REQUIRE((const void *)d_grad_img != (const void *)d_img && (const void *)d_grad_img != (const void *)d_grad_out,
+                 "diff_gated_bwd: d_grad_img must not alias d_img or d_grad_out");
+    const Shape s{batch, H, W};
+    UWIE_CHECK_WS(diff_enhance_bwd_ws_bytes(s));
+    return launch_diff_gated_bwd(d_img, planar ? 1 : 0, s, d_params, d_saved, d_grad_out, d_grad_img, d_grad_params, d_workspace,
+                                 (hipStream_t)stream);
 }
 
 int uwie_extract_features_u8(uwie_ctx *ctx, const uint8_t *d_in, float *d_features, int batch, int H, int W,

@@ -338,6 +338,10 @@ int select_lerp(const SelectPlan &plan, Shape s, float *d_out, hipStream_t st); 
 int select_lerp_chain(const SelectPlan &plan, Shape s, float eps, float *d_pct4, hipStream_t st);   // [B][3][4]
 // explicit sorted positions per image (vgg_16_UIE.py:78-82): os[bc*8 + 0/1] = sorted[int(L_low/100*n)], sorted[int(L_high/100*n)]
 int select_begin_stretch_ranks(Shape s, const float *d_params, int stride, void *ws, hipStream_t st, SelectPlan *plan);
+// the same with Python's indexing rules (deep_learning_parameters.py:73-77, devutil.h gated_rank): an image without a valid
+// position selects position 0 and sets UWIE_STATUS_DIFF_RANK in *d_status
+int select_begin_gated_ranks(Shape s, const float *d_params, int stride, uint32_t *d_status, void *ws, hipStream_t st,
+                             SelectPlan *plan);
 // k_diffenh.hip: DifferentiableEnhancement.forward (vgg_16_UIE.py:32-128) after the selection
 // d_saved (optional): [B][3][2] float = {p_lo, p_hi} per plane, what the backward needs from the forward
 int launch_diff_enhance(const float *d_img, int planar, Shape s, const float *d_params, int flags, const float *d_os,
@@ -346,6 +350,12 @@ int launch_diff_enhance(const float *d_img, int planar, Shape s, const float *d_
 size_t diff_enhance_bwd_ws_bytes(Shape s);
 int launch_diff_enhance_bwd(const float *d_img, int planar, Shape s, const float *d_params, int flags, const float *d_saved,
                             const float *d_grad_out, float *d_grad_img, float *d_grad_params, void *ws, hipStream_t st);
+// k_diffenh.hip: deep_learning_parameters.DifferentiableEnhancement.forward (:32-55), the gated gamma module, and its
+// gradient (params [B][4] = L_low, L_high, use_gamma, gamma; images without a valid sorted position get NaN)
+int launch_diff_gated(const float *d_img, int planar, Shape s, const float *d_params, const float *d_os, float *d_out,
+                      hipStream_t st, float *d_saved = nullptr);
+int launch_diff_gated_bwd(const float *d_img, int planar, Shape s, const float *d_params, const float *d_saved,
+                          const float *d_grad_out, float *d_grad_img, float *d_grad_params, void *ws, hipStream_t st);
 // float64 data (ES surface): first digit = f64_key(v) >> 53
 int select_begin64(Shape s, const double *q_percent, int nq, void *ws, hipStream_t st, SelectPlan *plan);
 int select_run64(const SelectPlan &plan, const double *d_vals, int planar, Shape s, bool pass1_done, hipStream_t st);

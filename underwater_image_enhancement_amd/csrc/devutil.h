@@ -233,6 +233,19 @@ __device__ __forceinline__ int reflect101(int p, int len)
     return p;
 }
 
+// deep_learning_parameters.DifferentiableEnhancement.color_stretch (:73-77): sorted_vals[int(L / 100.0 * n)] with Python's
+// rules and no clamp.  int() truncates toward zero (NaN: ValueError, inf: OverflowError); a negative index counts from the
+// end, one outside [-n, n - 1] is an IndexError.  False: no valid position (the caller marks the image, *k = 0).
+__device__ __forceinline__ bool gated_rank(float L, int n, int *k)
+{
+    const double pos = ((double)L / 100.0) * (double)n;
+    *k = 0;
+    if (!(pos > -(double)n - 1.0 && pos < (double)n)) return false;  // also NaN and +-inf
+    const int idx = (int)pos;                                          // trunc, within (-n - 1, n)
+    *k = idx < 0 ? idx + n : idx;
+    return true;
+}
+
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 {
 #pragma unroll

@@ -13,6 +13,12 @@
 // sums of grad omega, grad gamma, grad p_lo / p_hi plus the counts of x < p and x == p that locate the element torch's
 // stable sort routes each order statistic's gradient to; k_diff_enhance_bwd_finish reduces the partials in a fixed order
 // (no atomics: bit-identical runs) and scatters the two scalar terms per plane.
+//
+// Gated gamma (deep_learning_parameters.py:24-90, the module EndToEndTrainer trains through): the same
+// stretch with Python's indexing rules for the sorted positions (devutil.h gated_rank), then e = 1.0 / gamma (float32,
+// correctly rounded), z = pow(s + 1e-8, e), clamp(use_gamma * z + (1 - use_gamma) * s, 0, 1).  k_diff_gated /
+// k_diff_gated_bwd are its forward and backward sweep; the finish kernel is shared (GATED = true).  An image without a
+// valid sorted position gets NaN in its output and gradients (the selection set UWIE_STATUS_DIFF_RANK for it).
 #include "common.h"
 #include "devutil.h"
 
@@ -69,6 +75,40 @@ __global__ void __launch_bounds__(256) k_diff_enhance(const float *__restrict__ 
     }
 }
 
+// the gated module's forward: params[b] = {L_low, L_high, use_gamma, gamma}; saved as in k_diff_enhance
+__global__ void __launch_bounds__(256) k_diff_gated(const float *__restrict__ img, int planar, int n,
+                                                    const float *__restrict__ params, const float *__restrict__ os,
+                                                    float *__restrict__ out, float *__restrict__ saved)
+{
+    const int b = blockIdx.y;
+    if (saved && blockIdx.x == 0 && threadIdx.x < 6) {
+        const int c = threadIdx.x >> 1, q = threadIdx.x & 1;
+        saved[(b * 3 + c) * 2 + q] = os[(size_t)(b * 3 + c) * kSelOsStride + q];
+    }
+    const float *pr = params + b * 4;
+    float lo[3], rng[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float *o = os + (size_t)(b * 3 + c) * kSelOsStride;
+        lo[c] = o[0];
+        rng[c] = (o[1] - o[0]) + 1e-8f;
+    }
+    int k0, k1;
+    const bool ok0 = gated_rank(pr[0], n, &k0), ok1 = gated_rank(pr[1], n, &k1);
+    const bool ok = ok0 && ok1;
+    const float u = pr[2], e = 1.0f / pr[3], om = 1.0f - u;
+    const size_t base = (size_t)b * 3 * n;
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const size_t i = planar ? base + (size_t)c * n + p : base + (size_t)p * 3 + c;
+            const float sv = clamp01((img[i] - lo[c]) / rng[c]);
+            const float z = pow_f32_fast(sv + 1e-8f, e);
+            out[i] = ok ? clamp01(u * z + om * sv) : __builtin_nanf("");
+        }
+    }
+}
+
 // torch.sort position int((L / 100.0) * n) clamped to [0, n - 1] (vgg_16_UIE.py:78-82; k_sel_init_stretch_ranks)
 __device__ __forceinline__ long long stretch_rank(float L, int n)
 {
@@ -79,10 +119,40 @@ __device__ __forceinline__ long long stretch_rank(float L, int n)
 }
 
 // Per-block partials: kPartD float64 sums and kPartU counts per (image, block).
-//   sums:   0 grad omega, 1 grad gamma, 2 + c: sum of grad_x over plane c (the stretch's dL/dx before the scatter),
+//   sums:   0 grad omega (gated: grad use_gamma), 1 grad gamma (gated: grad e, e = 1 / gamma), 2 + c: sum of grad_x over plane c (the stretch's dL/dx before the scatter),
 //           5 + c: dL/dr of plane c (r = p_hi - p_lo + 1e-8)
 //   counts: c * 4 + {0: x < p_lo, 1: x == p_lo, 2: x < p_hi, 3: x == p_hi}
 constexpr int kPartD = 8, kPartU = 12;
+
+// The block's totals of a backward sweep: wave sums, then the four waves in order (fixed order: the same bits every run).
+__device__ __forceinline__ void store_partials(const double (&v)[kPartD], const uint32_t (&k)[kPartU], double *__restrict__ part,
+                                               uint32_t *__restrict__ cnt)
+{
+    __shared__ double sd[4][kPartD];
+    __shared__ uint32_t su[4][kPartU];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < kPartD; ++i) {
+        double a = v[i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+        if (lane == 0) sd[wid][i] = a;
+    }
+#pragma unroll
+    for (int i = 0; i < kPartU; ++i) {
+        const uint32_t a = wave_sum_u32(k[i]);
+        if (lane == 0) su[wid][i] = a;
+    }
+    __syncthreads();
+    const size_t slot = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (threadIdx.x < kPartD) {
+        const int i = threadIdx.x;
+        part[slot * kPartD + i] = ((sd[0][i] + sd[1][i]) + sd[2][i]) + sd[3][i];
+    } else if (threadIdx.x >= 64 && threadIdx.x < 64 + kPartU) {
+        const int i = threadIdx.x - 64;
+        cnt[slot * kPartU + i] = su[0][i] + su[1][i] + su[2][i] + su[3][i];
+    }
+}
 
 // One contiguous chunk of `chunk` pixels of one image per block, so that the equal counts of the blocks, in block order,
 // are the equal counts of the plane in linear index order (what the finish kernel scans for the stable-sort position).
@@ -194,38 +264,78 @@ __global__ void __launch_bounds__(256) k_diff_enhance_bwd(const float *__restric
             if (gimg) gimg[planar ? base + (size_t)c * n + p : base + (size_t)p * 3 + c] = gx;
         }
     }
-    // block totals: wave sums, then the four waves in order (fixed order: the same bits every run)
-    __shared__ double sd[4][kPartD];
-    __shared__ uint32_t su[4][kPartU];
-    double v[kPartD] = {s_om, s_ga, s_x[0], s_x[1], s_x[2], s_r[0], s_r[1], s_r[2]};
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const double v[kPartD] = {s_om, s_ga, s_x[0], s_x[1], s_x[2], s_r[0], s_r[1], s_r[2]};
+    store_partials(v, k, part, cnt);
+}
+
+// The gated module's backward sweep (same chunks, partials and counts as k_diff_enhance_bwd).  torch's graph, with v the
+// input of the final clamp and g its gradient after the clamp's mask: d use_gamma = g * z - g * s (MulBackward0 and
+// RsubBackward1), dz = g * use_gamma, d e = dz * (z * log(s + 1e-8)), ds = g * (1 - use_gamma) + dz * (e * (s + 1e-8)^(e - 1))
+// with (s + 1e-8)^(e - 1) = z / (s + 1e-8) in float64, rounded once.  d gamma = -d e * (r * r) (r = 1 / gamma) is formed
+// in the finish kernel.
+__global__ void __launch_bounds__(256) k_diff_gated_bwd(const float *__restrict__ img, int planar, int n, int chunk,
+                                                        const float *__restrict__ params, const float *__restrict__ saved,
+                                                        const float *__restrict__ gout, float *__restrict__ gimg,
+                                                        double *__restrict__ part, uint32_t *__restrict__ cnt)
+{
+    const int b = blockIdx.y;
+    float lo[3], hi[3], rng[3];
 #pragma unroll
-    for (int i = 0; i < kPartD; ++i) {
-        double a = v[i];
+    for (int c = 0; c < 3; ++c) {
+        lo[c] = saved[(b * 3 + c) * 2];
+        hi[c] = saved[(b * 3 + c) * 2 + 1];
+        rng[c] = (hi[c] - lo[c]) + 1e-8f;
+    }
+    int k0, k1;
+    const bool ok0 = gated_rank(params[b * 4 + 0], n, &k0), ok1 = gated_rank(params[b * 4 + 1], n, &k1);
+    const bool ok = ok0 && ok1;
+    const float u = params[b * 4 + 2], e = 1.0f / params[b * 4 + 3], om = 1.0f - u;
+    double s_u = 0.0, s_e = 0.0, s_x[3] = {0.0, 0.0, 0.0}, s_r[3] = {0.0, 0.0, 0.0};
+    uint32_t k[kPartU];
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
-        if (lane == 0) sd[wid][i] = a;
-    }
+    for (int i = 0; i < kPartU; ++i) k[i] = 0;
+    const size_t base = (size_t)b * 3 * n;
+    const int p0 = blockIdx.x * chunk;
+    const int p1 = min(p0 + chunk, n);
+    for (int p = p0 + (int)threadIdx.x; p < p1; p += 256) {
 #pragma unroll
-    for (int i = 0; i < kPartU; ++i) {
-        const uint32_t a = wave_sum_u32(k[i]);
-        if (lane == 0) su[wid][i] = a;
+        for (int c = 0; c < 3; ++c) {
+            const size_t i = planar ? base + (size_t)c * n + p : base + (size_t)p * 3 + c;
+            const float x = img[i], g = gout[i];
+            k[c * 4 + 0] += x < lo[c];
+            k[c * 4 + 1] += x == lo[c];
+            k[c * 4 + 2] += x < hi[c];
+            k[c * 4 + 3] += x == hi[c];
+            const float s0 = (x - lo[c]) / rng[c];
+            const float sv = clamp01(s0);
+            const float ye = sv + 1e-8f;
+            const float z = pow_f32_fast(ye, e);
+            const float v = u * z + om * sv;
+            const float gv = (v >= 0.0f && v <= 1.0f) ? g : 0.0f;
+            s_u += (double)(gv * z) - (double)(gv * sv);
+            const float gz = gv * u;
+            s_e += (double)(gz * (z * logf(ye)));
+            const float dz = e * (float)((double)z / (double)ye);
+            const float gs = gv * om + (e == 0.0f ? 0.0f : gz * dz);
+            // stretch: the clamp, (x - p_lo) / r
+            const float g0 = (s0 >= 0.0f && s0 <= 1.0f) ? gs : 0.0f;
+            const float gx = g0 / rng[c];
+            s_x[c] += (double)gx;
+            s_r[c] += (double)(-g0 * (s0 / rng[c]));
+            if (gimg) gimg[i] = ok ? gx : __builtin_nanf("");
+        }
     }
-    __syncthreads();
-    const size_t slot = (size_t)b * gridDim.x + blockIdx.x;
-    if (threadIdx.x < kPartD) {
-        const int i = threadIdx.x;
-        part[slot * kPartD + i] = ((sd[0][i] + sd[1][i]) + sd[2][i]) + sd[3][i];
-    } else if (threadIdx.x >= 64 && threadIdx.x < 64 + kPartU) {
-        const int i = threadIdx.x - 64;
-        cnt[slot * kPartU + i] = su[0][i] + su[1][i] + su[2][i] + su[3][i];
-    }
+    const double v[kPartD] = {s_u, s_e, s_x[0], s_x[1], s_x[2], s_r[0], s_r[1], s_r[2]};
+    store_partials(v, k, part, cnt);
 }
 
 // One block per (plane c, image b): the plane's partials in block order, then the element each order statistic's gradient
 // goes to.  torch.sort is stable on the CPU, so sorted position k of value p is the (k - #{x < p})-th element equal to p
 // in linear index order: the block's equal counts find the chunk, one pass over that chunk finds the element.
-// grad_params[b] = {0, 0, grad omega, grad gamma} (plane 0's block).
+// grad_params[b] = {0, 0, grad omega, grad gamma} (plane 0's block).  GATED: the gated module's sorted positions and
+// grad_params[b] = {0, 0, grad use_gamma, -grad e * (r * r)} (torch's ReciprocalBackward0, r = 1 / gamma); an image without a
+// valid position gets NaN parameter gradients and no scatter (its grad_img is NaN already).
+template <bool GATED>
 __global__ void __launch_bounds__(256) k_diff_enhance_bwd_finish(const float *__restrict__ img, int planar, int n, int chunk,
                                                                  int gx, const float *__restrict__ params,
                                                                  const float *__restrict__ saved,
@@ -264,16 +374,33 @@ __global__ void __launch_bounds__(256) k_diff_enhance_bwd_finish(const float *__
         }
         __syncthreads();
     }
+    long long k_lo, k_hi;
+    bool ok = true;
+    if (GATED) {
+        int k0, k1;
+        const bool ok0 = gated_rank(params[b * 4 + 0], n, &k0), ok1 = gated_rank(params[b * 4 + 1], n, &k1);
+        ok = ok0 && ok1;
+        k_lo = k0;
+        k_hi = k1;
+    } else {
+        k_lo = stretch_rank(params[b * 4 + 0], n);
+        k_hi = stretch_rank(params[b * 4 + 1], n);
+    }
     if (c == 0 && tid == 0) {
         gparams[b * 4 + 0] = 0.0f;
         gparams[b * 4 + 1] = 0.0f;
-        gparams[b * 4 + 2] = (float)rd[0][0];
-        gparams[b * 4 + 3] = (float)rd[1][0];
+        if (GATED) {
+            const float r = 1.0f / params[b * 4 + 3];
+            gparams[b * 4 + 2] = ok ? (float)rd[0][0] : __builtin_nanf("");
+            gparams[b * 4 + 3] = ok ? (float)rd[1][0] * -(r * r) : __builtin_nanf("");
+        } else {
+            gparams[b * 4 + 2] = (float)rd[0][0];
+            gparams[b * 4 + 3] = (float)rd[1][0];
+        }
     }
-    if (!gimg) return;
+    if (!gimg || !ok) return;
     // grad p_lo = -sum grad_x - dL/dr, grad p_hi = dL/dr (r = p_hi - p_lo + 1e-8)
     const float g_lo = (float)(-rd[2][0] - rd[3][0]), g_hi = (float)rd[3][0];
-    const long long k_lo = stretch_rank(params[b * 4 + 0], n), k_hi = stretch_rank(params[b * 4 + 1], n);
     const size_t base = (size_t)b * 3 * n;
     __shared__ int s_blk, s_pos;
     __shared__ long long s_j;
@@ -395,8 +522,34 @@ int launch_diff_enhance_bwd(const float *d_img, int planar, Shape s, const float
     default: UWIE_LAUNCH(k_diff_enhance_bwd<3>, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_grad_img, part, cnt); break;
     }
     UWIE_LAUNCH_CHECK();
-    UWIE_LAUNCH(k_diff_enhance_bwd_finish, dim3(3, s.B), dim3(256), 0, st, d_img, planar, n, g.chunk, g.gx, d_params, d_saved,
-                part, cnt, d_grad_img, d_grad_params);
+    UWIE_LAUNCH(k_diff_enhance_bwd_finish<false>, dim3(3, s.B), dim3(256), 0, st, d_img, planar, n, g.chunk, g.gx, d_params,
+                d_saved, part, cnt, d_grad_img, d_grad_params);
+    UWIE_LAUNCH_CHECK();
+    return UWIE_OK;
+}
+
+int launch_diff_gated(const float *d_img, int planar, Shape s, const float *d_params, const float *d_os, float *d_out,
+                      hipStream_t st, float *d_saved)
+{
+    const int n = (int)s.npx();
+    UWIE_LAUNCH(k_diff_gated, dim3(grid_for(n, 4096), s.B), dim3(256), 0, st, d_img, planar, n, d_params, d_os, d_out, d_saved);
+    UWIE_LAUNCH_CHECK();
+    return UWIE_OK;
+}
+
+int launch_diff_gated_bwd(const float *d_img, int planar, Shape s, const float *d_params, const float *d_saved,
+                          const float *d_grad_out, float *d_grad_img, float *d_grad_params, void *ws, hipStream_t st)
+{
+    const int n = (int)s.npx();
+    const BwdGeom g = bwd_geom(s);
+    Carver c(ws);
+    double *part = c.take<double>((size_t)s.B * g.gx * kPartD);
+    uint32_t *cnt = c.take<uint32_t>((size_t)s.B * g.gx * kPartU);
+    UWIE_LAUNCH(k_diff_gated_bwd, dim3(g.gx, s.B), dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out,
+                d_grad_img, part, cnt);
+    UWIE_LAUNCH_CHECK();
+    UWIE_LAUNCH(k_diff_enhance_bwd_finish<true>, dim3(3, s.B), dim3(256), 0, st, d_img, planar, n, g.chunk, g.gx, d_params,
+                d_saved, part, cnt, d_grad_img, d_grad_params);
     UWIE_LAUNCH_CHECK();
     return UWIE_OK;
 }

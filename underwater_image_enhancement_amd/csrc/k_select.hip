@@ -335,6 +335,32 @@ __global__ void k_sel_init_stretch_ranks(SelState<uint32_t> *st, int nbc, const 
     st[i] = s;
 }
 
+// deep_learning_parameters.DifferentiableEnhancement.color_stretch (:73-77): the same two sorted positions per image, by
+// Python's indexing rules instead of a clamp (gated_rank).  An image without a valid position selects position 0 (a safe
+// substitute) and sets UWIE_STATUS_DIFF_RANK; the gated kernels write NaN for it.
+__global__ void k_sel_init_gated_ranks(SelState<uint32_t> *st, int nbc, const float *__restrict__ params, int stride, int n,
+                                       uint32_t *status)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nbc) return;
+    const float *pr = params + (size_t)(i / 3) * stride;
+    SelState<uint32_t> s;
+    for (int q = 0; q < kMaxRanks; ++q) {
+        s.prefix[q] = 0;
+        s.gprefix[q] = 0;
+        s.rank[q] = 0;
+        s.gid[q] = 0;
+    }
+    int k[2];
+    const bool ok0 = gated_rank(pr[0], n, &k[0]), ok1 = gated_rank(pr[1], n, &k[1]);
+    const bool ok = ok0 && ok1;
+    s.rank[0] = ok ? (uint32_t)k[0] : 0u;
+    s.rank[1] = ok ? (uint32_t)k[1] : 0u;
+    if (!ok && status) atomicOr(status, (uint32_t)UWIE_STATUS_DIFF_RANK);
+    s.ngroups = 1;
+    st[i] = s;
+}
+
 template <typename V>
 int run_t(const SelectPlan &plan, const V *d_vals, int planar, Shape s, bool pass1_done, hipStream_t st,
           const uint32_t *only = nullptr)
@@ -1383,6 +1409,26 @@ int select_begin_stretch_ranks(Shape s, const float *d_params, int stride, void 
     plan->t[0] = 0.0;
     UWIE_LAUNCH(k_sel_init_stretch_ranks, dim3(cdiv(nbc, 64)), dim3(64), 0, st, (SelState<uint32_t> *)plan->state, nbc,
                 d_params, stride, (int)n);
+    UWIE_LAUNCH_CHECK();
+    UWIE_HIP_CHECK(hipMemsetAsync(plan->ghist, 0, sizeof(uint32_t) * (size_t)nbc * kMaxRanks * kBins, st));
+    return UWIE_OK;
+}
+
+int select_begin_gated_ranks(Shape s, const float *d_params, int stride, uint32_t *d_status, void *ws, hipStream_t st,
+                             SelectPlan *plan)
+{
+    const long long n = (long long)s.npx();
+    UWIE_REQUIRE(n >= 1 && n < (1ll << 31), "gated ranks: plane size out of range");
+    Carver c(ws);
+    const int nbc = s.B * 3;
+    plan->state = c.take<SelState<uint64_t>>(nbc);
+    plan->ghist = c.take<uint32_t>((size_t)nbc * kMaxRanks * kBins);
+    plan->os = c.take<double>((size_t)nbc * kMaxRanks);
+    plan->nq = 1;  // two ranks
+    plan->is64 = false;
+    plan->t[0] = 0.0;
+    UWIE_LAUNCH(k_sel_init_gated_ranks, dim3(cdiv(nbc, 64)), dim3(64), 0, st, (SelState<uint32_t> *)plan->state, nbc,
+                d_params, stride, (int)n, d_status);
     UWIE_LAUNCH_CHECK();
     UWIE_HIP_CHECK(hipMemsetAsync(plan->ghist, 0, sizeof(uint32_t) * (size_t)nbc * kMaxRanks * kBins, st));
     return UWIE_OK;

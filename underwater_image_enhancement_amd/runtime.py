@@ -115,12 +115,17 @@ class Device:
         return scope()
 
     # ------------------------------------------------------------------ device-side self checks (uwie_device_status)
-    def check_status(self):
+    def check_status(self, allow: int = 0) -> int:
         """Wait for the current stream and raise ``UwieError`` if a kernel found one of its invariants violated since the last
         check (include/uwie.h: UWIE_E_DEVICE) -- the results of those calls are not valid.  ``enhance`` & co. call this when
         they copy results back to the host (they synchronise there anyway); callers that keep tensors on the device call it
-        when they synchronise."""
-        check(self.lib.uwie_device_status(self._ctx, self.stream(), None))
+        when they synchronise.  Bits in ``allow`` (UWIE_STATUS_*) are returned instead of raised, for a caller that reports
+        them itself; any other bit still raises.  The word is cleared either way."""
+        bits = ctypes.c_uint32(0)
+        rc = self.lib.uwie_device_status(self._ctx, self.stream(), ctypes.byref(bits))
+        if rc != 0 and (bits.value == 0 or bits.value & ~allow):
+            check(rc)
+        return bits.value
 
     # ------------------------------------------------------------------ per-kernel timing (HIP events on the launch stream)
     def profile(self, on: bool, only: str | None = None):
@@ -253,6 +258,50 @@ class Device:
         check(self.lib.uwie_diff_enhance_bwd_f32(self._ctx, _ptr(img), _ptr(params), int(flags), int(planar), B, H, W, _ptr(saved),
                                                  _ptr(grad_out), _ptr(grad_img), _ptr(grad_params), _ptr(ws), ws.numel(),
                                                  self.stream()))
+        return grad_img, grad_params
+
+    def _diff_gated_shape(self, img, params, planar: bool):
+        assert img.dtype == torch.float32 and params.dtype == torch.float32 and img.dim() == 4
+        B = img.shape[0]
+        H, W = (img.shape[2], img.shape[3]) if planar else (img.shape[1], img.shape[2])
+        assert img.shape[1 if planar else 3] == 3 and tuple(params.shape) == (B, 4)
+        return B, H, W
+
+    def diff_gated_f32(self, img, params, planar: bool):
+        """deep_learning_parameters.DifferentiableEnhancement's forward (uwie_diff_gated_f32): img float32 cuda [B,3,H,W]
+        (planar) or [B,H,W,3]; params float32 [B,4] = L_low, L_high, use_gamma, gamma.  An image without a valid sorted
+        position gets NaN and sets UWIE_STATUS_DIFF_RANK (check_status)."""
+        B, H, W = self._diff_gated_shape(img, params, planar)
+        img, params = img.contiguous(), params.contiguous()
+        ws = self.workspace_for(B, H, W)
+        out = self.empty(tuple(img.shape), torch.float32)
+        check(self.lib.uwie_diff_gated_f32(self._ctx, _ptr(img), _ptr(out), B, H, W, int(planar), _ptr(params), 0, _ptr(ws),
+                                           ws.numel(), self.stream()))
+        return out
+
+    def diff_gated_save_f32(self, img, params, planar: bool):
+        """diff_gated_f32 that also returns what the backward needs: (out, saved float32 [B,3,2] = p_lo, p_hi per plane)."""
+        B, H, W = self._diff_gated_shape(img, params, planar)
+        img, params = img.contiguous(), params.contiguous()
+        ws = self.workspace_for(B, H, W)
+        out = self.empty(tuple(img.shape), torch.float32)
+        saved = self.empty((B, 3, 2), torch.float32)
+        check(self.lib.uwie_diff_gated_save_f32(self._ctx, _ptr(img), _ptr(out), B, H, W, int(planar), _ptr(params), 0,
+                                                _ptr(saved), _ptr(ws), ws.numel(), self.stream()))
+        return out, saved
+
+    def diff_gated_bwd_f32(self, img, params, saved, grad_out, planar: bool, want_img: bool = True):
+        """Gradient of diff_gated: (grad_img in img's layout or None when not wanted, grad_params float32 [B,4] =
+        0, 0, d use_gamma, d gamma)."""
+        assert grad_out.dtype == torch.float32 and tuple(grad_out.shape) == tuple(img.shape)
+        B, H, W = self._diff_gated_shape(img, params, planar)
+        img, params, saved, grad_out = img.contiguous(), params.contiguous(), saved.contiguous(), grad_out.contiguous()
+        ws = self.workspace(self.lib.uwie_diff_gated_bwd_workspace_bytes(B, H, W))
+        grad_img = self.empty(tuple(img.shape), torch.float32) if want_img else None
+        grad_params = self.empty((B, 4), torch.float32)
+        check(self.lib.uwie_diff_gated_bwd_f32(self._ctx, _ptr(img), _ptr(params), 0, int(planar), B, H, W, _ptr(saved),
+                                               _ptr(grad_out), _ptr(grad_img), _ptr(grad_params), _ptr(ws), ws.numel(),
+                                               self.stream()))
         return grad_img, grad_params
 
     def extract_features_u8(self, frames):
