@@ -134,6 +134,9 @@ void uwie_destroy(uwie_ctx *ctx);
  *                          no valid sorted position by Python's rules (int(L / 100.0 * n) outside [-n, n - 1]: IndexError;
  *                          L NaN: ValueError; L infinite: OverflowError).  That image's output and gradients are NaN. */
 #define UWIE_STATUS_DIFF_RANK 16u
+/*   UWIE_STATUS_RESIZE_DESC  uwie_resize_rgb_u8 (k_resize.hip): a frame descriptor has a NULL pointer or a side outside
+ *                            [1, UWIE_RESIZE_MAX_SRC]: nothing of that frame was read or written. */
+#define UWIE_STATUS_RESIZE_DESC 32u
 int uwie_device_status(uwie_ctx *ctx, void *stream, uint32_t *bits);
 
 /* Per-kernel timing for benchmarks (no reference counterpart; the reference only has a per-image wall clock,
@@ -299,6 +302,35 @@ int uwie_diff_gated_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_pa
  */
 int uwie_extract_features_u8(uwie_ctx *ctx, const uint8_t *d_in, float *d_features, int batch, int H, int W,
                              void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * cv2.resize(frame, (out_w, out_h)) (default INTER_LINEAR) of a batch of decoded RGB u8 frames, the per-frame preparation of
+ * deep_learning_parameters.EnhancementDataset (:214-247), vgg_16_UIE.ImprovedEnhancementDataset (:335-422) and
+ * use_trained_model.EnhancementPredictor._preprocess_for_vgg (:39-46).  OpenCV's fixed-point u8 path: a copy when the size
+ * does not change, INTER_AREA's fast path for an exact 2x reduction, otherwise two taps per axis with 11-bit coefficients
+ * and VResizeLinearVec_32s8u's rounding (DESIGN.md section 11 states the contract and its unpinned parts).
+ * d_desc: DEVICE table of `batch` descriptors, one per frame: a device pointer to a contiguous [H][W][3] frame (row stride
+ * 3 * W) and its size; frames may differ in size.  A descriptor outside the limits below sets UWIE_STATUS_RESIZE_DESC.
+ * d_flips (optional): [batch] u8, bit UWIE_FLIP_LR = np.fliplr and bit UWIE_FLIP_UD = np.flipud of the resized frame.
+ * Outputs, each optional (NULL = not written, at least one):
+ *   d_out_u8   [batch][out_h][out_w][3] the resized frames;
+ *   d_out_f32  [batch][3][out_h][out_w] float32 (float)v / 255.0f (IEEE division, as NumPy's astype(float32) / 255.0);
+ *   d_out_norm [batch][3][out_h][out_w] float32 ((float)v / 255.0f - mean3[c]) / std3[c], each operation rounded once
+ *              (torchvision's Normalize on float32 tensors); mean3 / std3 are host arrays of 3, required with d_out_norm.
+ * Every output element depends on its own frame only: the bytes do not depend on the batch or on the launch shape.
+ * UWIE_E_INVALID: batch, out_h or out_w < 1, batch > 65535, out_h or out_w > UWIE_RESIZE_MAX_SIDE, every output NULL.
+ */
+#define UWIE_RESIZE_MAX_SIDE 4096
+#define UWIE_RESIZE_MAX_SRC 32768
+#define UWIE_FLIP_LR 1
+#define UWIE_FLIP_UD 2
+typedef struct uwie_frame_desc {
+    const uint8_t *data; /* device pointer to [H][W][3] u8 */
+    int32_t H, W;
+} uwie_frame_desc;
+int uwie_resize_rgb_u8(uwie_ctx *ctx, const uwie_frame_desc *d_desc, int batch, int out_h, int out_w, const uint8_t *d_flips,
+                       uint8_t *d_out_u8, float *d_out_f32, float *d_out_norm, const float *mean3, const float *std3,
+                       void *stream);
 
 /*
  * QualityAssessment.comprehensive_assessment (quality_assessment.py:215-286; called on every strategy output by

@@ -11,6 +11,8 @@ CSRC = os.path.join(_HERE, "csrc")
 
 SURFACE_SIX, SURFACE_DICT = 0, 1
 STATUS_DIFF_RANK = 16  # include/uwie.h UWIE_STATUS_DIFF_RANK
+FLIP_LR, FLIP_UD = 1, 2  # include/uwie.h UWIE_FLIP_LR, UWIE_FLIP_UD
+RESIZE_MAX_SIDE, RESIZE_MAX_SRC = 4096, 32768  # include/uwie.h UWIE_RESIZE_MAX_SIDE, UWIE_RESIZE_MAX_SRC
 INTER_F64, INTER_FX32, INTER_F32T = 0, 1, 2  # uwie_params.inter_dtype
 DICT_STRATEGIES = {
     "strong_dehazing": 0,
@@ -94,6 +96,7 @@ SIGNATURES = {
     "uwie_feature_extractor_count": [_I, _I],
     "uwie_workspace_bytes_feature_extractor": [_I, _I, _I],
     "uwie_feature_extractor_u8": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _SZ, _VP],
+    "uwie_resize_rgb_u8": [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
     "uwie_quality_scores": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _SZ, _VP],
     "uwie_cast_classify": [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _SZ, _VP],
     "uwie_normalise_correct": [_VP, _VP, _VP, _VP, _I, _I, _I, _VP],

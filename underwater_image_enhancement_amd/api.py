@@ -627,6 +627,152 @@ class FeatureExtractor:
         return cls._row(img)
 
 
+# ------------------------------------------------------------------ trainer / predictor input batches (cv2.resize on the device)
+IMAGENET_MEAN = (0.485, 0.456, 0.406)  # vgg_16_UIE.py:327-330, use_trained_model.py:35-36 (T.Normalize)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+
+
+def _frame_set(frames, dev: Device):
+    """One frame, a batch or a ragged list -> (what Device.resize_rgb takes, was_numpy, single, sizes)."""
+    if isinstance(frames, (list, tuple)):
+        if not frames:
+            raise ValueError("empty frame list")
+        was_numpy = isinstance(frames[0], np.ndarray)
+        items = [np.ascontiguousarray(f) if isinstance(f, np.ndarray) else f.to(dev.torch_device).contiguous() for f in frames]
+        return items, was_numpy, False, [(int(f.shape[0]), int(f.shape[1])) for f in items]
+    batch, was_numpy, single = _as_batch_u8(frames, dev)
+    return batch, was_numpy, single, [(int(batch.shape[1]), int(batch.shape[2]))] * int(batch.shape[0])
+
+
+def _dsize(dsize):
+    w, h = (int(v) for v in dsize)
+    if w < 1 or h < 1:
+        raise ValueError(f"dsize must be positive (width, height), got {tuple(dsize)}")
+    return h, w
+
+
+def _norm_arg(normalize):
+    if normalize is None:
+        return None
+    if isinstance(normalize, str):
+        if normalize != "imagenet":
+            raise ValueError(f"unknown normalisation {normalize!r}")
+        return IMAGENET_MEAN, IMAGENET_STD
+    mean, std = normalize
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("normalize: (mean, std) with three values each")
+    return tuple(float(v) for v in mean), tuple(float(v) for v in std)
+
+
+def resize_frames(frames, dsize, flips=None, device: int | None = None):
+    """``cv2.resize(frame, dsize)`` (INTER_LINEAR) of uint8 RGB frames on the device: one ``[H,W,3]`` frame, a ``[B,H,W,3]``
+    batch or a list of frames of any sizes, in one launch.  ``dsize`` is OpenCV's ``(width, height)``.  ``flips``: per-frame
+    flags, 1 = ``np.fliplr`` and 2 = ``np.flipud`` of the result.  Returns uint8 ``[B,h,w,3]`` (``[h,w,3]`` for one frame);
+    NumPy in gives NumPy out, device tensors stay on the device.  The arithmetic is OpenCV's fixed-point path (DESIGN.md
+    section 11)."""
+    dev = get_device(device)
+    h, w = _dsize(dsize)
+    src, was_numpy, single, _ = _frame_set(frames, dev)
+    u8, _, _ = dev.resize_rgb(src, h, w, flips=flips)
+    out = _finish(u8, was_numpy, single, dev)
+    if not was_numpy:
+        dev.check_status()
+    return out
+
+
+def image_tensor(frames, dsize=None, normalize=None, flips=None, device: int | None = None):
+    """Float32 ``[B,3,h,w]`` on the device from uint8 RGB frames: ``u8.astype(float32) / 255.0`` then ``permute(2, 0, 1)``,
+    after ``cv2.resize(frame, dsize)`` when ``dsize`` is given (frames may then differ in size).  ``dsize=None`` keeps the
+    full resolution, as ``EnhancementPredictor._img_to_tensor`` (use_trained_model.py:48-51) does (frames of one size).
+    ``normalize``: ``"imagenet"`` or ``(mean, std)`` applies torchvision's ``Normalize`` (float32 ``sub`` then ``div``)."""
+    dev = get_device(device)
+    src, _, _, sizes = _frame_set(frames, dev)
+    if dsize is None:
+        if len(set(sizes)) != 1:
+            raise ValueError("frames of different sizes need a dsize")
+        h, w = sizes[0]
+    else:
+        h, w = _dsize(dsize)
+    norm = _norm_arg(normalize)
+    _, f32, nrm = dev.resize_rgb(src, h, w, flips=flips, want_u8=False, want_f32=norm is None, norm=norm)
+    dev.check_status()
+    return f32 if norm is None else nrm
+
+
+def vgg_input(frames, size: int = 224, device: int | None = None):
+    """``EnhancementPredictor._preprocess_for_vgg`` (use_trained_model.py:39-46) for uint8 RGB frames, batched: resize to
+    ``size`` x ``size``, ``/ 255``, CHW, ImageNet ``Normalize``.  Returns float32 ``[B,3,size,size]`` on the device.  (The
+    reference quantises its float image with ``(img * 255).astype(uint8)``; for ``u8 / 255`` that gives the frame back.)"""
+    return image_tensor(frames, (size, size), normalize="imagenet", device=device)
+
+
+def _draw_flips(n: int):
+    """augment_pair's draws (vgg_16_UIE.py:344-356), per item in index order: horizontal first, then vertical."""
+    out = np.zeros(n, np.uint8)
+    for i in range(n):
+        if np.random.rand() > 0.5:
+            out[i] |= _lib.FLIP_LR
+        if np.random.rand() > 0.5:
+            out[i] |= _lib.FLIP_UD
+    return out
+
+
+def training_batch(images, references=None, size: int = 256, features="extractor", augment: bool = False, flips=None,
+                   device: int | None = None):
+    """A training batch on the device, as the reference's data loaders collate it from their datasets' items:
+    ``{'image', 'reference'}`` float32 ``[B,3,size,size]`` and ``'features'`` float32 ``[B,F]``.
+
+    ``images``: uint8 RGB frames (a ``[B,H,W,3]`` batch or a list of frames of any sizes, NumPy or device tensors).
+    ``references``: None, or one entry per image (a frame, or None for a missing reference: the reference is then the
+    image, ``ref = img.copy()``).  An image and its reference may differ in size; each is resized on its own.
+    Per frame: ``cv2.resize(frame, (size, size))``, ``astype(float32) / 255.0``, CHW -- in one launch for images and
+    references together.
+    ``features``: ``"extractor"`` -- ``EnhancementDataset`` (deep_learning_parameters.py:214-247, size 256):
+    ``FeatureExtractor.extract_all_features`` of the resized image (``feature_extractor_rows``, cast to float32);
+    ``"basic"`` -- ``ImprovedEnhancementDataset`` (vgg_16_UIE.py:335-422, size 224): ``extract_basic_features`` of the
+    (flipped) resized image (``uwie_extract_features_u8``); ``None``: zeros ``[B,79]``.  Features describe the image as
+    the batch holds it, flipped when it is flipped.
+    ``augment``: draw each item's flips from ``np.random`` as ``augment_pair`` does (horizontal then vertical, items in
+    index order), so a seeded ``np.random`` gives a single-process pass of the reference dataset.  ``flips`` (per-item
+    flags, 1 = fliplr, 2 = flipud) overrides the draws.  Image and reference get the same flips."""
+    if features not in ("extractor", "basic", None):
+        raise ValueError(f"features must be 'extractor', 'basic' or None, got {features!r}")
+    dev = get_device(device)
+    src, _, _, sizes = _frame_set(images, dev)
+    B = len(sizes)
+    if flips is not None:
+        fl = np.asarray(flips, dtype=np.int64).reshape(-1)
+        if fl.size != B:
+            raise ValueError(f"flips: {fl.size} values for {B} images")
+    elif augment:
+        fl = _draw_flips(B)
+    else:
+        fl = np.zeros(B, np.int64)
+    refs = [None] * B if references is None else list(references)
+    if len(refs) != B:
+        raise ValueError(f"{len(refs)} references for {B} images")
+    present = [i for i, r in enumerate(refs) if r is not None]
+    frames = list(src) if isinstance(src, list) else [src[i] for i in range(B)]
+    ref_frames = [np.ascontiguousarray(refs[i]) if isinstance(refs[i], np.ndarray) else refs[i].to(dev.torch_device).contiguous()
+                  for i in present]
+    if ref_frames and isinstance(frames[0], np.ndarray) != isinstance(ref_frames[0], np.ndarray):
+        ref_frames = [f.cpu().numpy() if isinstance(frames[0], np.ndarray) else dev.tensor(f) for f in ref_frames]
+    allf = np.concatenate([fl, fl[present]]) if present else fl
+    u8, f32, _ = dev.resize_rgb(frames + ref_frames, size, size, flips=allf, want_u8=features is not None, want_f32=True)
+    image = f32[:B]
+    reference = image.clone()
+    if present:
+        reference[torch.as_tensor(present, device=dev.torch_device)] = f32[B:]
+    if features == "extractor":
+        feats = dev.feature_extractor(u8[:B]).to(torch.float32)
+    elif features == "basic":
+        feats = dev.extract_features_u8(u8[:B])
+    else:
+        feats = torch.zeros((B, 79), dtype=torch.float32, device=dev.torch_device)
+    dev.check_status()
+    return {"image": image, "reference": reference, "features": feats}
+
+
 # ------------------------------------------------------------------ float <-> u8 bridging
 def _recover_u8(img):
     """Invert ``u8.astype(float32)/255`` [+ ``color_correction``] exactly; returns (u8 frame, cast kind)."""

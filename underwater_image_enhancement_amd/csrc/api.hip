@@ -628,7 +628,8 @@ int uwie_device_status(uwie_ctx *ctx, void *stream, uint32_t *bits)
                   : (v & UWIE_STATUS_FALLBACK_SYNC) ? " the percentile fallback's blocks gave up waiting for each other (k_select.hip);"
                   : (v & UWIE_STATUS_QTREE_BOUNDS) ? " a quadtree score fell outside its histogram interval (k_airlight.hip, tuning q_hist = 3);"
                   : (v & UWIE_STATUS_FEATURE_COUNTS) ? " a frame's feature histograms do not count every pixel (k_extractor.hip);"
-                  : (v & UWIE_STATUS_DIFF_RANK) ? " a gated DifferentiableEnhancement image has no valid sorted position (an IndexError, ValueError or OverflowError in Python);" : "");
+                  : (v & UWIE_STATUS_DIFF_RANK) ? " a gated DifferentiableEnhancement image has no valid sorted position (an IndexError, ValueError or OverflowError in Python);"
+                  : (v & UWIE_STATUS_RESIZE_DESC) ? " a resize frame descriptor has a NULL pointer or a size out of range (k_resize.hip);" : "");
         return UWIE_E_DEVICE;
     }
     return UWIE_OK;
@@ -1206,6 +1207,21 @@ int uwie_feature_extractor_u8(uwie_ctx *ctx, const uint8_t *d_u8, const float *d
     const Shape s{batch, H, W};
     UWIE_CHECK_WS(feature_extractor_ws_bytes(s));
     return launch_feature_extractor(ctx, d_u8, d_f32, s, gray_shift, d_features, d_workspace, (hipStream_t)stream);
+}
+
+int uwie_resize_rgb_u8(uwie_ctx *ctx, const uwie_frame_desc *d_desc, int batch, int out_h, int out_w, const uint8_t *d_flips,
+                       uint8_t *d_out_u8, float *d_out_f32, float *d_out_norm, const float *mean3, const float *std3,
+                       void *stream)
+{
+    UWIE_REQUIRE(ctx && d_desc, "resize_rgb: NULL pointer");
+    UWIE_REQUIRE(d_out_u8 || d_out_f32 || d_out_norm, "resize_rgb: every output is NULL");
+    UWIE_REQUIRE(!d_out_norm || (mean3 && std3), "resize_rgb: normalised output without mean / std");
+    UWIE_REQUIRE(batch >= 1 && batch <= 65535, "resize_rgb: batch must be in [1, 65535]");
+    UWIE_REQUIRE(out_h >= 1 && out_w >= 1 && out_h <= UWIE_RESIZE_MAX_SIDE && out_w <= UWIE_RESIZE_MAX_SIDE,
+                 "resize_rgb: out_h / out_w must be in [1, UWIE_RESIZE_MAX_SIDE]");
+    UWIE_SCOPE(ctx);
+    return launch_resize_rgb(d_desc, batch, out_h, out_w, d_flips, d_out_u8, d_out_f32, d_out_norm, mean3, std3, ctx->d_status,
+                             (hipStream_t)stream);
 }
 
 /* ---------------------------------------------------------------- stage entry points */

@@ -226,6 +226,10 @@ size_t feature_extractor_ws_bytes(Shape s);
 int launch_feature_extractor(uwie_ctx *ctx, const uint8_t *d_u8, const float *d_f32, Shape s, int gray_shift, double *d_out,
                              void *ws, hipStream_t st);
 
+// k_resize.hip: cv2.resize of a ragged batch of RGB u8 frames (device descriptor table), u8 / float32 / normalised outputs
+int launch_resize_rgb(const uwie_frame_desc *d_desc, int B, int oh, int ow, const uint8_t *d_flips, uint8_t *d_u8, float *d_f32,
+                      float *d_norm, const float *mean3, const float *std3, uint32_t *d_status, hipStream_t st);
+
 // best[b] = first argmax over the n strategies of scores[k][b][8]; d_out (optional) [B][H][W][3] = d_all[best[b]][b]
 int launch_pick_best(const double *d_scores, int n, Shape s, const uint8_t *d_all, int32_t *d_best, uint8_t *d_out, hipStream_t st);
 

@@ -13,6 +13,7 @@ import torch
 from . import _lib
 from ._lib import UwieParams, check
 
+_FRAME_DESC = np.dtype([("data", "<u8"), ("H", "<i4"), ("W", "<i4")])  # include/uwie.h uwie_frame_desc
 _TRACE_DTYPE = np.dtype([("y0", "<i4"), ("x0", "<i4"), ("rows", "<i4"), ("cols", "<i4"), ("score", "<f8", (4,))])
 
 
@@ -331,6 +332,77 @@ class Device:
         check(self.lib.uwie_feature_extractor_u8(self._ctx, _ptr(frames_u8), _ptr(frames_f32), B, H, W, int(gray_shift), _ptr(out),
                                                  _ptr(ws), ws.numel(), self.stream()))
         return out
+
+    def frame_table(self, frames):
+        """Device descriptor table (uwie_frame_desc) of RGB u8 frames: a contiguous [B,H,W,3] tensor on this device, or a list
+        of [H,W,3] frames that are all host NumPy arrays (packed into one pinned buffer, one upload) or all tensors on this
+        device (their own pointers, no copy).  Returns (table, (keep, sizes)): ``keep`` is the memory the table points to.
+        Uploads go on the current stream, the launch that reads them too: the caching allocators may release them after it."""
+        if isinstance(frames, torch.Tensor):
+            B, H, W = self._bhw(frames)
+            assert frames.dtype == torch.uint8 and frames.device == self.torch_device
+            sizes = [(H, W)] * B
+            base, step = frames.data_ptr(), H * W * 3
+            ptrs = [base + i * step for i in range(B)]
+            keep = frames
+        else:
+            frames = list(frames)
+            if not frames:
+                raise ValueError("empty frame list")
+            on_host = [isinstance(f, np.ndarray) for f in frames]
+            if any(on_host) and not all(on_host):
+                raise TypeError("a frame list is either all host NumPy arrays or all device tensors")
+            for f in frames:
+                if f.dtype not in (np.uint8, torch.uint8):
+                    raise TypeError(f"expected uint8 frames, got {f.dtype}")
+                if f.ndim != 3 or f.shape[2] != 3:
+                    raise ValueError(f"expected [H,W,3] frames, got {tuple(f.shape)}")
+            sizes = [(int(f.shape[0]), int(f.shape[1])) for f in frames]
+            if all(on_host):
+                offs = np.cumsum([0] + [h * w * 3 for h, w in sizes])
+                pinned = torch.empty(int(offs[-1]), dtype=torch.uint8, pin_memory=True)
+                host = pinned.numpy()
+                for f, o0, o1 in zip(frames, offs[:-1], offs[1:]):
+                    host[o0:o1] = np.ascontiguousarray(f).reshape(-1)
+                keep = pinned.to(self.torch_device, non_blocking=True)
+                ptrs = [keep.data_ptr() + int(o) for o in offs[:-1]]
+            else:
+                for f in frames:
+                    if f.device != self.torch_device or not f.is_contiguous():
+                        raise ValueError("device frames must be contiguous tensors on this device")
+                keep = frames
+                ptrs = [f.data_ptr() for f in frames]
+        for h, w in sizes:
+            if not (1 <= h <= _lib.RESIZE_MAX_SRC and 1 <= w <= _lib.RESIZE_MAX_SRC):
+                raise ValueError(f"frame size {h}x{w} outside [1, {_lib.RESIZE_MAX_SRC}]")
+        table = np.zeros(len(sizes), _FRAME_DESC)
+        table["data"], table["H"], table["W"] = ptrs, [h for h, _ in sizes], [w for _, w in sizes]
+        dt = torch.from_numpy(table.view(np.uint8)).pin_memory().to(self.torch_device, non_blocking=True)
+        return dt, (keep, sizes)
+
+    def resize_rgb(self, frames, out_h: int, out_w: int, flips=None, want_u8: bool = True, want_f32: bool = False, norm=None):
+        """cv2.resize(frame, (out_w, out_h)) of every frame in one launch (uwie_resize_rgb_u8).  ``frames``: see frame_table
+        (frames may differ in size).  ``flips``: per-frame flags (1 = fliplr, 2 = flipud of the result) or None.
+        ``norm``: (mean3, std3) for the normalised planes, or None.  Returns (u8 [B,oh,ow,3] or None, float32 [B,3,oh,ow] =
+        v / 255 or None, normalised float32 [B,3,oh,ow] or None)."""
+        table, keep = self.frame_table(frames)
+        B = len(keep[1])
+        f = None
+        if flips is not None:
+            fl = np.asarray(flips, dtype=np.int64).reshape(-1)
+            if fl.size != B or np.any((fl < 0) | (fl > 3)):
+                raise ValueError("flips: one value in 0..3 per frame")
+            f = torch.from_numpy(fl.astype(np.uint8)).to(self.torch_device)
+        u8 = self.empty((B, out_h, out_w, 3), torch.uint8) if want_u8 else None
+        f32 = self.empty((B, 3, out_h, out_w), torch.float32) if want_f32 else None
+        nrm = m = s = None
+        if norm is not None:
+            nrm = self.empty((B, 3, out_h, out_w), torch.float32)
+            m = (ctypes.c_float * 3)(*[float(v) for v in norm[0]])
+            s = (ctypes.c_float * 3)(*[float(v) for v in norm[1]])
+        check(self.lib.uwie_resize_rgb_u8(self._ctx, _ptr(table), B, int(out_h), int(out_w), _ptr(f), _ptr(u8), _ptr(f32),
+                                          _ptr(nrm), m, s, self.stream()))
+        return u8, f32, nrm
 
     def quality_scores(self, frames_u8, frames_f32=None, weights=None, gray_shift: int = 15):
         """frames_u8: uint8 cuda [B,H,W,3] (the quantised image); frames_f32: optional float32 cuda [B,H,W,3];
