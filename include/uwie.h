@@ -120,8 +120,8 @@ void uwie_destroy(uwie_ctx *ctx);
  *   UWIE_STATUS_CANNY_LABEL  cv2.Canny's hysteresis (S6:150; k_canny.hip union / mark / emit / paint) met a component
  *                            label that the current launch did not write. */
 #define UWIE_STATUS_CANNY_LABEL 1u
-/*   UWIE_STATUS_FALLBACK_SYNC  the blocks of a plane in the percentile selection's one-launch fallback (k_rank_fallback) gave up
- *                              waiting for each other (seconds): the kernel terminated, that plane's percentiles are not valid. */
+/*   UWIE_STATUS_FALLBACK_SYNC  reserved, never set (it reported a wait between the blocks of an earlier percentile fallback;
+ *                              the selection's blocks no longer wait for each other). */
 #define UWIE_STATUS_FALLBACK_SYNC 2u
 /*   UWIE_STATUS_QTREE_BOUNDS   (tuning q_hist = 3 only: a checking route) a quadrant's reference-order score (compute_Q, S6:116-157)
  *                              fell outside the interval derived from its byte histogram, or the histogram route's decision

@@ -176,8 +176,8 @@ def test_dict_surface_matches_oracle(uw, orc, name):
 def test_dict_surface_select_and_store_modes(uw, orc):
     """The dict surface's dehazing strategies take their float64 percentiles from the linear-digit selection on an image
     that is recomputed per sweep, with the target bins predicted from a sample (default); prediction off or missing,
-    the stored-plane mode, the forced fallback to the generic key sweeps (tiny
-    candidate lists: flagged planes are written out first) and the generic sweeps alone must give the same floats."""
+    the stored-plane mode, the forced fallback to the key-digit passes (tiny
+    candidate lists: flagged planes' values are recomputed too) and the generic passes alone must give the same floats."""
     rng = np.random.default_rng(515)
     noisy = rng.integers(0, 256, (150, 210, 3), dtype=np.uint8)
     flatish = np.empty((330, 310, 3), np.uint8)
@@ -411,12 +411,8 @@ def test_sub_batch_streams_and_profile_filter(uw):
     assert _lib.load().uwie_profile_filter(dev._ctx, None) == 0
 
 
-def test_select_paths_agree(uw, orc):
-    """The percentile selection of strategies 1-3 has three routes: linear first digit with collected candidates (default),
-    its fallback to the generic sweeps when a candidate list overflows (forced here with a tiny list capacity, and hit for
-    real by a nearly constant frame), and the generic three-digit sweeps alone; strategies 1-2 run them either on the
-    the restored image recomputed per sweep (default) or on stored planes (tuning restore_store).  All must give the
-    oracle's bytes."""
+def select_frames():
+    """The frames of the selection-route tests: noisy, flatish, odd, wide, big."""
     rng = np.random.default_rng(404)
     noisy = rng.integers(0, 256, (150, 210, 3), dtype=np.uint8)
     flatish = np.empty((330, 310, 3), np.uint8)  # > 65536 pixels, almost all of one colour: one heavy interior bin
@@ -429,6 +425,16 @@ def test_select_paths_agree(uw, orc):
     big = np.empty((700, 720, 3), np.uint8)  # a block meets > 512 candidates of one bin in one step: LDS stage overflow
     big[:] = (60, 120, 200)
     big[::11, ::13] = rng.integers(0, 256, big[::11, ::13].shape, dtype=np.uint8)
+    return noisy, flatish, odd, wide, big
+
+
+def test_select_paths_agree(uw, orc):
+    """The percentile selection of strategies 1-3 has three routes: linear first digit with collected candidates (default),
+    its fallback to the key-digit passes when a candidate list overflows (forced here with a tiny list capacity, and hit for
+    real by a nearly constant frame), and the generic three-digit passes alone; strategies 1-2 run them either on the
+    the restored image recomputed per sweep (default) or on stored planes (tuning restore_store).  All must give the
+    oracle's bytes."""
+    noisy, flatish, odd, wide, big = select_frames()
     want_big = orc.enhance_u8(big, 2)
     dev = uw.get_device()
     # (store, rank): stored planes or recomputation; for the latter the histogram sweep (the default below 16 MP) and round 4's
@@ -450,6 +456,61 @@ def test_select_paths_agree(uw, orc):
             check_u8(uw.enhance(big, strategy=2), want_big, f"stage overflow, strategy 2 on big flat frame, store={store}")
     batch = np.stack([noisy[:120, :200], flatish[:120, :200], noisy[30:150, 10:210]])
     assert np.array_equal(uw.enhance(batch, strategy=2), np.stack([uw.enhance(f, strategy=2) for f in batch]))
+
+
+def test_select_flagged_planes_in_a_split_batch(uw, orc):
+    """Planes the linear-digit and rank-counting routes cannot answer (tiny lists: the flat frames' heavy bins overflow them)
+    take the key-digit passes, whose blocks meet at a per-plane ticket instead of waiting for each other.  A batch that mixes
+    such planes with planes the scans answer, split over four streams (so the passes of several sub-batches share the chip),
+    must give every frame's own result: the oracle's, and the same bytes as the frame run alone.  Routes: strategies 1-2
+    (rank-counting sweep), 3 (stored planes), a dict dehazing strategy (float64, recomputed) and float32 transmission.
+    Two frames have a known pattern.  The constant frame's pixels are all equal, so each of its planes restores to one value
+    in one bin, whose list overflows: all three planes flag.  The black-and-white frame restores to exact 0 and 1 only ((0 - A) / t + A <= 0 and
+    (1 - A) / t + A >= 1 for 0 < t <= 1), so every rank falls into the bin of exact 0 or exact 1, which the scans answer
+    without a list: none of its planes flags, whatever the capacity.  The other crops may go either way."""
+    import torch
+    from underwater_image_enhancement_amd import _lib
+    from underwater_image_enhancement_amd.api import _dict_params
+
+    noisy, flatish, odd, wide, big = select_frames()
+    flat = np.empty((120, 200, 3), np.uint8)
+    flat[:] = (90, 140, 180)
+    yy, xx = np.mgrid[0:120, 0:200]
+    checker = np.repeat((((yy // 20) + (xx // 20)) % 2 * 255).astype(np.uint8)[:, :, None], 3, axis=2)
+    batch = np.stack([flat, noisy[:120, :200], checker, big[200:320, 300:500], odd[:120, :200], wide[100:220, 400:600],
+                      flatish[150:270, 60:260], flatish[:120, :200]])
+    dev = uw.get_device()
+    name = "medium_dehazing"
+    p = _dict_params(dev, name, {})
+
+    def dict_run(frames):
+        u8, f64 = dev.enhance_u8_f64(torch.from_numpy(np.ascontiguousarray(frames)).to(dev.torch_device), p)
+        return u8.cpu().numpy(), f64.cpu().numpy()
+
+    base_f32t = uw.enhance(batch, strategy=2, inter_dtype=_lib.INTER_F32T)  # (the lists answer every plane of these frames)
+    base_u8, base_f64 = dict_run(batch)
+    with dev.tuning(streams=4, lin_cap=16, rank_sweep=2):
+        for k in (1, 2, 3):
+            got = uw.enhance(batch, strategy=k)
+            for i, u8 in enumerate(batch):
+                check_u8(got[i], orc.enhance_u8(u8, k), f"strategy {k}, frame {i}")
+                assert np.array_equal(got[i], uw.enhance(u8, strategy=k)), (k, i)
+        got = uw.enhance(batch, strategy=2, inter_dtype=_lib.INTER_F32T)
+        assert np.array_equal(got, base_f32t)
+        for i, u8 in enumerate(batch):
+            assert np.array_equal(got[i], uw.enhance(u8, strategy=2, inter_dtype=_lib.INTER_F32T)), ("F32T", i)
+        out, outf = dict_run(batch)
+        # float64: the fused guided filter's tolerance on t (1e-11, its bands chosen from the job) shows against the oracle
+        # and between job shapes; the selection routes agree exactly on one job
+        assert np.array_equal(out, base_u8) and np.array_equal(outf, base_f64)
+        alone = []
+        for i, u8 in enumerate(batch):
+            want = orc.DictStrategyOracle.run(orc.normalise_u8(u8), name, {})
+            alone.append(dict_run(u8[None])[1][0])
+            assert np.abs(outf[i] - want).max() < 1e-9 and np.abs(outf[i] - alone[i]).max() < 1e-9, (name, i)
+        assert dev.check_status() == 0
+    for i, u8 in enumerate(batch):
+        assert np.array_equal(dict_run(u8[None])[1][0], alone[i]), (name, i)
 
 
 # ------------------------------------------------------------------ general (not u8-derived) float images

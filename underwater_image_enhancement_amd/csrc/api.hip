@@ -286,13 +286,13 @@ int six_dehaze_tail(uwie_ctx *ctx, const uint8_t *d_in, const int32_t *kind, Sha
     bool recompute = false;
     if (tune().select_generic) {
         UWIE_TRY(select_begin(s, q, k == 3 ? 4 : 2, P.scratch, st, &plan));
-        UWIE_TRY(launch_restore_planar_hist(d_in, kind, P.A, P.t, s, P.F, plan.ghist, st, false, nullptr, nullptr, t_is_f32));
+        UWIE_TRY(launch_restore_planar_hist(d_in, kind, P.A, P.t, s, P.F, plan.ghist, st, false, nullptr, t_is_f32));
         UWIE_TRY(select_run(plan, P.F, 1, s, true, st));
     } else {
         // Strategies 1 and 2 never store the restored image: the histogram sweep (which also files the elements of the
         // predicted target bins, select_lin_begin) and the stretch each recompute it from the frame and t (restore.h:
-        // 11 + 14 bytes per pixel instead of 23 + 15, and no collecting sweep).  P.F is only written for images whose
-        // selection falls back to the generic sweeps.  Tuning restore_store keeps the stored planes (4K x 64: 17.9 vs
+        // 11 + 14 bytes per pixel instead of 23 + 15, and no collecting sweep); so do the key-digit passes of planes the
+        // selection flags.  Tuning restore_store keeps the stored planes (4K x 64: 17.9 vs
         // 17.5 ms per step, round 2); the tests compare both modes.
         recompute = k != 3 && !tune().restore_store;
         // Strategy 3 keeps the planes (its tail reads them), so the exact target bins can be collected from them by one
@@ -307,9 +307,9 @@ int six_dehaze_tail(uwie_ctx *ctx, const uint8_t *d_in, const int32_t *kind, Sha
         if (recompute && plan.predicted && !t_is_f32 && tune().rank_sweep && big && s.npx() >= 4) {
             // round 4: no histogram at all -- counts below the predicted windows + the windows' members (k_restore_rank)
             UWIE_TRY(launch_restore_rank(src, s, plan, st));
-            UWIE_TRY(select_rank_run(plan, P.F, s, st, src));
+            UWIE_TRY(select_rank_run(plan, s, st, src));
         } else {
-            UWIE_TRY(launch_restore_planar_hist(d_in, kind, P.A, P.t, s, recompute ? nullptr : P.F, plan.ghist, st, true, nullptr,
+            UWIE_TRY(launch_restore_planar_hist(d_in, kind, P.A, P.t, s, recompute ? nullptr : P.F, plan.ghist, st, true,
                                                 &plan, t_is_f32));
             UWIE_TRY(select_lin_run(plan, P.F, s, st, recompute ? &src : nullptr));
         }
@@ -364,12 +364,11 @@ int run_dict_dehaze(uwie_ctx *ctx, const uint8_t *d_in, Shape s, const uwie_para
         UWIE_TRY(select_run64(plan, P.F64, 1, s, true, st));
     } else {
         // the float64 image (24 B/px) is not stored either: histogram sweep, collecting sweep and stretch recompute it
-        // from the frame and t (11 B/px each); P.F64 only serves images that fall back to the generic sweeps.
-        // Tuning restore_store keeps the stored planes.
+        // from the frame and t (11 B/px each), and so do the key-digit passes of flagged planes.  Tuning restore_store keeps
+        // the stored planes.
         recompute = !tune().restore_store;
         UWIE_TRY(select_lin_begin64(s, q, 2, P.scratch, st, &plan, &src));
-        UWIE_TRY(launch_recover64_planar_hist(d_in, P.A, P.t, s, recompute ? nullptr : P.F64, plan.ghist, st, true, nullptr,
-                                              &plan));
+        UWIE_TRY(launch_recover64_planar_hist(d_in, P.A, P.t, s, recompute ? nullptr : P.F64, plan.ghist, st, true, &plan));
         UWIE_TRY(select_lin_run64(plan, P.F64, s, st, recompute ? &src : nullptr));
     }
     UWIE_TRY(select_lerp64(plan, s, P.pct64, st));
@@ -625,7 +624,6 @@ int uwie_device_status(uwie_ctx *ctx, void *stream, uint32_t *bits)
     if (v) {
         set_error("device status 0x%x:%s the results of the calls since the last check are not valid", v,
                   (v & UWIE_STATUS_CANNY_LABEL) ? " Canny hysteresis met a component label that this launch did not write (k_canny.hip);"
-                  : (v & UWIE_STATUS_FALLBACK_SYNC) ? " the percentile fallback's blocks gave up waiting for each other (k_select.hip);"
                   : (v & UWIE_STATUS_QTREE_BOUNDS) ? " a quadtree score fell outside its histogram interval (k_airlight.hip, tuning q_hist = 3);"
                   : (v & UWIE_STATUS_FEATURE_COUNTS) ? " a frame's feature histograms do not count every pixel (k_extractor.hip);"
                   : (v & UWIE_STATUS_DIFF_RANK) ? " a gated DifferentiableEnhancement image has no valid sorted position (an IndexError, ValueError or OverflowError in Python);"

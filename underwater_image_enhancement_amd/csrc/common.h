@@ -279,7 +279,7 @@ struct SelectPlan {
     // linear-digit path (select_lin_*): per (image, channel) state, candidate lists and fallback flags
     void *lin;
     float *lists;          // [B*3][kLinLists][cap]
-    uint32_t *flags;       // [B*3] 1 = a candidate list overflowed, use the generic sweeps
+    uint32_t *flags;       // [B*3] 1 = a candidate list overflowed, use the key-digit passes
     uint32_t cap;
     bool predicted;        // the producer files the predicted windows: the collecting sweep is the rare fallback
     uint32_t ranks[2 * kMaxPct];
@@ -329,13 +329,12 @@ struct RestoreSrc;
 // predict != nullptr: the target bins are predicted from a subsample of the restored image (k_lin_sample)
 int select_lin_begin(Shape s, const double *q_percent, int nq, void *ws, hipStream_t st, SelectPlan *plan,
                      const RestoreSrc *predict = nullptr);
-// src != nullptr: the values are recomputed from *src; d_planar is then only written (and read back) for planes that
-// fall back to the generic sweeps
-int select_lin_run(const SelectPlan &plan, float *d_planar, Shape s, hipStream_t st, const RestoreSrc *src = nullptr);
+// src != nullptr: the values are recomputed from *src (d_planar is not read); flagged planes take the key-digit passes
+int select_lin_run(const SelectPlan &plan, const float *d_planar, Shape s, hipStream_t st, const RestoreSrc *src = nullptr);
 // float64 planes (ES surface): linear first digit by the producer, one collecting sweep, finish on the lists
 int select_lin_begin64(Shape s, const double *q_percent, int nq, void *ws, hipStream_t st, SelectPlan *plan,
                        const RestoreSrc *predict = nullptr);
-int select_lin_run64(const SelectPlan &plan, double *d_planar, Shape s, hipStream_t st, const RestoreSrc *src = nullptr);
+int select_lin_run64(const SelectPlan &plan, const double *d_planar, Shape s, hipStream_t st, const RestoreSrc *src = nullptr);
 int select_begin(Shape s, const double *q_percent, int nq, void *ws, hipStream_t st, SelectPlan *plan);
 int select_run(const SelectPlan &plan, const float *d_vals, int planar, Shape s, bool pass1_done, hipStream_t st);
 int select_lerp(const SelectPlan &plan, Shape s, float *d_out, hipStream_t st);                     // [B][3][nq]
@@ -378,10 +377,10 @@ struct RestoreSrc {
 // t32: d_t holds float32 data (RestoreSrc::t32)
 int launch_restore_planar_hist(const uint8_t *d_in, const int32_t *d_kind, const float *d_A, const double *d_t, Shape s,
                                float *d_planar, uint32_t *d_ghist, hipStream_t st, bool linear = false,
-                               const uint32_t *d_only = nullptr, const SelectPlan *plan = nullptr, int t32 = 0);
+                               const SelectPlan *plan = nullptr, int t32 = 0);
 // the rank-counting sweep (k_restore_rank): counts below each predicted window + the windows' members, no histogram
 int launch_restore_rank(const RestoreSrc &src, Shape s, const SelectPlan &plan, hipStream_t st);
-int select_rank_run(const SelectPlan &plan, float *d_planar, Shape s, hipStream_t st, const RestoreSrc &src);
+int select_rank_run(const SelectPlan &plan, Shape s, hipStream_t st, const RestoreSrc &src);
 size_t tail_ws_bytes(Shape s, int tx, int ty);
 // d_pct: [B][3][pct_stride] = lo1, hi1 [, lo2, hi2]; two = second stretch present; gamma_mode 0/1/2
 int launch_tail_clahe(uwie_ctx *ctx, const float *d_planar, const float *d_pct, int pct_stride, float eps, int two,
@@ -397,8 +396,7 @@ int launch_tail_plain(const float *d_planar, const float *d_pct, int pct_stride,
 // ES surface (float64): recover_image (ES:237-249) -> planar float64 + first select digit; color_enhancement
 // (ES:269-270, eps 1e-10) [-> gamma_correction (ES:284-285)] -> (y*255).astype(u8) (main.py:155) / float32 copy
 int launch_recover64_planar_hist(const uint8_t *d_in, const float *d_A, const double *d_t, Shape s, double *d_planar,
-                                 uint32_t *d_ghist, hipStream_t st, bool linear = false, const uint32_t *d_only = nullptr,
-                                 const SelectPlan *plan = nullptr);
+                                 uint32_t *d_ghist, hipStream_t st, bool linear = false, const SelectPlan *plan = nullptr);
 int launch_tail_plain64(const double *d_planar, const double *d_pct, Shape s, int apply_gamma, double gamma,
                         uint8_t *d_out_u8, float *d_out_f32, hipStream_t st, const RestoreSrc *src = nullptr,
                         double *d_out_f64 = nullptr);

@@ -35,15 +35,14 @@ __device__ __forceinline__ uint8_t sat_u8(int v) { return (uint8_t)min(max(v, 0)
 
 // grid (nblk, B), block 256.  LIN: the histogram is over lin_digit() (select_lin_*), else over the top 11 key bits.
 // planar == nullptr: histogram only (the consumers recompute the image from S, restore.h); ghist == nullptr: image
-// only; only != nullptr: images none of whose three planes is flagged are skipped.
+// only.
 // COLLECT (with LIN): values whose digit lies in one of the plane's NW predicted windows (LinState::wlo, wspan; two for
 // two percentiles, four for strategy 3's four) are filed into the window's list on the way: staged in LDS, moved out in
 // batches (a block reserves list space once per batch and window).
 // V = double: the ES surface's float64 image (restore.h four64), float64 planes and lists.
 template <bool LIN, bool COLLECT, int NW = 2, typename V = float>
 __global__ void __launch_bounds__(256) k_restore_planar_hist(RestoreSrc S, int npx, V *__restrict__ planar,
-                                                             uint32_t *__restrict__ ghist,
-                                                             const uint32_t *__restrict__ only, LinState *__restrict__ lin,
+                                                             uint32_t *__restrict__ ghist, LinState *__restrict__ lin,
                                                              V *__restrict__ lists, uint32_t cap)
 {
     constexpr int NB = LIN ? 2052 : 2048;
@@ -61,7 +60,6 @@ __global__ void __launch_bounds__(256) k_restore_planar_hist(RestoreSrc S, int n
     __shared__ uint32_t scount[NS], sbase[NS];
     __shared__ double dtab[FAST ? 768 : 1];
     const int b = blockIdx.y, tid = threadIdx.x;
-    if (only && !(only[3 * b] | only[3 * b + 1] | only[3 * b + 2])) return;
     if (ghist) {
         for (int i = tid; i < 3 * NB; i += 256) (&h[0][0])[i] = 0;
         if (tid < NS) scount[tid] = 0;
@@ -323,7 +321,7 @@ __global__ void __launch_bounds__(256) k_restore_planar_hist(RestoreSrc S, int n
 //     to its count, one inside the window goes to the window's list, as in the histogram sweep.
 // k_rank_scan (k_select.hip) then finds each rank in (below, below + list length) and k_lin_finish selects inside the list.
 // A rank outside its window (the sample misled the prediction, ~6e-5 per window), or a list that overflowed, flags the
-// plane for the generic sweeps exactly as before.  Results are the same order statistics: identical bytes.
+// plane for the key-digit passes (k_select.hip k_sel_pass).  Results are the same order statistics: identical bytes.
 // grid (nblk, B), block 256.  float64 transmission only (UWIE_INTER_F32T keeps the histogram sweep: there the float32
 // restore IS the value).
 constexpr float kRankMargin = 1e-5f;
@@ -1384,8 +1382,7 @@ float gamma_exponent(int mode, double g) { return mode == 1 ? (float)g : mode ==
 }  // namespace
 
 int launch_restore_planar_hist(const uint8_t *d_in, const int32_t *d_kind, const float *d_A, const double *d_t, Shape s,
-                               float *d_planar, uint32_t *d_ghist, hipStream_t st, bool linear, const uint32_t *d_only,
-                               const SelectPlan *plan, int t32)
+                               float *d_planar, uint32_t *d_ghist, hipStream_t st, bool linear, const SelectPlan *plan, int t32)
 {
     // 24.6 KB of LDS per block: six blocks per CU, 1536 resident on the chip.  Enough blocks for several full rounds
     // (2048 blocks were 1.33 rounds: a third of the chip idle for half the kernel).
@@ -1403,16 +1400,16 @@ int launch_restore_planar_hist(const uint8_t *d_in, const int32_t *d_kind, const
     if (plan) {
         UWIE_REQUIRE(linear && d_ghist == plan->ghist, "restore: a selection plan goes with its own linear histogram");
         if (plan->nq <= 2)
-            UWIE_LAUNCH(k_restore_hist_collect, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist, d_only,
+            UWIE_LAUNCH(k_restore_hist_collect, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist,
                         (LinState *)plan->lin, plan->lists, plan->cap);
         else
-            UWIE_LAUNCH(k_restore_hist_collect4, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist, d_only,
+            UWIE_LAUNCH(k_restore_hist_collect4, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist,
                         (LinState *)plan->lin, plan->lists, plan->cap);
     } else if (linear) {
-        UWIE_LAUNCH(k_restore_hist_lin, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist, d_only,
+        UWIE_LAUNCH(k_restore_hist_lin, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist,
                     (LinState *)nullptr, (float *)nullptr, 0u);
     } else {
-        UWIE_LAUNCH(k_restore_hist_key, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist, d_only,
+        UWIE_LAUNCH(k_restore_hist_key, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist,
                     (LinState *)nullptr, (float *)nullptr, 0u);
     }
     UWIE_LAUNCH_CHECK();
@@ -1435,7 +1432,7 @@ int launch_restore_rank(const RestoreSrc &src, Shape s, const SelectPlan &plan, 
 }
 
 int launch_recover64_planar_hist(const uint8_t *d_in, const float *d_A, const double *d_t, Shape s, double *d_planar,
-                                 uint32_t *d_ghist, hipStream_t st, bool linear, const uint32_t *d_only, const SelectPlan *plan)
+                                 uint32_t *d_ghist, hipStream_t st, bool linear, const SelectPlan *plan)
 {
     int nblk = cdiv(12288, s.B);
     nblk = nblk < 16 ? 16 : nblk > 384 ? 384 : nblk;
@@ -1448,13 +1445,13 @@ int launch_recover64_planar_hist(const uint8_t *d_in, const float *d_A, const do
     const auto k_recover64_hist_key = k_restore_planar_hist<false, false, 2, double>;
     if (plan) {
         UWIE_REQUIRE(linear && d_ghist == plan->ghist && plan->nq <= 2, "recover: a selection plan goes with its own linear histogram");
-        UWIE_LAUNCH(k_recover64_hist_collect, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist, d_only,
+        UWIE_LAUNCH(k_recover64_hist_collect, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist,
                     (LinState *)plan->lin, reinterpret_cast<double *>(plan->lists), plan->cap);
     } else if (linear) {
-        UWIE_LAUNCH(k_recover64_hist_lin, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist, d_only, (LinState *)nullptr,
+        UWIE_LAUNCH(k_recover64_hist_lin, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist, (LinState *)nullptr,
                     (double *)nullptr, 0u);
     } else {
-        UWIE_LAUNCH(k_recover64_hist_key, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist, d_only, (LinState *)nullptr,
+        UWIE_LAUNCH(k_recover64_hist_key, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist, (LinState *)nullptr,
                     (double *)nullptr, 0u);
     }
     UWIE_LAUNCH_CHECK();

@@ -6,10 +6,13 @@
 //     a = sorted[prev], b = sorted[prev + 1];  r = a + (b - a) * t;  if t >= 0.5: r = b - (b - a) * (1 - t)
 // The index arithmetic depends only on (n, q) and is done on the host in that dtype; the two order statistics per
 // percentile are found EXACTLY on the device by an MSD radix select on the order-preserving integer image of the
-// float bits (float32: 11+11+10 bits, float64: 5x11+9): per digit one LDS-privatised histogram sweep over the channel
-// plane, then a tiny scan kernel that narrows every query to the bucket holding its rank.  Up to 8 ranks
-// (4 percentiles) per channel are resolved in the same sweeps; queries sharing a prefix share a histogram ("group").
-// A producer kernel may accumulate the first digit's histogram itself (k_fused.hip), saving one sweep.
+// float bits (float32: 11+11+10 bits, float64: 5x11+9): one launch of k_sel_pass per digit.  Its blocks count slabs of the
+// channel plane into LDS and add the counts to the plane's histogram; the block that arrives last at the plane's ticket
+// narrows every query to the bucket holding its rank (no block waits for another).  Up to 8 ranks (4 percentiles) per
+// channel are resolved in the same passes; queries sharing a prefix share a histogram ("group").  The values come from
+// stored planes or are recomputed from the frame and the transmission (restore.h).  A producer kernel may accumulate the
+// first digit's histogram itself (k_fused.hip), saving one sweep.  The same passes answer the planes that the linear-digit
+// and rank-counting routes below flag.
 #include <cmath>
 #include <cstdlib>
 
@@ -55,23 +58,26 @@ struct SelState {                 // one per (image, channel)
     uint32_t rank[kMaxRanks];     // remaining rank inside the prefix bucket
     uint32_t gid[kMaxRanks];      // histogram group of the query
     uint32_t ngroups;
+    uint32_t ticket;              // blocks of the running pass that have added their counts (k_sel_pass)
 };
+// (select_ws_bytes carves the states at this stride for both key widths)
+static_assert(sizeof(SelState<uint64_t>) == 200 && sizeof(SelState<uint32_t>) <= 200, "selection state layout");
 
 struct RankList {
     uint32_t r[kMaxRanks];
     int n;
 };
+
 template <typename V>
 struct FracList {
     V t[kMaxPct];
     int n;
 };
 
+// the state before the first pass: every query in group 0 with its whole rank
 template <typename K>
-__global__ void k_sel_init(SelState<K> *st, int nbc, RankList ranks)
+__device__ SelState<K> sel_state(const RankList &ranks)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nbc) return;
     SelState<K> s;
     for (int q = 0; q < kMaxRanks; ++q) {
         s.prefix[q] = 0;
@@ -80,7 +86,16 @@ __global__ void k_sel_init(SelState<K> *st, int nbc, RankList ranks)
         s.gid[q] = 0;
     }
     s.ngroups = 1;
-    st[i] = s;
+    s.ticket = 0;
+    return s;
+}
+
+template <typename K>
+__global__ void k_sel_init(SelState<K> *st, int nbc, RankList ranks)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nbc) return;
+    st[i] = sel_state<K>(ranks);
 }
 
 template <typename V>
@@ -94,7 +109,7 @@ __device__ __forceinline__ void sel_count(uint32_t *h, V v, int shift, int bits,
         atomicAdd(&h[d], 1u);
     } else {
         // prefixes of distinct groups differ, so at most one matches: select its index, then one conditional atomic
-        // (gp[g] for g >= ng holds a value no prefix can take, see k_sel_hist)
+        // (gp[g] for g >= ng holds a value no prefix can take, see k_sel_pass)
         const K pre = key >> (shift + bits);
         uint32_t idx = 0xffffffffu;
 #pragma unroll
@@ -107,126 +122,264 @@ __device__ __forceinline__ void sel_count(uint32_t *h, V v, int shift, int bits,
     }
 }
 
-// grid (blocks, B*3); dynamic LDS = ng_cap * nbins * 4 bytes.  Each block sweeps a contiguous slab of the plane with
-// 16-byte loads where the layout allows; only elements whose resolved prefix matches a query group are counted.
-template <typename V>
-__global__ void __launch_bounds__(256) k_sel_hist(const V *__restrict__ vals, size_t img_stride, size_t chan_stride,
-                                                  int elem_stride, int n,
-                                                  const SelState<typename Traits<V>::K> *__restrict__ st, int shift,
-                                                  int bits, int first_pass, int ng_cap, uint32_t *__restrict__ ghist,
-                                                  const uint32_t *__restrict__ only)
+// digit d (0 <= d < nbins, nbins <= 2304) with excl(d) <= rank < incl(d) over the LDS counts h[]; all 256 threads call
+__device__ void block_find_digit(const uint32_t *h, int nbins, uint32_t rank, uint32_t *wsum, uint32_t *found,
+                                 uint32_t &digit, uint32_t &rrank)
 {
-    using K = typename Traits<V>::K;
-    constexpr int VEC = 16 / sizeof(V);
-    extern __shared__ uint32_t h[];
-    const int bc = blockIdx.y, nbins = 1 << bits;
-    if (only && !only[bc]) return;  // fallback sweeps of the linear path: only planes whose candidate list overflowed
-    const SelState<K> *s = st + bc;
-    const int ng = first_pass ? 1 : min((int)s->ngroups, ng_cap);
-    K gp[kMaxRanks];
-#pragma unroll
-    for (int g = 0; g < kMaxRanks; ++g) gp[g] = g < ng ? s->gprefix[g] : ~K(0);  // ~0 >> (shift + bits) is not a prefix
-    for (int i = threadIdx.x; i < ng * nbins; i += 256) h[i] = 0;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, per = (nbins + 255) / 256;
+    uint32_t loc = 0;
+    for (int i = 0; i < per; ++i) {
+        const int k = tid * per + i;
+        if (k < nbins) loc += h[k];
+    }
+    uint32_t incl = wave_incl_scan_u32(loc);
     __syncthreads();
-    const V *v = vals + (size_t)(bc / 3) * img_stride + (size_t)(bc % 3) * chan_stride;
-    const uint32_t mask = (uint32_t)nbins - 1;
-    const int per = (((n + 3) / 4 + gridDim.x - 1) / gridDim.x) * 4;                // slab, multiple of 4 elements
-    const int lo = min(n, blockIdx.x * per), hi = min(n, lo + per);                 // lo == hi for surplus blocks
-    if (elem_stride == 1 && ((size_t)v & 15) == 0) {
-        const int hiv = lo + ((hi - lo) / VEC) * VEC;
-        constexpr int U = 4;  // 16-byte loads in flight per thread: the sweep is latency-bound, not compute-bound
-        int i = lo + threadIdx.x * VEC;
-        for (; i + (U - 1) * 256 * VEC < hiv; i += U * 256 * VEC) {
-            uint4 raw[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) raw[u] = *reinterpret_cast<const uint4 *>(v + i + u * 256 * VEC);
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                V q[VEC];
-                *reinterpret_cast<uint4 *>(q) = raw[u];
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) sel_count<V>(h, q[j], shift, bits, mask, first_pass, ng, nbins, gp);
+    if (lane == 63) wsum[w] = incl;
+    if (tid == 0) { found[0] = (uint32_t)nbins - 1; found[1] = 0; }
+    __syncthreads();
+    for (int i = 0; i < w; ++i) incl += wsum[i];
+    const uint32_t excl = incl - loc;
+    if (excl <= rank && rank < incl) {
+        uint32_t acc = excl;
+        for (int i = 0; i < per; ++i) {
+            const int k = tid * per + i;
+            const uint32_t c = k < nbins ? h[k] : 0;
+            if (rank < acc + c) {
+                found[0] = (uint32_t)k;
+                found[1] = rank - acc;
+                break;
             }
+            acc += c;
         }
-        for (; i < hiv; i += 256 * VEC) {
-            V q[VEC];
-            *reinterpret_cast<uint4 *>(q) = *reinterpret_cast<const uint4 *>(v + i);
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) sel_count<V>(h, q[j], shift, bits, mask, first_pass, ng, nbins, gp);
-        }
-        for (int i = hiv + threadIdx.x; i < hi; i += 256) sel_count<V>(h, v[i], shift, bits, mask, first_pass, ng, nbins, gp);
-    } else {
-        for (int i = lo + threadIdx.x; i < hi; i += 256)
-            sel_count<V>(h, v[(size_t)i * elem_stride], shift, bits, mask, first_pass, ng, nbins, gp);
     }
     __syncthreads();
-    uint32_t *gh = ghist + (size_t)bc * kMaxRanks * kBins;
-    for (int i = threadIdx.x; i < ng * nbins; i += 256) {
-        const uint32_t c = h[i];
-        if (c) atomicAdd(&gh[(i / nbins) * kBins + (i % nbins)], c);
-    }
+    digit = found[0];
+    rrank = found[1];
+    __syncthreads();
 }
 
-// one block per (image, channel): narrow each query by one digit, then regroup the prefixes
-template <typename V>
-__global__ void __launch_bounds__(256) k_sel_scan(SelState<typename Traits<V>::K> *__restrict__ st,
-                                                  const uint32_t *__restrict__ ghist, int bits, int nq, int last_pass,
-                                                  V *__restrict__ os, const uint32_t *__restrict__ only)
+// Value sources of k_sel_pass: each(bc, lo, hi, f) calls f(v) for the values of plane bc at the positions lo .. hi - 1 that
+// the calling thread owns (lo is a multiple of 4; all 256 threads of the block call).
+// Stored values: [B][3][n] planes (planar) or [B][n][3] pixels, with 16-byte loads where the layout allows.
+template <typename T>
+struct StoredVals {
+    using V = T;
+    const V *vals;
+    size_t img_stride, chan_stride;
+    int elem_stride;
+    template <class F>
+    __device__ __forceinline__ void each(int bc, int lo, int hi, F &&f) const
+    {
+        constexpr int VEC = 16 / sizeof(V);
+        const V *v = vals + (size_t)(bc / 3) * img_stride + (size_t)(bc % 3) * chan_stride;
+        if (elem_stride == 1 && ((size_t)v & 15) == 0) {
+            const int hiv = lo + ((hi - lo) / VEC) * VEC;
+            constexpr int U = 4;  // 16-byte loads in flight per thread: the sweep is latency-bound, not compute-bound
+            int i = lo + threadIdx.x * VEC;
+            for (; i + (U - 1) * 256 * VEC < hiv; i += U * 256 * VEC) {
+                uint4 raw[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) raw[u] = *reinterpret_cast<const uint4 *>(v + i + u * 256 * VEC);
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    V q[VEC];
+                    *reinterpret_cast<uint4 *>(q) = raw[u];
+#pragma unroll
+                    for (int j = 0; j < VEC; ++j) f(q[j]);
+                }
+            }
+            for (; i < hiv; i += 256 * VEC) {
+                V q[VEC];
+                *reinterpret_cast<uint4 *>(q) = *reinterpret_cast<const uint4 *>(v + i);
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) f(q[j]);
+            }
+            for (int i = hiv + threadIdx.x; i < hi; i += 256) f(v[i]);
+        } else {
+            for (int i = lo + threadIdx.x; i < hi; i += 256) f(v[(size_t)i * elem_stride]);
+        }
+    }
+};
+// Values recomputed from the frame and the transmission, by the expressions of the producers that histogram them
+// (k_fused.hip k_restore_planar_hist): float32 restore (UWIE_INTER_F32T: restore.h one32_raw), or the ES surface's float64
+// image (restore.h four64's expression, on the same groups of four pixels, for the plane's channel only).  The channel is a template argument: a[c] / att[c] with a
+// runtime c would keep the restore's registers in scratch memory.
+template <typename T>
+struct RestoredVals {
+    using V = T;
+    RestoreSrc S;
+    int npx;
+    template <int C, class F>
+    __device__ __forceinline__ void channel(int b, int lo, int hi, F &f) const
+    {
+        if constexpr (sizeof(V) == 8) {  // four64's sequence for channel C alone: the same groups, the same branch per group
+            RestoreImg R;
+            R.init(S, b, (size_t)npx);
+            for (int p = lo + threadIdx.x * 4; p < hi; p += 1024) {
+                const int m = min(4, hi - p);
+                uint32_t u[4];
+                double tv[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    u[i] = i < m ? R.img[(size_t)(p + i) * 3 + C] : 0u;
+                    tv[i] = i < m ? R.t[p + i] : 1.0;
+                }
+                const bool fast = R.recip_ok(tv[0]) && R.recip_ok(tv[1]) && R.recip_ok(tv[2]) && R.recip_ok(tv[3]);
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (i < m) f(fast ? R.one64_fast(u[i], C, tv[i], R.recip(tv[i])) : R.one64(u[i], C, tv[i]));
+            }
+        } else if (S.t32) {
+            RestoreImg32 R;
+            R.init(S, b, (size_t)npx);
+            for (int p = lo + threadIdx.x; p < hi; p += 256)
+                f(fminf(fmaxf(R.one32_raw(R.img[(size_t)p * 3 + C], C, R.recip32(R.tf()[p])), 0.0f), 1.0f));
+        } else {
+            RestoreImg R;
+            R.init(S, b, (size_t)npx);
+            for (int p = lo + threadIdx.x; p < hi; p += 256) {
+                const uint32_t u = R.img[(size_t)p * 3 + C];
+                const double tv = R.t[p];
+                f(R.recip_ok(tv) ? R.one_fast(u, C, tv, R.recip(tv)) : R.one(u, C, tv));
+            }
+        }
+    }
+    template <class F>
+    __device__ __forceinline__ void each(int bc, int lo, int hi, F &&f) const
+    {
+        const int b = bc / 3, c = bc % 3;
+        if (c == 0) channel<0>(b, lo, hi, f);
+        else if (c == 1) channel<1>(b, lo, hi, f);
+        else channel<2>(b, lo, hi, f);
+    }
+};
+
+// One digit of the select: grid (blocks, B*3), dynamic LDS = (pass ? nq : 1) * nbins * 4 bytes.  Each block counts a
+// contiguous slab of the plane (sweep = 0: nothing, the producer has counted the first digit), counting only the elements
+// whose resolved prefix matches a query group, and adds its counts to the plane's histogram.  Then it takes a ticket; the
+// block that arrives last narrows each query by the digit, regroups the prefixes, writes the order statistics after the last
+// digit, and leaves the histogram counters and the ticket at zero for the next pass.  No block waits for another, so the
+// result does not depend on how the blocks are dispatched.  only != nullptr: planes with only[bc] == 0 return at once.
+template <class Src>
+__global__ void __launch_bounds__(256) k_sel_pass(Src src, int n, SelState<typename Traits<typename Src::V>::K> *__restrict__ st,
+                                                  int pass, int nq, int sweep, uint32_t *__restrict__ ghist,
+                                                  typename Src::V *__restrict__ os, const uint32_t *__restrict__ only)
 {
+    using V = typename Src::V;
     using K = typename Traits<V>::K;
-    __shared__ uint32_t wsum[4];
-    __shared__ uint32_t found_digit, found_rank;
-    const int bc = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    extern __shared__ uint32_t h[];
+    __shared__ uint32_t wsum[4], found[2];
+    __shared__ SelState<K> ss;  // the last arriver's copy of the plane's state
+    constexpr int kStateWords = sizeof(SelState<K>) / 4;
+    const int bc = blockIdx.y, tid = threadIdx.x;
     if (only && !only[bc]) return;
     SelState<K> *s = st + bc;
-    const int nbins = 1 << bits, per = nbins / 256;
-    const uint32_t *gh = ghist + (size_t)bc * kMaxRanks * kBins;
+    const int shift = Traits<V>::shift(pass), bits = Traits<V>::bits(pass), nbins = 1 << bits;
+    const int ng = pass == 0 ? 1 : min((int)s->ngroups, nq);
+    uint32_t *gh = ghist + (size_t)bc * kSelGroupStride;
+    if (sweep) {
+        K gp[kMaxRanks];
+#pragma unroll
+        for (int g = 0; g < kMaxRanks; ++g) gp[g] = g < ng ? s->gprefix[g] : ~K(0);  // ~0 >> (shift + bits) is not a prefix
+        for (int i = tid; i < ng * nbins; i += 256) h[i] = 0;
+        __syncthreads();
+        const uint32_t mask = (uint32_t)nbins - 1;
+        const int per = (((n + 3) / 4 + gridDim.x - 1) / gridDim.x) * 4;  // slab, multiple of 4 elements
+        const int lo = min(n, blockIdx.x * per), hi = min(n, lo + per);  // lo == hi for surplus blocks
+        src.each(bc, lo, hi, [&](V v) { sel_count<V>(h, v, shift, bits, mask, pass == 0, ng, nbins, gp); });
+        __syncthreads();
+        for (int i = tid; i < ng * nbins; i += 256) {
+            const uint32_t c = h[i];
+            if (c) atomicAdd(&gh[(i / nbins) * kBins + (i % nbins)], c);
+        }
+    }
+    // arrival: the counts are device-scope atomics, released at agent scope before the ticket; the last arriver acquires
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const uint32_t arrived = __hip_atomic_fetch_add(&s->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        found[0] = arrived == gridDim.x - 1;
+        if (found[0]) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+    }
+    __syncthreads();
+    if (!found[0]) return;  // block-uniform
+    // behind the acquire, plain loads: the plane's state, and its counts eight loads in flight per thread
+    if (tid < kStateWords) reinterpret_cast<uint32_t *>(&ss)[tid] = reinterpret_cast<const uint32_t *>(s)[tid];
+    for (int i0 = 0; i0 < ng * nbins; i0 += 8 * 256) {
+        uint32_t c[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = i0 + u * 256 + tid;
+            c[u] = i < ng * nbins ? gh[(i / nbins) * kBins + (i % nbins)] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (i0 + u * 256 + tid < ng * nbins) h[i0 + u * 256 + tid] = c[u];
+    }
+    __syncthreads();
+    for (int i = tid; i < ng * nbins; i += 256) gh[(i / nbins) * kBins + (i % nbins)] = 0;  // (for the next pass)
     for (int q = 0; q < nq; ++q) {
-        const uint32_t *hq = gh + s->gid[q] * kBins;
-        const uint32_t rank = s->rank[q];
-        uint32_t loc = 0;
-        for (int i = 0; i < per; ++i) loc += hq[tid * per + i];
-        uint32_t incl = wave_incl_scan_u32(loc);
-        if (lane == 63) wsum[w] = incl;
-        __syncthreads();
-        uint32_t off = 0;
-        for (int i = 0; i < w; ++i) off += wsum[i];
-        incl += off;
-        const uint32_t excl = incl - loc;
-        if (excl <= rank && rank < incl) {
-            uint32_t acc = excl;
-            for (int i = 0; i < per; ++i) {
-                const uint32_t c = hq[tid * per + i];
-                if (rank < acc + c) {
-                    found_digit = tid * per + i;
-                    found_rank = rank - acc;
-                    break;
-                }
-                acc += c;
-            }
-        }
-        __syncthreads();
+        uint32_t d, rr;
+        block_find_digit(h + ss.gid[q] * nbins, nbins, ss.rank[q], wsum, found, d, rr);
         if (tid == 0) {
-            s->prefix[q] = (s->prefix[q] << bits) | (K)found_digit;
-            s->rank[q] = found_rank;
+            ss.prefix[q] = (ss.prefix[q] << bits) | (K)d;
+            ss.rank[q] = rr;
         }
-        __syncthreads();
     }
     if (tid == 0) {
-        uint32_t ng = 0;
+        uint32_t ngr = 0;
         for (int q = 0; q < nq; ++q) {
             uint32_t g = 0;
-            for (; g < ng; ++g)
-                if (s->gprefix[g] == s->prefix[q]) break;
-            if (g == ng) s->gprefix[ng++] = s->prefix[q];
-            s->gid[q] = g;
+            for (; g < ngr; ++g)
+                if (ss.gprefix[g] == ss.prefix[q]) break;
+            if (g == ngr) ss.gprefix[ngr++] = ss.prefix[q];
+            ss.gid[q] = g;
         }
-        s->ngroups = ng;
-        if (last_pass)
-            for (int q = 0; q < nq; ++q) os[bc * kMaxRanks + q] = Traits<V>::value(s->prefix[q]);
+        ss.ngroups = ngr;
+        ss.ticket = 0;
+        if (pass == Traits<V>::NPASS - 1)
+            for (int q = 0; q < nq; ++q) os[bc * kMaxRanks + q] = Traits<V>::value(ss.prefix[q]);
     }
+    __syncthreads();
+    if (tid < kStateWords) reinterpret_cast<uint32_t *>(s)[tid] = reinterpret_cast<const uint32_t *>(&ss)[tid];
 }
 
+// All digits of the select for the planes of `only` (every plane: nullptr).  The state (k_sel_init, or the scan kernels of the
+// routes below) and the counters (zero, or the first digit's when pass1_done) are ready.
+template <class Src>
+int sel_passes(const SelectPlan &plan, const Src &src, int n, int nbc, int blocks, bool pass1_done, const uint32_t *only,
+               hipStream_t st)
+{
+    using V = typename Src::V;
+    using K = typename Traits<V>::K;
+    const int nq = 2 * plan.nq;
+    for (int p = 0; p < Traits<V>::NPASS; ++p) {
+        const int sweep = p > 0 || !pass1_done;
+        const size_t lds = (size_t)(p == 0 ? 1 : nq) * (1u << Traits<V>::bits(p)) * sizeof(uint32_t);
+        UWIE_LAUNCH(k_sel_pass<Src>, dim3(sweep ? blocks : 1, nbc), dim3(256), lds, st, src, n, (SelState<K> *)plan.state, p, nq,
+                    sweep, plan.ghist, (V *)plan.os, only);
+        UWIE_LAUNCH_CHECK();
+    }
+    return UWIE_OK;
+}
+
+// blocks per plane of a pass.  Stored values: few, fat blocks (the LDS histogram is zeroed and flushed once per block, and every
+// block pays an agent-scope release on the pass's critical path), at least 256 in all: with the 1024 of the former sweep kernel
+// the DifferentiableEnhancement forward took 1.27 instead of 1.21 ms at 8 x 4K and 96 instead of 84 us at 32 x 224^2.
+// Recomputed values (the flagged planes of the linear-digit and rank routes): 96 per plane, the grid of the round-4 fallback
+// (11 bytes per value, three planes per frame: 24 took 2.8 ms for two flagged 4K planes), whatever the batch.
+int pass_blocks(long long n, int nbc, bool recomputed)
+{
+    if (recomputed) return 96;
+    int blocks = (int)((n + 262143) / 262144);
+    if (blocks * nbc < 256) blocks = cdiv(256, nbc);
+    return std::max(1, std::min(blocks, 256));
+}
 // NumPy's _lerp (numpy/lib/_function_base_impl.py), in the data's dtype
 template <typename V>
 __device__ __forceinline__ V np_lerp(V a, V b, V t)
@@ -318,21 +471,15 @@ __global__ void k_sel_init_stretch_ranks(SelState<uint32_t> *st, int nbc, const 
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nbc) return;
     const float *pr = params + (size_t)(i / 3) * stride;
-    SelState<uint32_t> s;
-    for (int q = 0; q < kMaxRanks; ++q) {
-        s.prefix[q] = 0;
-        s.gprefix[q] = 0;
-        s.rank[q] = 0;
-        s.gid[q] = 0;
-    }
+    RankList ranks;
+    ranks.n = 2;
     for (int q = 0; q < 2; ++q) {
         const double pos = ((double)pr[q] / 100.0) * (double)n;
         long long idx = (long long)pos;  // int(): truncation toward zero
         idx = idx < 0 ? 0 : idx > n - 1 ? n - 1 : idx;
-        s.rank[q] = (uint32_t)idx;
+        ranks.r[q] = (uint32_t)idx;
     }
-    s.ngroups = 1;
-    st[i] = s;
+    st[i] = sel_state<uint32_t>(ranks);
 }
 
 // deep_learning_parameters.DifferentiableEnhancement.color_stretch (:73-77): the same two sorted positions per image, by
@@ -344,51 +491,23 @@ __global__ void k_sel_init_gated_ranks(SelState<uint32_t> *st, int nbc, const fl
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nbc) return;
     const float *pr = params + (size_t)(i / 3) * stride;
-    SelState<uint32_t> s;
-    for (int q = 0; q < kMaxRanks; ++q) {
-        s.prefix[q] = 0;
-        s.gprefix[q] = 0;
-        s.rank[q] = 0;
-        s.gid[q] = 0;
-    }
     int k[2];
     const bool ok0 = gated_rank(pr[0], n, &k[0]), ok1 = gated_rank(pr[1], n, &k[1]);
     const bool ok = ok0 && ok1;
-    s.rank[0] = ok ? (uint32_t)k[0] : 0u;
-    s.rank[1] = ok ? (uint32_t)k[1] : 0u;
+    RankList ranks;
+    ranks.n = 2;
+    ranks.r[0] = ok ? (uint32_t)k[0] : 0u;
+    ranks.r[1] = ok ? (uint32_t)k[1] : 0u;
     if (!ok && status) atomicOr(status, (uint32_t)UWIE_STATUS_DIFF_RANK);
-    s.ngroups = 1;
-    st[i] = s;
+    st[i] = sel_state<uint32_t>(ranks);
 }
 
 template <typename V>
-int run_t(const SelectPlan &plan, const V *d_vals, int planar, Shape s, bool pass1_done, hipStream_t st,
-          const uint32_t *only = nullptr)
+int run_t(const SelectPlan &plan, const V *d_vals, int planar, Shape s, bool pass1_done, hipStream_t st)
 {
-    using K = typename Traits<V>::K;
-    const long long n = (long long)s.npx();
-    const int nbc = s.B * 3;
-    SelState<K> *state = (SelState<K> *)plan.state;
-    // few, fat blocks: the LDS histogram is zeroed and flushed once per block
-    int blocks = (int)((n + 262143) / 262144);
-    if (blocks * nbc < 1024) blocks = cdiv(1024, nbc);
-    blocks = blocks < 1 ? 1 : blocks > 256 ? 256 : blocks;
-    const int ng_cap = 2 * plan.nq;  // at most one group per rank
-    for (int p = 0; p < Traits<V>::NPASS; ++p) {
-        const int shift = Traits<V>::shift(p), bits = Traits<V>::bits(p);
-        if (p > 0) UWIE_HIP_CHECK(hipMemsetAsync(plan.ghist, 0, sizeof(uint32_t) * (size_t)nbc * kMaxRanks * kBins, st));
-        if (p > 0 || !pass1_done) {
-            const size_t lds = (size_t)(p == 0 ? 1 : ng_cap) * (1u << bits) * sizeof(uint32_t);
-            UWIE_LAUNCH(k_sel_hist<V>, dim3(blocks, nbc), dim3(256), lds, st, d_vals, (size_t)n * 3,
-                        planar ? (size_t)n : (size_t)1, planar ? 1 : 3, (int)n, state, shift, bits, p == 0 ? 1 : 0, ng_cap,
-                        plan.ghist, only);
-            UWIE_LAUNCH_CHECK();
-        }
-        UWIE_LAUNCH(k_sel_scan<V>, dim3(nbc), dim3(256), 0, st, state, plan.ghist, bits, 2 * plan.nq,
-                    p == Traits<V>::NPASS - 1 ? 1 : 0, (V *)plan.os, only);
-        UWIE_LAUNCH_CHECK();
-    }
-    return UWIE_OK;
+    const int n = (int)s.npx(), nbc = s.B * 3;
+    const StoredVals<V> src{d_vals, (size_t)n * 3, planar ? (size_t)n : (size_t)1, planar ? 1 : 3};
+    return sel_passes(plan, src, n, nbc, pass_blocks(n, nbc, false), pass1_done, nullptr, st);
 }
 
 template <typename V>
@@ -417,42 +536,6 @@ uint32_t lin_cap(Shape s)
     const uint32_t dflt = (uint32_t)std::max<size_t>(65536, s.npx() / 64);
     const long v = tune().lin_cap;  // (0 outside an entry point: the workspace is sized for the default)
     return v > 0 && v < (long)dflt ? (uint32_t)v : dflt;
-}
-
-// digit d (0 <= d < nbins, nbins <= 2304) with excl(d) <= rank < incl(d) over the LDS counts h[]; all 256 threads call
-__device__ void block_find_digit(const uint32_t *h, int nbins, uint32_t rank, uint32_t *wsum, uint32_t *found,
-                                 uint32_t &digit, uint32_t &rrank)
-{
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, per = (nbins + 255) / 256;
-    uint32_t loc = 0;
-    for (int i = 0; i < per; ++i) {
-        const int k = tid * per + i;
-        if (k < nbins) loc += h[k];
-    }
-    uint32_t incl = wave_incl_scan_u32(loc);
-    __syncthreads();
-    if (lane == 63) wsum[w] = incl;
-    if (tid == 0) { found[0] = (uint32_t)nbins - 1; found[1] = 0; }
-    __syncthreads();
-    for (int i = 0; i < w; ++i) incl += wsum[i];
-    const uint32_t excl = incl - loc;
-    if (excl <= rank && rank < incl) {
-        uint32_t acc = excl;
-        for (int i = 0; i < per; ++i) {
-            const int k = tid * per + i;
-            const uint32_t c = k < nbins ? h[k] : 0;
-            if (rank < acc + c) {
-                found[0] = (uint32_t)k;
-                found[1] = rank - acc;
-                break;
-            }
-            acc += c;
-        }
-    }
-    __syncthreads();
-    digit = found[0];
-    rrank = found[1];
-    __syncthreads();
 }
 
 constexpr int kLinSampleOff = 4096;  // the sample histogram of a plane lives behind the producer's in its ghist group
@@ -490,15 +573,18 @@ __global__ void __launch_bounds__(256) k_lin_sample(RestoreSrc S, int npx, int s
 // one block per (image, channel): clears the state; with a sample (ns > 0) the window of percentile j spans the bins
 // that hold the sample ranks r_j*ns/n -+ delta, delta = 4 binomial standard deviations of the sample rank (+2); windows
 // that touch are merged.  shift: test knob, moves the windows up by that many bins.
-__global__ void __launch_bounds__(256) k_lin_predict(LinState *__restrict__ st, const uint32_t *__restrict__ ghist,
+__global__ void __launch_bounds__(256) k_lin_predict(LinState *__restrict__ st, uint32_t *__restrict__ ghist,
                                                      RankList ranks, uint32_t n, uint32_t ns, int shift)
 {
     __shared__ uint32_t h[kLinBins], wsum[4], found[2], wl[kMaxPct], wh[kMaxPct];
     const int bc = blockIdx.x, tid = threadIdx.x;
     if (tid < kMaxPct) { wl[tid] = kLinNoWin; wh[tid] = 0; }
     if (ns > 0) {
-        const uint32_t *gh = ghist + (size_t)bc * kSelGroupStride + kLinSampleOff;
-        for (int i = tid; i < kLinBins; i += 256) h[i] = gh[i];
+        uint32_t *gh = ghist + (size_t)bc * kSelGroupStride + kLinSampleOff;
+        for (int i = tid; i < kLinBins; i += 256) {
+            h[i] = gh[i];
+            gh[i] = 0;  // (the plane's counters are zero again for the key-digit passes of a flagged plane)
+        }
         __syncthreads();
         for (int j = 0; j < ranks.n / 2 && j < kMaxPct; ++j) {
             const double p = (double)ranks.r[2 * j] / (double)n, sd = sqrt((double)ns * p * (1.0 - p));
@@ -543,16 +629,20 @@ __global__ void __launch_bounds__(256) k_lin_predict(LinState *__restrict__ st, 
 // one block per (image, channel): the bin of every rank from the producer's histogram; ranks in the bins of exact
 // 0 / exact 1 are answered here.  A plane all of whose other queries fall into the predicted windows is done with
 // collecting (ngroups = 0, gid = the window's list); otherwise its queries are grouped by bin for the collecting sweep.
+// The plane's key-digit state is set and its histogram counters are left at zero, for the passes if the plane is flagged.
 template <typename V>
-__global__ void __launch_bounds__(256) k_lin_scan(LinState *__restrict__ st, const uint32_t *__restrict__ ghist,
-                                                  RankList ranks, V *__restrict__ os, uint32_t *__restrict__ flags,
-                                                  uint32_t cap, uint32_t *__restrict__ bar)
+__global__ void __launch_bounds__(256) k_lin_scan(LinState *__restrict__ st, uint32_t *__restrict__ ghist, RankList ranks,
+                                                  V *__restrict__ os, uint32_t *__restrict__ flags, uint32_t cap,
+                                                  SelState<typename Traits<V>::K> *__restrict__ sel)
 {
     __shared__ uint32_t h[kLinBins], wsum[4], found[2], qbin[kMaxRanks], qrr[kMaxRanks];
-    if (bar && threadIdx.x == 0) bar[blockIdx.x] = 0;  // the one-launch fallback's per-plane barrier counter (k_rank_fallback)
     const int bc = blockIdx.x, tid = threadIdx.x;
-    const uint32_t *gh = ghist + (size_t)bc * kSelGroupStride;
-    for (int i = tid; i < kLinBins; i += 256) h[i] = gh[i];
+    if (tid == 0) sel[bc] = sel_state<typename Traits<V>::K>(ranks);
+    uint32_t *gh = ghist + (size_t)bc * kSelGroupStride;
+    for (int i = tid; i < kLinBins; i += 256) {
+        h[i] = gh[i];
+        gh[i] = 0;
+    }
     __syncthreads();
     for (int q = 0; q < ranks.n; ++q) {
         uint32_t d, rr;
@@ -601,13 +691,13 @@ __global__ void __launch_bounds__(256) k_lin_scan(LinState *__restrict__ st, con
 // wlo .. wlo + wspan in its list (gcount of them) and `below` elements lie in the bins under it, so rank r belongs to the
 // window with below <= r < below + gcount, at position r - below of its list.  Bins 0 and kLinBins - 1 hold exact zeros and
 // exact ones only: a rank under a window that starts at bin 1 is 0, one above a window that ends at bin 2048 is 1.  Anything
-// else -- the prediction missed, or the list overflowed -- flags the plane for the generic sweeps.
+// else -- the prediction missed, or the list overflowed -- flags the plane for the key-digit passes (whose state is set here).
 __global__ void k_rank_scan(LinState *__restrict__ st, RankList ranks, float *__restrict__ os, uint32_t *__restrict__ flags,
-                            uint32_t cap, int nbc, uint32_t *__restrict__ bar)
+                            uint32_t cap, int nbc, SelState<uint32_t> *__restrict__ sel)
 {
     const int bc = blockIdx.x * blockDim.x + threadIdx.x;
     if (bc >= nbc) return;
-    bar[bc] = 0;  // the fallback's per-plane barrier counter (k_rank_fallback)
+    sel[bc] = sel_state<uint32_t>(ranks);
     LinState s = st[bc];
     bool miss = false;
     for (int q = 0; q < kMaxRanks; ++q) { s.rr[q] = 0; s.qbin[q] = 0; s.gid[q] = kLinDone; s.gbin[q] = kLinDone; }
@@ -1056,111 +1146,6 @@ __global__ void __launch_bounds__(1024) k_lin_finish(const LinState *__restrict_
     if (tid == 0) os[bc * kMaxRanks + q1] = Traits<V>::value((K)(s_nloc > r_mine + 1u ? prefix : s_kmin));
 }
 
-// The rank route's fallback in ONE launch (round 4): a plane the scan flagged -- a rank outside its predicted window, a list
-// that overflowed -- gets its four order statistics from three key-digit sweeps (11 + 11 + 10 bits, as k_sel_hist / k_sel_scan)
-// over values RECOMPUTED from the frame and the transmission: no stored float32 planes (12 B/px of workspace that a strategy-2
-// call no longer reserves), and one launch that returns at once for every unflagged plane instead of eleven that each do.
-// grid (G, B*3), block 256: the G blocks of a flagged plane meet at a counter in global memory between the sweeps.  Workgroups
-// are dispatched in the order of their linear index (x fastest), so the G blocks of a plane are dispatched together and the
-// blocks that wait can only be waiting for blocks that are resident or about to be: no deadlock while G fits the chip.  The
-// wait is bounded all the same (UWIE_STATUS_FALLBACK_SYNC).
-constexpr int kFallbackBlocks = 96;  // (24 took 2.8 ms for two flagged 4K planes: a block then sweeps 346 K pixels three times)
-__global__ void __launch_bounds__(256) k_rank_fallback(RestoreSrc S, int npx, RankList ranks, const uint32_t *__restrict__ flags,
-                                                       uint32_t *__restrict__ ghist, uint32_t *__restrict__ bar, float *__restrict__ os,
-                                                       uint32_t *__restrict__ status)
-{
-    const int bc = blockIdx.y;
-    if (!flags[bc]) return;  // block-uniform: the common case
-    __shared__ uint32_t h[4][2048], wsum[4], found[2];
-    __shared__ uint32_t s_pre[4], s_rank[4];
-    const int b = bc / 3, c = bc % 3, tid = threadIdx.x, G = gridDim.x, nq = ranks.n;
-    uint32_t *gh = ghist + (size_t)bc * kMaxRanks * kBins;  // 16384 counters: sweep 0 [0, 2048), sweep 1 [2048, 10240), sweep 2 [10240, 14336)
-    uint32_t phase = 0;
-    auto plane_barrier = [&]() {
-        ++phase;
-        __syncthreads();
-        if (tid == 0) {
-            __threadfence();
-            atomicAdd(&bar[bc], 1u);
-            uint32_t spins = 0;
-            while (__hip_atomic_load(&bar[bc], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < phase * (uint32_t)G) {
-                __builtin_amdgcn_s_sleep(8);
-                if (++spins > (1u << 22)) {  // seconds: a defect, not a wait
-                    atomicOr(status, (uint32_t)UWIE_STATUS_FALLBACK_SYNC);
-                    break;
-                }
-            }
-            __threadfence();
-        }
-        __syncthreads();
-    };
-    for (int i = blockIdx.x * 256 + tid; i < kMaxRanks * kBins; i += G * 256) gh[i] = 0;
-    plane_barrier();
-    RestoreImg R;
-    RestoreImg32 R32;  // UWIE_INTER_F32T: the float32 restore IS the value (restore.h pixel32)
-    if (S.t32) R32.init(S, b, (size_t)npx);
-    else R.init(S, b, (size_t)npx);
-    const int per = (npx + G - 1) / G, lo = min(npx, (int)blockIdx.x * per), hi = min(npx, lo + per);
-    uint32_t pre[4] = {0, 0, 0, 0}, rk[4] = {0, 0, 0, 0}, gpre[4] = {0, 0, 0, 0};
-    for (int q = 0; q < 4; ++q) rk[q] = q < nq ? ranks.r[q] : ranks.r[0];
-    int ng = 1;
-    uint32_t goff = 0;
-    for (int pass = 0; pass < 3; ++pass) {
-        const int shift = Traits<float>::shift(pass), bits = Traits<float>::bits(pass), nbins = 1 << bits;
-        for (int i = tid; i < ng * nbins; i += 256) (&h[0][0])[(i / nbins) * 2048 + (i % nbins)] = 0;
-        __syncthreads();
-        for (int p = lo + tid; p < hi; p += 256) {
-            float v;
-            if (S.t32) {
-                const uint32_t u = R32.img[(size_t)p * 3 + c];
-                v = fminf(fmaxf(R32.one32_raw(u, c, R32.recip32(R32.tf()[p])), 0.0f), 1.0f);
-            } else {
-                const uint32_t u = R.img[(size_t)p * 3 + c];
-                const double tv = R.t[p];
-                v = R.recip_ok(tv) ? R.one_fast(u, c, tv, R.recip(tv)) : R.one(u, c, tv);
-            }
-            const uint32_t key = f32_key(v), d = (key >> shift) & (uint32_t)(nbins - 1), hp = pass ? key >> (shift + bits) : 0u;
-            for (int g = 0; g < ng; ++g)
-                if (hp == gpre[g]) atomicAdd(&h[g][d], 1u);
-        }
-        __syncthreads();
-        for (int i = tid; i < ng * nbins; i += 256) {
-            const uint32_t cnt = h[i / nbins][i % nbins];
-            if (cnt) atomicAdd(&gh[goff + (uint32_t)i], cnt);
-        }
-        plane_barrier();
-        for (int i = tid; i < ng * nbins; i += 256) h[i / nbins][i % nbins] = __hip_atomic_load(&gh[goff + (uint32_t)i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        // every block narrows the four queries by this digit (redundantly: no second barrier), then regroups the prefixes
-        for (int q = 0; q < 4; ++q) {
-            int g = 0;
-            for (int j = 0; j < ng; ++j)
-                if (pre[q] == gpre[j]) g = j;
-            uint32_t d, rr;
-            block_find_digit(h[g], nbins, rk[q], wsum, found, d, rr);
-            if (tid == 0) {
-                s_pre[q] = (pre[q] << bits) | d;
-                s_rank[q] = rr;
-            }
-            __syncthreads();
-        }
-        for (int q = 0; q < 4; ++q) {
-            pre[q] = s_pre[q];
-            rk[q] = s_rank[q];
-        }
-        __syncthreads();
-        goff += (uint32_t)(ng * nbins);
-        ng = 0;
-        for (int q = 0; q < 4; ++q) {
-            bool seen = false;
-            for (int j = 0; j < ng; ++j) seen = seen || gpre[j] == pre[q];
-            if (!seen) gpre[ng++] = pre[q];
-        }
-    }
-    if (blockIdx.x == 0 && tid == 0)
-        for (int q = 0; q < nq; ++q) os[bc * kMaxRanks + q] = Traits<float>::value(pre[q]);
-}
-
 struct LinBufs {
     LinState *lin;
     float *lists;
@@ -1230,8 +1215,8 @@ int select_lin_begin(Shape s, const double *q_percent, int nq, void *ws, hipStre
 }
 
 // After the producer has filled the linear-digit histogram: scan -> one collecting sweep -> finish on the lists;
-// planes whose list overflowed (a heavy bin, e.g. a constant image) take the generic three sweeps.
-int select_lin_run(const SelectPlan &plan, float *d_planar, Shape s, hipStream_t st, const RestoreSrc *src)
+// planes whose list overflowed (a heavy bin, e.g. a constant image) take the key-digit passes.
+int select_lin_run(const SelectPlan &plan, const float *d_planar, Shape s, hipStream_t st, const RestoreSrc *src)
 {
     const int n = (int)s.npx(), nbc = s.B * 3;
     RankList ranks;
@@ -1240,7 +1225,7 @@ int select_lin_run(const SelectPlan &plan, float *d_planar, Shape s, hipStream_t
     UWIE_REQUIRE(!src || ranks.n <= 4, "select_lin_run: the recomputing sweep handles at most two percentiles");
     LinState *lin = (LinState *)plan.lin;
     UWIE_LAUNCH(k_lin_scan<float>, dim3(nbc), dim3(256), 0, st, lin, plan.ghist, ranks, (float *)plan.os, plan.flags, plan.cap,
-                src ? reinterpret_cast<uint32_t *>(plan.state) : (uint32_t *)nullptr);
+                (SelState<uint32_t> *)plan.state);
     UWIE_LAUNCH_CHECK();
     int blocks = (int)(((long long)n + 131071) / 131072);
     if (blocks * nbc < 1024) blocks = cdiv(1024, nbc);
@@ -1259,45 +1244,27 @@ int select_lin_run(const SelectPlan &plan, float *d_planar, Shape s, hipStream_t
     UWIE_LAUNCH(k_lin_finish<float>, dim3(nbc, ranks.n), dim3(1024), 0, st, lin, (const float *)plan.lists, plan.cap, (float *)plan.os,
                 plan.flags, 0, kLinLists);
     UWIE_LAUNCH_CHECK();
-    // the flagged planes (their kernels return at once for the others).  Recomputed values: the one-launch fallback, no stored
-    // planes (round 4; rounds 1-3 wrote the flagged images out and ran the generic chain: eleven launches and 12 B/px of
-    // workspace).  Stored planes: the generic three-digit sweeps on them.
-    if (src) {
-        uwie_ctx *ctx = current_ctx();
-        UWIE_REQUIRE(ctx != nullptr, "select_lin_run: needs a context");
-        UWIE_LAUNCH(k_rank_fallback, dim3(kFallbackBlocks, nbc), dim3(256), 0, st, *src, n, ranks, plan.flags, plan.ghist,
-                    reinterpret_cast<uint32_t *>(plan.state), (float *)plan.os, ctx->d_status);
-        UWIE_LAUNCH_CHECK();
-        return UWIE_OK;
-    }
-    UWIE_LAUNCH(k_sel_init<uint32_t>, dim3(cdiv(nbc, 64)), dim3(64), 0, st, (SelState<uint32_t> *)plan.state, nbc, ranks);
-    UWIE_LAUNCH_CHECK();
-    UWIE_HIP_CHECK(hipMemsetAsync(plan.ghist, 0, sizeof(uint32_t) * (size_t)nbc * kMaxRanks * kBins, st));
-    return run_t<float>(plan, d_planar, 1, s, false, st, plan.flags);
+    // the flagged planes: the key-digit passes over their recomputed or stored values (they return at once for the others)
+    if (src) return sel_passes(plan, RestoredVals<float>{*src, n}, n, nbc, pass_blocks(n, nbc, true), false, plan.flags, st);
+    const StoredVals<float> vals{d_planar, (size_t)n * 3, (size_t)n, 1};
+    return sel_passes(plan, vals, n, nbc, pass_blocks(n, nbc, false), false, plan.flags, st);
 }
 
-// After launch_restore_rank: scan -> finish on the window lists; flagged planes take the fallback above.
-int select_rank_run(const SelectPlan &plan, float *d_planar, Shape s, hipStream_t st, const RestoreSrc &src)
+// After launch_restore_rank: scan -> finish on the window lists; flagged planes take the key-digit passes.
+int select_rank_run(const SelectPlan &plan, Shape s, hipStream_t st, const RestoreSrc &src)
 {
-    const int nbc = s.B * 3;
+    const int n = (int)s.npx(), nbc = s.B * 3;
     RankList ranks;
     ranks.n = 2 * plan.nq;
     for (int j = 0; j < ranks.n; ++j) ranks.r[j] = plan.ranks[j];
     LinState *lin = (LinState *)plan.lin;
     UWIE_LAUNCH(k_rank_scan, dim3(cdiv(nbc, 64)), dim3(64), 0, st, lin, ranks, (float *)plan.os, plan.flags, kRankCapMul * plan.cap, nbc,
-                reinterpret_cast<uint32_t *>(plan.state));
+                (SelState<uint32_t> *)plan.state);
     UWIE_LAUNCH_CHECK();
     UWIE_LAUNCH(k_lin_finish<float>, dim3(nbc, ranks.n), dim3(1024), 0, st, lin, (const float *)plan.lists, kRankCapMul * plan.cap,
                 (float *)plan.os, plan.flags, 1, kLinLists / kRankCapMul);
     UWIE_LAUNCH_CHECK();
-    (void)d_planar;  // (no stored planes on this route)
-    uwie_ctx *ctx = current_ctx();
-    UWIE_REQUIRE(ctx != nullptr && ranks.n <= 4, "select_rank_run: needs a context and at most two percentiles");
-    // the barrier counters: one word per plane in the selection state's memory, cleared by k_rank_scan
-    UWIE_LAUNCH(k_rank_fallback, dim3(kFallbackBlocks, nbc), dim3(256), 0, st, src, (int)s.npx(), ranks, plan.flags, plan.ghist,
-                reinterpret_cast<uint32_t *>(plan.state), (float *)plan.os, ctx->d_status);
-    UWIE_LAUNCH_CHECK();
-    return UWIE_OK;
+    return sel_passes(plan, RestoredVals<float>{src, n}, n, nbc, pass_blocks(n, nbc, true), false, plan.flags, st);
 }
 
 // float64 planes (ES surface): the same selection without the prediction; the lists hold doubles
@@ -1345,7 +1312,7 @@ int select_lin_begin64(Shape s, const double *q_percent, int nq, void *ws, hipSt
     return UWIE_OK;
 }
 
-int select_lin_run64(const SelectPlan &plan, double *d_planar, Shape s, hipStream_t st, const RestoreSrc *src)
+int select_lin_run64(const SelectPlan &plan, const double *d_planar, Shape s, hipStream_t st, const RestoreSrc *src)
 {
     const int n = (int)s.npx(), nbc = s.B * 3;
     RankList ranks;
@@ -1355,7 +1322,7 @@ int select_lin_run64(const SelectPlan &plan, double *d_planar, Shape s, hipStrea
     LinState *lin = (LinState *)plan.lin;
     double *lists = reinterpret_cast<double *>(plan.lists);
     UWIE_LAUNCH(k_lin_scan<double>, dim3(nbc), dim3(256), 0, st, lin, plan.ghist, ranks, (double *)plan.os, plan.flags, plan.cap,
-                (uint32_t *)nullptr);
+                (SelState<uint64_t> *)plan.state);
     UWIE_LAUNCH_CHECK();
     int blocks = (int)(((long long)n + 131071) / 131072);
     if (blocks * nbc < 1024) blocks = cdiv(1024, nbc);
@@ -1372,16 +1339,10 @@ int select_lin_run64(const SelectPlan &plan, double *d_planar, Shape s, hipStrea
     UWIE_LAUNCH(k_lin_finish<double>, dim3(nbc, ranks.n), dim3(1024), 0, st, lin, (const double *)lists, plan.cap, (double *)plan.os,
                 plan.flags, 0, kLinLists);
     UWIE_LAUNCH_CHECK();
-    // generic path for the flagged planes (its kernels return at once for the others); without stored planes the
-    // flagged images are written out first
-    if (src) {
-        const int rc = launch_recover64_planar_hist(src->in, src->A, src->t, s, d_planar, nullptr, st, true, plan.flags);
-        if (rc != UWIE_OK) return rc;
-    }
-    UWIE_LAUNCH(k_sel_init<uint64_t>, dim3(cdiv(nbc, 64)), dim3(64), 0, st, (SelState<uint64_t> *)plan.state, nbc, ranks);
-    UWIE_LAUNCH_CHECK();
-    UWIE_HIP_CHECK(hipMemsetAsync(plan.ghist, 0, sizeof(uint32_t) * (size_t)nbc * kMaxRanks * kBins, st));
-    return run_t<double>(plan, d_planar, 1, s, false, st, plan.flags);
+    // the flagged planes: the key-digit passes over their recomputed or stored values (they return at once for the others)
+    if (src) return sel_passes(plan, RestoredVals<double>{*src, n}, n, nbc, pass_blocks(n, nbc, true), false, plan.flags, st);
+    const StoredVals<double> vals{d_planar, (size_t)n * 3, (size_t)n, 1};
+    return sel_passes(plan, vals, n, nbc, pass_blocks(n, nbc, false), false, plan.flags, st);
 }
 
 size_t select_ws_bytes(Shape s)
