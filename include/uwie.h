@@ -202,6 +202,16 @@ int uwie_enhance_u8(uwie_ctx *ctx, const uint8_t *d_in, uint8_t *d_out_u8, float
 int uwie_enhance_u8_f64(uwie_ctx *ctx, const uint8_t *d_in, uint8_t *d_out_u8, double *d_out_f64, int batch, int H, int W,
                         const uwie_params *p, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* Read-only: the percentiles the last uwie_enhance_u8 / uwie_enhance_u8_f64 call on this workspace (same batch, H, W, p)
+ * stretched with, widened to double, into d_out: [batch][3][2] (L_low, L_high) for SIX strategies 1-2 and the DICT
+ * dehazing strategies, [batch][3][4] (lo1, hi1, lo2, hi2: the contrast stretch's and white balance's) for SIX strategy 3.
+ * The buffers are found by the enhance call's own carving, sub-batch slices of tuning `streams` included, for the
+ * context's CURRENT tuning: call it under the tuning of the enhance call.  The context remembers whether its last enhance
+ * call was uwie_enhance_u8_f64, which never splits the batch, and reads that call's single layout then.  Dehazing
+ * strategies only. */
+int uwie_enhance_percentiles(uwie_ctx *ctx, const void *d_workspace, size_t workspace_bytes, int batch, int H, int W,
+                             const uwie_params *p, double *d_out, void *stream);
+
 /* The same strategies on GENERAL float images: the reference's functions take "float HxWx3 in [0, 1]" (S6:230-285,
  * ES:477-508) and its own harnesses feed np.random.rand (ES:516, example_usage.py:27,44,112).  uwie_enhance_u8 starts from
  * the u8 frame a float image was made of (the fast path: every kernel exploits that a pixel value is a function of its
@@ -432,6 +442,10 @@ int uwie_restore(uwie_ctx *ctx, const uint8_t *d_in, const int32_t *d_kind, cons
  * S6:196-197,216-217): d_out [batch][3][nq] float32.  q in percent. */
 int uwie_percentiles_f32(uwie_ctx *ctx, const float *d_img, int batch, int H, int W, const double *q_percent, int nq,
                          float *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* The same on float64 images [batch][H][W][3] (NumPy's float64 arithmetic, ES:265-266): d_out [batch][3][nq] float64. */
+int uwie_percentiles_f64(uwie_ctx *ctx, const double *d_img, int batch, int H, int W, const double *q_percent, int nq,
+                         double *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* enhance_contrast / white_balance (S6:191-199, 211-219): clip((x-lo)/(hi-lo+1e-6),0,1). */
 int uwie_stretch_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, double lo_percent,

@@ -31,6 +31,9 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
         assert hasattr(lib, name), f"{name} declared in include/uwie.h but not exported by libuwie.so"
         assert name in _lib.SIGNATURES, f"{name} has no ctypes signature in _lib.py"
     assert sorted(_lib.SIGNATURES) == names
+    # the selection accessors (tests/test_gpu_select.py reaches every route through them)
+    for name in ("uwie_percentiles_f32", "uwie_percentiles_f64", "uwie_enhance_percentiles"):
+        assert name in names
 
 
 def test_params_struct_matches_header_and_reference_defaults(lib):
@@ -74,6 +77,8 @@ def test_null_arguments_are_rejected_without_a_gpu(lib):
     assert lib.uwie_enhance_u8(None, None, None, None, 1, 8, 8, None, None, 0, None) == -1
     assert lib.uwie_params_init(None, 0, 1) == -1
     assert lib.uwie_rgb2lab_u8(None, None, None, 0, None) == -1
+    assert lib.uwie_percentiles_f64(None, None, 1, 8, 8, None, 1, None, None, 0, None) == -1
+    assert lib.uwie_enhance_percentiles(None, None, 0, 1, 8, 8, None, None, None) == -1
 
 
 def test_no_cpu_fallback_without_a_device():

@@ -81,6 +81,7 @@ SIGNATURES = {
     "uwie_guided_plan": [_I, _I, _I, _I, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
     "uwie_enhance_u8": [_VP, _VP, _VP, _VP, _I, _I, _I, _PP, _VP, _SZ, _VP],
     "uwie_enhance_u8_f64": [_VP, _VP, _VP, _VP, _I, _I, _I, _PP, _VP, _SZ, _VP],
+    "uwie_enhance_percentiles": [_VP, _VP, _SZ, _I, _I, _I, _PP, _VP, _VP],
     "uwie_enhance_all_u8": [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _SZ, _VP],
     "uwie_workspace_bytes_select": [_I, _I, _I, _VP, _I, _I],
     "uwie_select_best_u8": [_VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP],
@@ -106,6 +107,7 @@ SIGNATURES = {
     "uwie_guided_filter": [_VP, _VP, _VP, _I, _I, _I, _I, _D, _I, _VP, _VP, _SZ, _VP],
     "uwie_restore": [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP],
     "uwie_percentiles_f32": [_VP, _VP, _I, _I, _I, ctypes.POINTER(_D), _I, _VP, _VP, _SZ, _VP],
+    "uwie_percentiles_f64": [_VP, _VP, _I, _I, _I, ctypes.POINTER(_D), _I, _VP, _VP, _SZ, _VP],
     "uwie_stretch_f32": [_VP, _VP, _VP, _I, _I, _I, _D, _D, _VP, _SZ, _VP],
     "uwie_gamma_f32": [_VP, _VP, _VP, _SZ, _D, _I, _VP],
     "uwie_clahe_f32": [_VP, _VP, _VP, _I, _I, _I, _D, _I, _I, _VP, _SZ, _VP],

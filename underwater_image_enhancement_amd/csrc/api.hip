@@ -794,6 +794,45 @@ size_t uwie_workspace_bytes_all(int batch, int H, int W, const uwie_params *p6)
     return c.total();
 }
 
+// The buffers of a uwie_enhance_u8 call on this workspace: the whole batch in one Pipe (nsplit = 1), or -- tuning `streams`,
+// may_split -- up to four sub-batches, each with its own slice.  uwie_enhance_percentiles finds the last call's percentiles
+// by the same carving, so the two cannot disagree.  total: the single layout's bytes (what the call requires of the workspace).
+struct EnhanceLayout {
+    int nsplit;
+    int cnt[4], start[4];
+    Pipe P[4];
+    size_t total;
+};
+
+static EnhanceLayout carve_enhance(void *d_workspace, size_t workspace_bytes, Shape s, const uwie_params *p, bool may_split)
+{
+    EnhanceLayout L{};
+    Carver c(d_workspace);
+    L.P[0] = carve_pipe(c, s, p);
+    L.total = c.total();
+    L.nsplit = 1;
+    L.cnt[0] = s.B;
+    L.start[0] = 0;
+    const int nsplit = may_split ? enhance_split(s.B) : 1;
+    if (nsplit >= 2 && s.B >= nsplit) {
+        EnhanceLayout S = L;
+        size_t off = 0;
+        bool fits_ws = true;
+        for (int i = 0, b0 = 0; i < nsplit; ++i) {
+            S.cnt[i] = s.B / nsplit + (i < s.B % nsplit ? 1 : 0);
+            S.start[i] = b0;
+            b0 += S.cnt[i];
+            Carver ci(static_cast<char *>(d_workspace) + off);
+            S.P[i] = carve_pipe(ci, Shape{S.cnt[i], s.H, s.W}, p);
+            if (off + ci.total() > workspace_bytes) fits_ws = false;  // (a caller that sized for another parameter set)
+            off = (off + ci.total() + 255) & ~(size_t)255;
+        }
+        S.nsplit = nsplit;
+        if (fits_ws) L = S;
+    }
+    return L;
+}
+
 int uwie_enhance_u8(uwie_ctx *ctx, const uint8_t *d_in, uint8_t *d_out_u8, float *d_out_f32, int batch, int H, int W,
                     const uwie_params *p, void *d_workspace, size_t workspace_bytes, void *stream)
 {
@@ -802,55 +841,43 @@ int uwie_enhance_u8(uwie_ctx *ctx, const uint8_t *d_in, uint8_t *d_out_u8, float
     UWIE_CHECK_SHAPE(batch, H, W);
     UWIE_TRY(check_params(p));
     const Shape s{batch, H, W};
-    Carver c(d_workspace);
-    Pipe P = carve_pipe(c, s, p);
-    UWIE_CHECK_WS(c.total());
+    const EnhanceLayout L = carve_enhance(d_workspace, workspace_bytes, s, p, true);
+    UWIE_CHECK_WS(L.total);
+    ctx->last_enhance_f64 = false;
+    const Pipe &P = L.P[0];
     hipStream_t st = (hipStream_t)stream;
     // Frames are independent, so the batch runs as sub-batches on separate streams: while one sits in an issue-bound
     // stage (guided filter) another can be in a memory-bound one.  The caller's stream waits for all of them.
-    const int nsplit = enhance_split(batch);
-    if (nsplit >= 2 && batch >= nsplit) {
-        int cnt[4], start[4];
-        Pipe Ps[4];
-        size_t off = 0;
-        bool fits_ws = true;
-        for (int i = 0, b0 = 0; i < nsplit; ++i) {
-            cnt[i] = batch / nsplit + (i < batch % nsplit ? 1 : 0);
-            start[i] = b0;
-            b0 += cnt[i];
-            Carver ci(static_cast<char *>(d_workspace) + off);
-            Ps[i] = carve_pipe(ci, Shape{cnt[i], H, W}, p);
-            if (off + ci.total() > workspace_bytes) fits_ws = false;  // (a caller that sized for another parameter set)
-            off = (off + ci.total() + 255) & ~(size_t)255;
-        }
-        if (fits_ws) {
-            if (!ctx->aux_ready) {
-                for (int i = 0; i < 4; ++i) {
-                    UWIE_HIP_CHECK(hipStreamCreateWithFlags(&ctx->aux[i], hipStreamNonBlocking));
-                    UWIE_HIP_CHECK(hipEventCreateWithFlags(&ctx->join[i], hipEventDisableTiming));
-                }
-                UWIE_HIP_CHECK(hipEventCreateWithFlags(&ctx->fork, hipEventDisableTiming));
-                ctx->aux_ready = true;
+    const int nsplit = L.nsplit;
+    if (nsplit >= 2) {
+        const int *cnt = L.cnt, *start = L.start;
+        const Pipe *Ps = L.P;
+        if (!ctx->aux_ready) {
+            for (int i = 0; i < 4; ++i) {
+                UWIE_HIP_CHECK(hipStreamCreateWithFlags(&ctx->aux[i], hipStreamNonBlocking));
+                UWIE_HIP_CHECK(hipEventCreateWithFlags(&ctx->join[i], hipEventDisableTiming));
             }
-            UWIE_HIP_CHECK(hipEventRecord(ctx->fork, st));
-            const size_t px = (size_t)H * W;
-            for (int i = 0; i < nsplit; ++i) {
-                UWIE_HIP_CHECK(hipStreamWaitEvent(ctx->aux[i], ctx->fork, 0));
-                const size_t b0 = (size_t)start[i];
-                const Shape si{cnt[i], H, W};
-                const uint8_t *in_i = d_in + b0 * px * 3;
-                uint8_t *o8 = d_out_u8 ? d_out_u8 + b0 * px * 3 : nullptr;
-                float *of = d_out_f32 ? d_out_f32 + b0 * px * 3 : nullptr;
-                int rc;
-                if (p->surface == UWIE_SURFACE_SIX) rc = run_six(ctx, in_i, si, p, Ps[i], o8, of, ctx->aux[i]);
-                else if (!dehazes(p)) rc = launch_code_strategy(ctx, in_i, nullptr, si, p, o8, of, Ps[i].scratch, ctx->aux[i]);
-                else rc = run_dict_dehaze(ctx, in_i, si, p, Ps[i], o8, of, ctx->aux[i]);
-                if (rc != UWIE_OK) return rc;
-                UWIE_HIP_CHECK(hipEventRecord(ctx->join[i], ctx->aux[i]));
-            }
-            for (int i = 0; i < nsplit; ++i) UWIE_HIP_CHECK(hipStreamWaitEvent(st, ctx->join[i], 0));
-            return UWIE_OK;
+            UWIE_HIP_CHECK(hipEventCreateWithFlags(&ctx->fork, hipEventDisableTiming));
+            ctx->aux_ready = true;
         }
+        UWIE_HIP_CHECK(hipEventRecord(ctx->fork, st));
+        const size_t px = (size_t)H * W;
+        for (int i = 0; i < nsplit; ++i) {
+            UWIE_HIP_CHECK(hipStreamWaitEvent(ctx->aux[i], ctx->fork, 0));
+            const size_t b0 = (size_t)start[i];
+            const Shape si{cnt[i], H, W};
+            const uint8_t *in_i = d_in + b0 * px * 3;
+            uint8_t *o8 = d_out_u8 ? d_out_u8 + b0 * px * 3 : nullptr;
+            float *of = d_out_f32 ? d_out_f32 + b0 * px * 3 : nullptr;
+            int rc;
+            if (p->surface == UWIE_SURFACE_SIX) rc = run_six(ctx, in_i, si, p, Ps[i], o8, of, ctx->aux[i]);
+            else if (!dehazes(p)) rc = launch_code_strategy(ctx, in_i, nullptr, si, p, o8, of, Ps[i].scratch, ctx->aux[i]);
+            else rc = run_dict_dehaze(ctx, in_i, si, p, Ps[i], o8, of, ctx->aux[i]);
+            if (rc != UWIE_OK) return rc;
+            UWIE_HIP_CHECK(hipEventRecord(ctx->join[i], ctx->aux[i]));
+        }
+        for (int i = 0; i < nsplit; ++i) UWIE_HIP_CHECK(hipStreamWaitEvent(st, ctx->join[i], 0));
+        return UWIE_OK;
     }
     if (p->surface == UWIE_SURFACE_SIX) {
         return run_six(ctx, d_in, s, p, P, d_out_u8, d_out_f32, st);
@@ -871,6 +898,7 @@ int uwie_enhance_u8_f64(uwie_ctx *ctx, const uint8_t *d_in, uint8_t *d_out_u8, d
     Carver c(d_workspace);
     Pipe P = carve_pipe(c, s, p);
     UWIE_CHECK_WS(c.total());
+    ctx->last_enhance_f64 = true;  // (the whole batch in one layout: uwie_enhance_percentiles reads that one)
     hipStream_t st = (hipStream_t)stream;
     if (!dehazes(p)) return launch_code_strategy(ctx, d_in, nullptr, s, p, d_out_u8, nullptr, P.scratch, st, d_out_f64);
     return run_dict_dehaze(ctx, d_in, s, p, P, d_out_u8, nullptr, st, d_out_f64);
@@ -1332,6 +1360,40 @@ int uwie_percentiles_f32(uwie_ctx *ctx, const float *d_img, int batch, int H, in
     const Shape s{batch, H, W};
     UWIE_CHECK_WS(select_ws_bytes(s));
     return launch_percentiles_f32(d_img, 0, s, q_percent, nq, d_out, d_workspace, (hipStream_t)stream);
+}
+
+int uwie_percentiles_f64(uwie_ctx *ctx, const double *d_img, int batch, int H, int W, const double *q_percent, int nq,
+                         double *d_out, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE(ctx && d_img && q_percent && d_out, "percentiles_f64: NULL pointer");
+    UWIE_SCOPE(ctx);
+    UWIE_CHECK_SHAPE(batch, H, W);
+    const Shape s{batch, H, W};
+    UWIE_CHECK_WS(select_ws_bytes(s));
+    return launch_percentiles_f64(d_img, s, q_percent, nq, d_out, d_workspace, (hipStream_t)stream);
+}
+
+int uwie_enhance_percentiles(uwie_ctx *ctx, const void *d_workspace, size_t workspace_bytes, int batch, int H, int W,
+                             const uwie_params *p, double *d_out, void *stream)
+{
+    UWIE_REQUIRE(ctx && d_workspace && d_out, "enhance_percentiles: NULL context, workspace or output pointer");
+    UWIE_SCOPE(ctx);
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_TRY(check_params(p));
+    UWIE_REQUIRE(dehazes(p), "enhance_percentiles: only the dehazing strategies select percentiles in the workspace");
+    const Shape s{batch, H, W};
+    const EnhanceLayout L = carve_enhance(const_cast<void *>(d_workspace), workspace_bytes, s, p, !ctx->last_enhance_f64);
+    UWIE_CHECK_WS(L.total);
+    hipStream_t st = (hipStream_t)stream;
+    const bool dict = p->surface == UWIE_SURFACE_DICT;
+    const size_t per = (!dict && p->strategy == 3) ? 4 : 2;  // values per (image, channel)
+    for (int i = 0; i < L.nsplit; ++i) {
+        const size_t n = (size_t)L.cnt[i] * 3 * per;
+        double *o = d_out + (size_t)L.start[i] * 3 * per;
+        if (dict) UWIE_HIP_CHECK(hipMemcpyAsync(o, L.P[i].pct64, n * sizeof(double), hipMemcpyDeviceToDevice, st));
+        else UWIE_TRY(launch_widen_f32(L.P[i].pct, o, n, st));
+    }
+    return UWIE_OK;
 }
 
 int uwie_stretch_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, double lo_percent,

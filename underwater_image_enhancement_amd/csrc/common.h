@@ -126,6 +126,8 @@ struct uwie_ctx {
     hipStream_t aux[4];
     hipEvent_t fork, join[4];
     bool aux_ready;
+    // the last enhance call on this context was uwie_enhance_u8_f64, which never splits the batch (uwie_enhance_percentiles)
+    bool last_enhance_f64 = false;
 };
 
 namespace uwie {
@@ -264,6 +266,10 @@ size_t select_ws_bytes(Shape s);
 // d_vals: float32 image, HWC ([B][H][W][3], planar = 0) or planar ([B][3][H][W], planar = 1); d_out [B][3][nq]
 int launch_percentiles_f32(const float *d_vals, int planar, Shape s, const double *q_percent, int nq, float *d_out,
                            void *ws, hipStream_t st);
+// the same on a float64 image ([B][H][W][3]); d_out [B][3][nq]
+int launch_percentiles_f64(const double *d_vals, Shape s, const double *q_percent, int nq, double *d_out, void *ws, hipStream_t st);
+// d_out[i] = (double)d_in[i], i < n
+int launch_widen_f32(const float *d_in, double *d_out, size_t n, hipStream_t st);
 
 // selection in pieces, for producers that fuse the first histogram sweep (digit = f32_key(v) >> 21, 2048 bins,
 // accumulated into plan.ghist[(b*3 + c) * kSelGroupStride + digit])

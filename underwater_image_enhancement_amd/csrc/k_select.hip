@@ -1440,4 +1440,30 @@ int launch_percentiles_f32(const float *d_vals, int planar, Shape s, const doubl
     return select_lerp(plan, s, d_out, st);
 }
 
+int launch_percentiles_f64(const double *d_vals, Shape s, const double *q_percent, int nq, double *d_out, void *ws, hipStream_t st)
+{
+    SelectPlan plan;
+    int rc = select_begin64(s, q_percent, nq, ws, st, &plan);
+    if (rc != UWIE_OK) return rc;
+    rc = select_run64(plan, d_vals, 0, s, false, st);
+    if (rc != UWIE_OK) return rc;
+    return select_lerp64(plan, s, d_out, st);
+}
+
+namespace {
+__global__ void k_widen_f32(const float *__restrict__ in, double *__restrict__ out, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = (double)in[i];
+}
+}  // namespace
+
+int launch_widen_f32(const float *d_in, double *d_out, size_t n, hipStream_t st)
+{
+    if (n == 0) return UWIE_OK;
+    UWIE_LAUNCH(k_widen_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_in, d_out, n);
+    UWIE_LAUNCH_CHECK();
+    return UWIE_OK;
+}
+
 }  // namespace uwie

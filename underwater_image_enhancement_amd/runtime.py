@@ -170,6 +170,28 @@ class Device:
                                            _ptr(ws), ws.numel(), self.stream()))
         return out, outf
 
+    def enhance_percentiles(self, B, H, W, p: UwieParams):
+        """The percentiles the last enhance_u8 / enhance_u8_f64 call of this Device (same B, H, W, p, and the same tuning:
+        call it inside that call's ``tuning`` scope) stretched with: float64 [B,3,2] (L_low, L_high), or [B,3,4] (lo1, hi1,
+        lo2, hi2) for six_stadigy strategy 3.  Reads the Device's kept workspace (uwie_enhance_percentiles); the context
+        knows whether its last enhance call was uwie_enhance_u8_f64, which never splits the batch."""
+        ws = self.workspace_for(B, H, W, p)
+        k = 4 if p.surface == _lib.SURFACE_SIX and p.strategy == 3 else 2
+        out = self.empty((B, 3, k), torch.float64)
+        check(self.lib.uwie_enhance_percentiles(self._ctx, _ptr(ws), ws.numel(), B, H, W, ctypes.byref(p), _ptr(out),
+                                                self.stream()))
+        return out
+
+    def enhance_u8_with_percentiles(self, frames, p: UwieParams, want_float: bool = False):
+        """enhance_u8, and the percentiles it used: (uint8 [B,H,W,3], float32 or None, float64 [B,3,2 or 4])."""
+        out, outf = self.enhance_u8(frames, p, want_float)
+        return out, outf, self.enhance_percentiles(*self._bhw(frames), p)
+
+    def enhance_u8_f64_with_percentiles(self, frames, p: UwieParams):
+        """enhance_u8_f64, and the percentiles it used: (uint8 [B,H,W,3], float64 [B,H,W,3], float64 [B,3,2])."""
+        out, outf = self.enhance_u8_f64(frames, p)
+        return out, outf, self.enhance_percentiles(*self._bhw(frames), p)
+
     def enhance_float(self, img, p: UwieParams, want: str = "native"):
         """General (not u8-derived) float images [B,H,W,3], float32 (either surface) or float64 (dict surface): returns
         (uint8 [B,H,W,3], float image): float32 for the six_stadigy surface, float64 for the dict surface."""
@@ -511,6 +533,16 @@ class Device:
         ws = self.workspace_for(B, H, W)
         out = self.empty((B, 3, len(q_percent)), torch.float32)
         check(self.lib.uwie_percentiles_f32(self._ctx, _ptr(img), B, H, W, q, len(q_percent), _ptr(out), _ptr(ws),
+                                            ws.numel(), self.stream()))
+        return out
+
+    def percentiles_f64(self, img, q_percent):
+        B, H, W = self._bhw(img)
+        assert img.dtype == torch.float64
+        q = (ctypes.c_double * len(q_percent))(*[float(v) for v in q_percent])
+        ws = self.workspace_for(B, H, W)
+        out = self.empty((B, 3, len(q_percent)), torch.float64)
+        check(self.lib.uwie_percentiles_f64(self._ctx, _ptr(img), B, H, W, q, len(q_percent), _ptr(out), _ptr(ws),
                                             ws.numel(), self.stream()))
         return out
 
