@@ -137,6 +137,10 @@ void uwie_destroy(uwie_ctx *ctx);
 /*   UWIE_STATUS_RESIZE_DESC  uwie_resize_rgb_u8 (k_resize.hip): a frame descriptor has a NULL pointer or a side outside
  *                            [1, UWIE_RESIZE_MAX_SRC]: nothing of that frame was read or written. */
 #define UWIE_STATUS_RESIZE_DESC 32u
+/*   UWIE_STATUS_CLASSIFY_NAN  uwie_classify_f64 / uwie_predict_strategy_u8 (k_classify.hip): a row holds NaN after scaling and
+ *                             the model is GB or SVC (scikit-learn raises "Input X contains NaN"): that row's label is -1,
+ *                             its proba NaN.  (Random forests route NaN and never set it.) */
+#define UWIE_STATUS_CLASSIFY_NAN 64u
 int uwie_device_status(uwie_ctx *ctx, void *stream, uint32_t *bits);
 
 /* Per-kernel timing for benchmarks (no reference counterpart; the reference only has a per-image wall clock,
@@ -391,6 +395,83 @@ size_t uwie_workspace_bytes_select(int batch, int H, int W, const uwie_params *p
 int uwie_select_best_u8(uwie_ctx *ctx, const uint8_t *d_in, int batch, int H, int W, const uwie_params *ps, int n,
                         const double *weights8, uint8_t *d_best_u8, int32_t *d_best, double *d_scores, uint8_t *d_all_u8,
                         void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------- strategy classifier: main.py:398-433 (predict) ---------------- */
+
+/*
+ * A fitted scikit-learn model of one of the three kinds train_classifier fits (main.py:271-275), with its StandardScaler,
+ * as flat HOST arrays (underwater_image_enhancement_amd/classifier.py exports them).  F = n_features, C = n_classes,
+ * T = n_trees, N = n_nodes, S = n_sv, P = C * (C - 1) / 2.
+ *   all      mean[F], scale[F]: StandardScaler.mean_ / scale_ (zeros / ones without centring / scaling)
+ *   RF, GB   tree_offset[T + 1] (root of tree t at node tree_offset[t]; tree_offset[T] = N), per node (tree-local child
+ *            indices, -1 for both at a leaf): left[N], right[N], feature[N], threshold[N], missing_left[N];
+ *            value: RF [N][C] (the tree_.value class fractions), GB [N] (the regression leaf value)
+ *   GB       T = n_stages * K trees, stage-major, K = 1 for two classes and C otherwise; learning_rate; init[K] (the
+ *            estimator's own _raw_predict_init)
+ *   SVC      sv[S][F] (support_vectors_), dual_coef[C - 1][S] (_dual_coef_), intercept[P] (_intercept_: libsvm's -rho),
+ *            n_support[C], prob_a[P], prob_b[P] (_probA / _probB), gamma (_gamma); RBF kernel only
+ */
+#define UWIE_MODEL_RF 0
+#define UWIE_MODEL_GB 1
+#define UWIE_MODEL_SVC 2
+typedef struct uwie_model_desc {
+    int32_t kind, n_features, n_classes, n_trees, n_nodes, n_sv;
+    const double *mean, *scale;
+    const int32_t *tree_offset, *left, *right, *feature;
+    const double *threshold;
+    const uint8_t *missing_left;
+    const double *value;
+    double learning_rate;
+    const double *init;
+    const double *sv, *dual_coef, *intercept;
+    const int32_t *n_support;
+    const double *prob_a, *prob_b;
+    double gamma;
+} uwie_model_desc;
+typedef struct uwie_model uwie_model;
+
+/* Host only (no context, no device).  UWIE_E_INVALID for: an unknown kind; n_features outside 1..1024; n_classes outside
+ * 2..32; more than 4096 trees or 2^22 nodes; tree offsets that are not increasing from 0 to n_nodes; an internal node whose
+ * feature is >= n_features or whose children are not strictly greater than itself and less than its tree's node count
+ * (scikit-learn's builders always satisfy this: every walk ends within node_count steps); more than 65536 support vectors
+ * or n_support not summing to n_sv; a NULL array; a non-finite mean, scale (or a zero one), threshold, value, init,
+ * learning rate, gamma or coefficient. */
+int uwie_model_check(const uwie_model_desc *desc);
+/* uwie_model_check, then one upload of the model into a device blob of ctx's device (synchronous). */
+int uwie_model_create(uwie_ctx *ctx, const uwie_model_desc *desc, uwie_model **out_model);
+void uwie_model_destroy(uwie_model *model);
+int uwie_model_info(const uwie_model *model, int *kind, int *n_classes, int *n_features);
+
+/*
+ * scaler.transform + classifier.predict / predict_proba (main.py:423-428) per row.  d_rows: [batch][n_features] float64,
+ * unscaled; d_label: [batch] int32, the index into classes_; d_proba: [batch][n_classes] float64.  n_features must be the
+ * model's.  A row's result depends on that row alone (no atomics on results, no waits between workgroups): the same bits at
+ * every batch size and on every run.
+ *   scaling  (x - mean) / scale in float64, each operation rounded once (StandardScaler.transform).
+ *   trees    the scaled row cast to float32 (scikit-learn's DTYPE); at a node, go left iff (double)x <= threshold, or, for
+ *            NaN, iff missing_left.
+ *   RF       proba = ((0 + v_0) + v_1 + ...) / T over the leaves' class fractions in tree order (forest.predict_proba with
+ *            n_jobs=None); label = first maximum.  Bit for bit.  NaN rows are routed (the forest accepts them).
+ *   GB       raw[k] = init[k], then raw[k] += learning_rate * value[leaf] stage by stage (predict_stages): bit for bit;
+ *            label = first argmax (raw >= 0 for two classes); proba = softmax (exp(raw - max) / sequential sum), or expit
+ *            1 / (1 + exp(-raw)) giving [1 - p, p]: within 1e-15 (the device's exp).
+ *   SVC      libsvm's svm_predict_values / svm_predict_probability: kernel exp(-gamma * |x - sv|^2) with the squared distance
+ *            summed serially over features (libsvm: a BLAS ddot, order unknown), decision values within 1e-12; label = the
+ *            one-vs-one vote (ties to the lower class, NOT argmax of proba); Platt sigmoid clamped to [1e-7, 1 - 1e-7] and
+ *            multiclass_probability (Wu, Lin and Weng's method 2): proba within 1e-9.
+ * A GB / SVC row holding NaN after scaling (scikit-learn: ValueError "Input X contains NaN") gets label -1, NaN proba, and
+ * sets UWIE_STATUS_CLASSIFY_NAN.  No workspace.
+ */
+int uwie_classify_f64(uwie_ctx *ctx, const uwie_model *model, const double *d_rows, int batch, int n_features, int32_t *d_label,
+                      double *d_proba, void *stream);
+/* uwie_feature_extractor_u8 (gray_shift, d_f32 as there) followed by uwie_classify_f64 on the device, no host round trip:
+ * main.py:419-428 for a batch.  d_rows (optional): [batch][79] receives the feature rows.  A frame size whose row has 74
+ * values (H or W odd and > 1) against a 79-feature model is UWIE_E_INVALID before any launch.
+ * Workspace: uwie_workspace_bytes_predict(batch, H, W). */
+size_t uwie_workspace_bytes_predict(int batch, int H, int W);
+int uwie_predict_strategy_u8(uwie_ctx *ctx, const uwie_model *model, const uint8_t *d_u8, const float *d_f32, int batch, int H,
+                             int W, int gray_shift, int32_t *d_label, double *d_proba, double *d_rows, void *d_workspace,
+                             size_t workspace_bytes, void *stream);
 
 /* ---------------- per-stage entry points (parity tests, composition) ---------------- */
 

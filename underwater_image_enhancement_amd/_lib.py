@@ -11,6 +11,7 @@ CSRC = os.path.join(_HERE, "csrc")
 
 SURFACE_SIX, SURFACE_DICT = 0, 1
 STATUS_DIFF_RANK = 16  # include/uwie.h UWIE_STATUS_DIFF_RANK
+STATUS_CLASSIFY_NAN = 64  # include/uwie.h UWIE_STATUS_CLASSIFY_NAN
 FLIP_LR, FLIP_UD = 1, 2  # include/uwie.h UWIE_FLIP_LR, UWIE_FLIP_UD
 RESIZE_MAX_SIDE, RESIZE_MAX_SRC = 4096, 32768  # include/uwie.h UWIE_RESIZE_MAX_SIDE, UWIE_RESIZE_MAX_SRC
 INTER_F64, INTER_FX32, INTER_F32T = 0, 1, 2  # uwie_params.inter_dtype
@@ -54,9 +55,25 @@ class UwieParams(ctypes.Structure):
     ]
 
 
+class UwieModelDesc(ctypes.Structure):
+    """Mirror of ``struct uwie_model_desc`` (include/uwie.h): host arrays of one exported classifier."""
+
+    _fields_ = [("kind", ctypes.c_int32), ("n_features", ctypes.c_int32), ("n_classes", ctypes.c_int32),
+                ("n_trees", ctypes.c_int32), ("n_nodes", ctypes.c_int32), ("n_sv", ctypes.c_int32),
+                ("mean", ctypes.c_void_p), ("scale", ctypes.c_void_p),
+                ("tree_offset", ctypes.c_void_p), ("left", ctypes.c_void_p), ("right", ctypes.c_void_p),
+                ("feature", ctypes.c_void_p), ("threshold", ctypes.c_void_p), ("missing_left", ctypes.c_void_p),
+                ("value", ctypes.c_void_p), ("learning_rate", ctypes.c_double), ("init", ctypes.c_void_p),
+                ("sv", ctypes.c_void_p), ("dual_coef", ctypes.c_void_p), ("intercept", ctypes.c_void_p),
+                ("n_support", ctypes.c_void_p), ("prob_a", ctypes.c_void_p), ("prob_b", ctypes.c_void_p),
+                ("gamma", ctypes.c_double)]
+
+
 # name -> argument types (return type is int unless listed in _RESTYPES)
 _VP, _SZ, _I, _D = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_double
 _PP = ctypes.POINTER(UwieParams)
+_PM = ctypes.POINTER(UwieModelDesc)
+_PI = ctypes.POINTER(_I)
 SIGNATURES = {
     "uwie_last_error": [],
     "uwie_version": [],
@@ -97,6 +114,13 @@ SIGNATURES = {
     "uwie_feature_extractor_count": [_I, _I],
     "uwie_workspace_bytes_feature_extractor": [_I, _I, _I],
     "uwie_feature_extractor_u8": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _SZ, _VP],
+    "uwie_model_check": [_PM],
+    "uwie_model_create": [_VP, _PM, ctypes.POINTER(_VP)],
+    "uwie_model_destroy": [_VP],
+    "uwie_model_info": [_VP, _PI, _PI, _PI],
+    "uwie_classify_f64": [_VP, _VP, _VP, _I, _I, _VP, _VP, _VP],
+    "uwie_workspace_bytes_predict": [_I, _I, _I],
+    "uwie_predict_strategy_u8": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _SZ, _VP],
     "uwie_resize_rgb_u8": [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
     "uwie_quality_scores": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _SZ, _VP],
     "uwie_cast_classify": [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _SZ, _VP],
@@ -130,6 +154,8 @@ _RESTYPES = {
     "uwie_diff_enhance_bwd_workspace_bytes": ctypes.c_size_t,
     "uwie_diff_gated_bwd_workspace_bytes": ctypes.c_size_t,
     "uwie_workspace_bytes_feature_extractor": ctypes.c_size_t,
+    "uwie_workspace_bytes_predict": ctypes.c_size_t,
+    "uwie_model_destroy": None,
 }
 
 _lib = None

@@ -627,7 +627,8 @@ int uwie_device_status(uwie_ctx *ctx, void *stream, uint32_t *bits)
                   : (v & UWIE_STATUS_QTREE_BOUNDS) ? " a quadtree score fell outside its histogram interval (k_airlight.hip, tuning q_hist = 3);"
                   : (v & UWIE_STATUS_FEATURE_COUNTS) ? " a frame's feature histograms do not count every pixel (k_extractor.hip);"
                   : (v & UWIE_STATUS_DIFF_RANK) ? " a gated DifferentiableEnhancement image has no valid sorted position (an IndexError, ValueError or OverflowError in Python);"
-                  : (v & UWIE_STATUS_RESIZE_DESC) ? " a resize frame descriptor has a NULL pointer or a size out of range (k_resize.hip);" : "");
+                  : (v & UWIE_STATUS_RESIZE_DESC) ? " a resize frame descriptor has a NULL pointer or a size out of range (k_resize.hip);"
+                  : (v & UWIE_STATUS_CLASSIFY_NAN) ? " a row holds NaN and the model is GB or SVC (scikit-learn: ValueError, Input X contains NaN);" : "");
         return UWIE_E_DEVICE;
     }
     return UWIE_OK;
@@ -1233,6 +1234,110 @@ int uwie_feature_extractor_u8(uwie_ctx *ctx, const uint8_t *d_u8, const float *d
     const Shape s{batch, H, W};
     UWIE_CHECK_WS(feature_extractor_ws_bytes(s));
     return launch_feature_extractor(ctx, d_u8, d_f32, s, gray_shift, d_features, d_workspace, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------- strategy classifier (k_classify.hip)
+struct uwie_model {
+    int device;
+    ClsModel m;  // device pointers into blob
+    void *blob;
+};
+
+int uwie_model_check(const uwie_model_desc *desc) { return classify_model_check(desc); }
+
+int uwie_model_create(uwie_ctx *ctx, const uwie_model_desc *desc, uwie_model **out_model)
+{
+    UWIE_REQUIRE(ctx && out_model, "model_create: NULL context or out_model");
+    *out_model = nullptr;
+    UWIE_TRY(classify_model_check(desc));
+    UWIE_SCOPE(ctx);
+    const size_t bytes = classify_blob_bytes(desc);
+    char *host = static_cast<char *>(calloc(bytes, 1));
+    UWIE_REQUIRE(host != nullptr, "model_create: host allocation failed");
+    void *blob = nullptr;
+    hipError_t e = hipMalloc(&blob, bytes);
+    ClsModel m{};
+    if (e == hipSuccess) {
+        m = classify_pack(desc, host, blob);
+        e = hipMemcpy(blob, host, bytes, hipMemcpyHostToDevice);
+    }
+    free(host);
+    if (e != hipSuccess) {
+        if (blob) (void)hipFree(blob);
+        set_error("model_create: upload of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+        return UWIE_E_HIP;
+    }
+    *out_model = new uwie_model{ctx->device, m, blob};
+    return UWIE_OK;
+}
+
+void uwie_model_destroy(uwie_model *model)
+{
+    if (!model) return;
+    int prev = -1;
+    const bool switch_dev = hipGetDevice(&prev) == hipSuccess && prev != model->device && hipSetDevice(model->device) == hipSuccess;
+    (void)hipFree(model->blob);
+    if (switch_dev) (void)hipSetDevice(prev);
+    delete model;
+}
+
+int uwie_model_info(const uwie_model *model, int *kind, int *n_classes, int *n_features)
+{
+    UWIE_REQUIRE(model != nullptr, "model_info: NULL model");
+    if (kind) *kind = model->m.kind;
+    if (n_classes) *n_classes = model->m.C;
+    if (n_features) *n_features = model->m.F;
+    return UWIE_OK;
+}
+
+int uwie_classify_f64(uwie_ctx *ctx, const uwie_model *model, const double *d_rows, int batch, int n_features, int32_t *d_label,
+                      double *d_proba, void *stream)
+{
+    UWIE_REQUIRE(ctx && model && d_rows && d_label && d_proba, "classify: NULL pointer");
+    UWIE_REQUIRE(model->device == ctx->device, "classify: the model lives on another device");
+    UWIE_REQUIRE(batch >= 1 && batch <= (1 << 24), "classify: batch must be 1..2^24");
+    if (n_features != model->m.F) {
+        set_error("classify: rows have %d features, the model expects %d", n_features, model->m.F);
+        return UWIE_E_INVALID;
+    }
+    UWIE_SCOPE(ctx);
+    return launch_classify(model->m, d_rows, batch, d_label, d_proba, ctx->d_status, (hipStream_t)stream);
+}
+
+size_t uwie_workspace_bytes_predict(int batch, int H, int W)
+{
+    if (!shape_ok(batch, H, W) || batch > 65535) return 0;
+    const Shape s{batch, H, W};
+    Carver c(nullptr);
+    c.take<double>((size_t)batch * feature_extractor_count(H, W));
+    c.take<char>(feature_extractor_ws_bytes(s));
+    return c.total();
+}
+
+int uwie_predict_strategy_u8(uwie_ctx *ctx, const uwie_model *model, const uint8_t *d_u8, const float *d_f32, int batch, int H,
+                             int W, int gray_shift, int32_t *d_label, double *d_proba, double *d_rows, void *d_workspace,
+                             size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE(ctx && model && d_u8 && d_label && d_proba, "predict: NULL pointer");
+    UWIE_REQUIRE(model->device == ctx->device, "predict: the model lives on another device");
+    UWIE_SCOPE(ctx);
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_REQUIRE(batch <= 65535, "predict: batch must be <= 65535");
+    UWIE_REQUIRE(gray_shift == 14 || gray_shift == 15, "gray_shift must be 14 or 15");
+    const int n = feature_extractor_count(H, W);
+    if (n != model->m.F) {
+        set_error("predict: a %dx%d frame gives %d feature values, the model expects %d", H, W, n, model->m.F);
+        return UWIE_E_INVALID;
+    }
+    const Shape s{batch, H, W};
+    UWIE_CHECK_WS(uwie_workspace_bytes_predict(batch, H, W));
+    Carver c(d_workspace);
+    double *rows = c.take<double>((size_t)batch * n);
+    void *fx_ws = c.take<char>(feature_extractor_ws_bytes(s));
+    if (d_rows) rows = d_rows;
+    hipStream_t st = (hipStream_t)stream;
+    UWIE_TRY(launch_feature_extractor(ctx, d_u8, d_f32, s, gray_shift, rows, fx_ws, st));
+    return launch_classify(model->m, rows, batch, d_label, d_proba, ctx->d_status, st);
 }
 
 int uwie_resize_rgb_u8(uwie_ctx *ctx, const uwie_frame_desc *d_desc, int batch, int out_h, int out_w, const uint8_t *d_flips,

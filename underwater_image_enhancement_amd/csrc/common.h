@@ -232,6 +232,31 @@ int launch_feature_extractor(uwie_ctx *ctx, const uint8_t *d_u8, const float *d_
 int launch_resize_rgb(const uwie_frame_desc *d_desc, int B, int oh, int ow, const uint8_t *d_flips, uint8_t *d_u8, float *d_f32,
                       float *d_norm, const float *mean3, const float *std3, uint32_t *d_status, hipStream_t st);
 
+// k_classify.hip: scaler + RandomForest / GradientBoosting / SVC(rbf) prediction per row (main.py:398-433)
+struct ClsNode {  // one tree node; a leaf has left = right = -1 (its feature is 0)
+    double thr;
+    int32_t left, right, feat, miss;
+};
+struct ClsModel {  // device pointers into one blob (uwie_model_create)
+    int kind, F, C, T, K, S;
+    double lr, gamma;
+    const double *mean, *scale;
+    const int32_t *tree_off;  // [T + 1]
+    const ClsNode *nodes;     // [N]
+    const double *value;      // RF [N][C], GB [N]
+    const double *init;       // GB [K]
+    const double *svT;        // SVC [F][S]: support vectors, feature-major
+    const double *coef;       // [C - 1][S]
+    const double *rho;        // [P] = -intercept
+    const double *prob_a, *prob_b;
+    const int32_t *sv_start;  // [C + 1]
+};
+int classify_model_check(const uwie_model_desc *d);
+size_t classify_blob_bytes(const uwie_model_desc *d);
+ClsModel classify_pack(const uwie_model_desc *d, void *host_blob, const void *dev_blob);
+int launch_classify(const ClsModel &m, const double *d_rows, int B, int32_t *d_label, double *d_proba, uint32_t *d_status,
+                    hipStream_t st);
+
 // best[b] = first argmax over the n strategies of scores[k][b][8]; d_out (optional) [B][H][W][3] = d_all[best[b]][b]
 int launch_pick_best(const double *d_scores, int n, Shape s, const uint8_t *d_all, int32_t *d_best, uint8_t *d_out, hipStream_t st);
 
