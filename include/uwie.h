@@ -173,8 +173,7 @@ int uwie_params_init(uwie_params *p, int surface, int strategy);
  *     whose decision differs get their plane again; 2: histograms from that pass, the gray plane from the quadtree's level-0
  *     Canny pre-pass; 0: one pass over the frame per stage, as in rounds 1-3);
  *   SAME TRANSMISSION TO 1e-11, hence the u8 contract of uwie_params.gf_exact = 0 -- which fused guided-filter kernel runs:
- *     gf_pipe (1), gf_split (1), gf_bands (0 = chosen from the job).  They sum the same windows in different orders.
- *     (UWIE_INTER_F32T needs the wavefront kernels: with gf_pipe = 0 it keeps float64.)
+ *     gf_split (1), gf_bands (0 = chosen from the job).  They sum the same windows in different orders.
  *   canny_fault_inject (0) is for tests/test_gpu_robustness.py only (it breaks an invariant on purpose; see uwie_device_status).
  * An environment variable UWIE_<NAME> sets the initial value; it is read once, in uwie_create -- no entry point reads the
  * environment.  Unknown names are an error. */
@@ -512,7 +511,7 @@ int uwie_guided_filter(uwie_ctx *ctx, const uint8_t *d_gray, const float *d_t0, 
  * ring periods between row ksize and row H - (ksize - 2); the rows above and below go to the general kernel
  * (k_guided_pipe) in a second launch.  0 rows = the general kernel alone (small jobs, odd widths, other windows).
  * For benchmarks that price each kernel by the pixels it covers.  The function has no context: it answers for the DEFAULT
- * tuning (gf_pipe = gf_split = 1, gf_bands = 0); a context with other settings runs a different plan. */
+ * tuning (gf_split = 1, gf_bands = 0); a context with other settings runs a different plan. */
 int uwie_guided_plan(int batch, int H, int W, int ksize, int *split_row0, int *split_rows);
 
 /* restore_image (S6:183-188): float32 [batch][H][W][3]. */

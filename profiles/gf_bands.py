@@ -18,7 +18,7 @@ gray = (255 * (field + 0.03 * torch.randn((B, H, W), device="cuda", generator=g)
 t0 = (1.0 - 0.5 * (field * 0.9 + 0.05 * torch.rand((B, H, W), device="cuda", generator=g))).clamp(0.1, 1.0).float().contiguous()
 for rnd in range(2):
     for bands in (0, 2, 3, 4, 5, 6, 7, 8, 10, 12):
-        dev.tune(gf_pipe=1, gf_split=1, gf_bands=bands)
+        dev.tune(gf_split=1, gf_bands=bands)
         dev.guided_filter(gray, t0, 15, 1e-3, exact=False)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

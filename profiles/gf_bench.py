@@ -1,7 +1,8 @@
 """Guided-filter kernel variants side by side: time per launch and max |t - t_ref| against the exact-order kernel.
 
 usage: python profiles/gf_bench.py [H W B [k eps]]   (default 2160 3840 16 15 0.5)
-Variants are selected through the context's route selectors (uwie_set_tuning: gf_pipe, gf_split) and the mode argument.
+Variants are selected through the context's route selectors (uwie_set_tuning: gf_split) and the mode argument; the LDS-tiled
+strip kernel (k_guided_fast) is timed on window 7, which the wavefront kernels do not take.
 """
 import os
 import sys
@@ -25,28 +26,30 @@ gray = (255 * (field + 0.03 * torch.randn((B, H, W), device="cuda", generator=g)
 t0 = (1.0 - 0.5 * (field * 0.9 + 0.05 * torch.rand((B, H, W), device="cuda", generator=g))).clamp(0.1, 1.0).float().contiguous()
 
 
-def run(sel, exact=False, reps=5):
-    dev.tune(gf_pipe=1, gf_split=1, gf_bands=0)
+def run(sel, exact=False, reps=5, kk=k):
+    dev.tune(gf_split=1, gf_bands=0)
     dev.tune(**sel)
-    t = dev.guided_filter(gray, t0, k, eps, exact=exact)
+    t = dev.guided_filter(gray, t0, kk, eps, exact=exact)
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(reps):
-        t = dev.guided_filter(gray, t0, k, eps, exact=exact)
+        t = dev.guided_filter(gray, t0, kk, eps, exact=exact)
     e1.record()
     torch.cuda.synchronize()
     return t, e0.elapsed_time(e1) / reps
 
 
 nb = min(B, 2)
-ref, ms_ref = run({}, exact=True, reps=1)
-ref = ref[:nb].clone()
-print(f"{H}x{W} x{B} k={k} eps={eps}")
-print(f"  exact-order kernels      {ms_ref:8.3f} ms")
-for name, env, mode in (("LDS-tiled strip kernel", {"gf_pipe": 0}, False), ("pipe, f64 ring in LDS", {"gf_split": 0}, False),
-                        ("pipe, f64 split ring", {}, False), ("pipe, fx32 ring", {}, 2)):
-    t, ms = run(env, exact=mode)
-    err = (t[:nb] - ref).abs().max().item()
+refs = {}
+for kk in (k, 7):
+    ref, ms_ref = run({}, exact=True, reps=1, kk=kk)
+    refs[kk] = ref[:nb].clone()
+    print(f"{H}x{W} x{B} k={kk} eps={eps}")
+    print(f"  exact-order kernels      {ms_ref:8.3f} ms")
+for name, env, mode, kk in (("LDS-tiled strip kernel", {}, False, 7), ("pipe, f64 ring in LDS", {"gf_split": 0}, False, k),
+                            ("pipe, f64 split ring", {}, False, k), ("pipe, fx32 ring", {}, 2, k)):
+    t, ms = run(env, exact=mode, kk=kk)
+    err = (t[:nb] - refs[kk]).abs().max().item()
     gbs = B * H * W * 13 / ms / 1e6
-    print(f"  {name:24s} {ms:8.3f} ms   {gbs:7.1f} GB/s algorithmic   max|t - t_exact| = {err:.3e}")
+    print(f"  {name:24s} k={kk:2d} {ms:8.3f} ms   {gbs:7.1f} GB/s algorithmic   max|t - t_exact| = {err:.3e}")

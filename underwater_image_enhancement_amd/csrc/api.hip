@@ -60,13 +60,13 @@ private:
     }
 
 struct KnobName { const char *name; int Tuning::*field; };
-const KnobName kKnobs[] = {{"gf_pipe", &Tuning::gf_pipe}, {"gf_split", &Tuning::gf_split}, {"gf_bands", &Tuning::gf_bands},
+const KnobName kKnobs[] = {{"gf_split", &Tuning::gf_split}, {"gf_bands", &Tuning::gf_bands},
                            {"select_generic", &Tuning::select_generic}, {"restore_store", &Tuning::restore_store},
                            {"lin_predict3", &Tuning::lin_predict3}, {"lin_cap", &Tuning::lin_cap},
                            {"lin_no_predict", &Tuning::lin_no_predict}, {"q_hist", &Tuning::q_hist}, {"lin_predict_shift", &Tuning::lin_predict_shift},
                            {"streams", &Tuning::streams}, {"canny_prepass", &Tuning::canny_prepass},
                            {"canny_fault_inject", &Tuning::canny_fault_inject}, {"rank_sweep", &Tuning::rank_sweep},
-                           {"gf_fuse", &Tuning::gf_fuse}, {"exact_fused", &Tuning::exact_fused}, {"entry_fuse", &Tuning::entry_fuse}};
+                           {"gf_fuse", &Tuning::gf_fuse}, {"entry_fuse", &Tuning::entry_fuse}};
 
 void tuning_from_env(Tuning *t)  // uwie_create only
 {
@@ -109,10 +109,11 @@ struct Pipe {
     double *F64;    // float64 planar image (dict-surface dehazing only)
     double *pct64;
     uint8_t *gray;
-    float *t0;
+    float *t0;      // inside the scratch unless `planes`
     double *t;
     void *scratch;
     size_t scratch_bytes;
+    bool planes;      // the scratch holds the exact-order guided filter's six float64 planes
     uint32_t *qpart;  // level-0 quadrant shares of cast detection's chunks (tuning entry_fuse; inside the scratch, behind what cast
                       // detection and the quadtree use), or nullptr
     int32_t *guess;   // ... and the cast kinds its gray plane was first written for
@@ -132,6 +133,19 @@ bool dehazes(const uwie_params *p)
 {
     if (p->surface == UWIE_SURFACE_SIX) return p->strategy >= 1 && p->strategy <= 3;
     return p->strategy >= UWIE_DICT_STRONG_DEHAZING && p->strategy <= UWIE_DICT_LIGHT_ENHANCEMENT;
+}
+
+// The guided filter of a u8 dehazing call: t0 comes from the frame (k_trans_init, or inside the fused kernel)
+GuidedRequest u8_guided(const uwie_params *p)
+{
+    const bool six = p->surface == UWIE_SURFACE_SIX;
+    GuidedRequest r{p->gf_ksize, p->gf_eps, p->gf_exact != 0};
+    // fixed-point a/b ring: only with the pre-clipped transmission of the six_stadigy surface (0.1 <= t0 <= 1 bounds a, b)
+    r.fx = six && p->inter_dtype == UWIE_INTER_FX32;
+    // (the three-digit key sweeps of tuning select_generic instantiate the restore for the float64 plane only: no float32 t there)
+    r.f32_ok = six && p->inter_dtype == UWIE_INTER_F32T && !tune().select_generic;
+    r.t0_from_frame = true;
+    return r;
 }
 
 Pipe carve_pipe(Carver &c, Shape s, const uwie_params *p)
@@ -156,8 +170,8 @@ Pipe carve_pipe(Carver &c, Shape s, const uwie_params *p)
         P.F = c.take<float>(n * 3);
     }
     const int tx = p ? p->tiles_x : 8, ty = p ? p->tiles_y : 8;
-    // the exact-order guided filter materialises six float64 planes; the default kernels keep everything on chip
-    const bool gf_planes = dz && (!p || p->gf_exact || !guided_fast_handles(s, p->gf_ksize));
+    // the exact-order guided filter materialises six float64 planes; the other routes keep everything on chip
+    const bool gf_planes = dz && (!p || plan_guided(s, u8_guided(p)).planes);
     if (dz) {
         P.gray = c.take<uint8_t>(n);
         // The raw transmission lives from k_trans_init to the end of the guided filter.  The scratch region is idle exactly then
@@ -179,14 +193,15 @@ Pipe carve_pipe(Carver &c, Shape s, const uwie_params *p)
         if (P.scratch_bytes < qoff + quad_part_bytes(s)) P.scratch_bytes = qoff + quad_part_bytes(s);
     }
     P.scratch = c.take<char>(P.scratch_bytes);
+    P.planes = gf_planes;
     if (dz && !gf_planes) P.t0 = static_cast<float *>(P.scratch);
     if (qoff && P.scratch) P.qpart = reinterpret_cast<uint32_t *>(static_cast<char *>(P.scratch) + qoff);
     return P;
 }
 
 // A parameter set whose carve_pipe layout holds every one of `n` six_stadigy sets (uwie_enhance_all_u8 runs them from
-// one workspace): dehazing layout, the exact-order guided filter's planes if any dehazing set needs them (gf_exact, or
-// a window the fused kernels do not take), the largest CLAHE tile grid.
+// one workspace): dehazing layout, the exact-order guided filter's planes if any dehazing set's plan needs them, the largest
+// CLAHE tile grid.
 uwie_params merged_params(const uwie_params *ps, int n, Shape s)
 {
     uwie_params m = ps[0];
@@ -196,30 +211,22 @@ uwie_params merged_params(const uwie_params *ps, int n, Shape s)
         if (ps[i].surface == UWIE_SURFACE_SIX && ps[i].strategy == 3) m.strategy = 3;  // (its tail reads the stored planes)
         if (ps[i].tiles_x > m.tiles_x) m.tiles_x = ps[i].tiles_x;
         if (ps[i].tiles_y > m.tiles_y) m.tiles_y = ps[i].tiles_y;
-        if (ps[i].surface == UWIE_SURFACE_SIX && ps[i].strategy <= 3 &&
-            (ps[i].gf_exact || !guided_fast_handles(s, ps[i].gf_ksize)))
-            m.gf_exact = 1;
+        if (ps[i].surface == UWIE_SURFACE_SIX && ps[i].strategy <= 3 && plan_guided(s, u8_guided(&ps[i])).planes) m.gf_exact = 1;
     }
     return m;
 }
 
-// *t_is_f32 (optional): set when the transmission was written as float32 (UWIE_INTER_F32T and a window / frame the
-// wavefront kernels take); everything downstream reads it through RestoreSrc::t32
-int stage_guided(uwie_ctx *ctx, const Pipe &P, Shape s, const uwie_params *p, hipStream_t st, int *t_is_f32 = nullptr)
+// The guided filter of a u8 dehazing call on P's buffers: t0 from `frame` (k_trans_init into P.t0, or inside the fused kernel),
+// then t.  *t_is_f32 (optional): t was written as float32; everything downstream reads it through RestoreSrc::t32.
+int stage_guided(const Pipe &P, Shape s, const uwie_params *p, const FuseT0Args &frame, hipStream_t st, int *t_is_f32 = nullptr)
 {
-    int handled = 0;
-    if (t_is_f32) *t_is_f32 = 0;
-    if (t_is_f32 && p->inter_dtype == UWIE_INTER_F32T && !p->gf_exact && p->surface == UWIE_SURFACE_SIX && tune().gf_pipe) {
-        UWIE_TRY(launch_guided_pipe(P.gray, P.t0, s, p->gf_ksize, p->gf_eps, 0, P.t, &handled, st, true));
-        if (handled) {
-            *t_is_f32 = 1;
-            return UWIE_OK;
-        }
-    }
-    // fixed-point a/b ring: only with the pre-clipped transmission of the six_stadigy surface (0.1 <= t0 <= 1 bounds a, b)
-    const bool fx = p->surface == UWIE_SURFACE_SIX && p->inter_dtype == UWIE_INTER_FX32;
-    if (!p->gf_exact) UWIE_TRY(launch_guided_fast(P.gray, P.t0, s, p->gf_ksize, p->gf_eps, P.t, &handled, st, fx));
-    if (!handled) UWIE_TRY(launch_guided(P.gray, P.t0, s, p->gf_ksize, p->gf_eps, P.t, P.scratch, st));
+    const GuidedPlan g = plan_guided(s, u8_guided(p));
+    // the exact-order filter builds its planes in the scratch, where t0 lives otherwise (enhance_all runs each set's own plan
+    // in one merged layout)
+    UWIE_REQUIRE(!g.planes || (P.planes && P.t0 != P.scratch), "guided filter: the workspace layout has no planes for the exact-order filter");
+    if (g.t0) UWIE_TRY(launch_trans_init(frame.rgb, frame.kind, frame.A, s, frame.omega, frame.norm_eps, frame.pre_clip, P.t0, st));
+    UWIE_TRY(launch_guided_plan(g, s, P.gray, P.t0, P.t, P.scratch, st, &frame));
+    if (t_is_f32) *t_is_f32 = g.t_f32;
     return UWIE_OK;
 }
 
@@ -267,16 +274,7 @@ int six_dehaze_tail(uwie_ctx *ctx, const uint8_t *d_in, const int32_t *kind, Sha
     const float eps = 1e-6f;  // six_stadigy.py:198,218
     const int k = p->strategy;
     int t_is_f32 = 0;
-    // (the three-digit key sweeps of tuning select_generic instantiate the restore for the float64 plane only: no float32 t there)
-    const bool want_f32 = p->inter_dtype == UWIE_INTER_F32T && !tune().select_generic && !(s.W & 1);
-    if (!p->gf_exact && p->gf_eps > 0.0 && (p->inter_dtype != UWIE_INTER_FX32) && guided_fused_takes(s, p->gf_ksize)) {
-        // round 4: the transmission's first half (S6:170-174) is evaluated inside the guided filter: no t0 plane
-        UWIE_TRY(launch_guided_fused(P.gray, d_in, kind, P.A, (float)p->omega, 1e-6f, 1, s, p->gf_ksize, p->gf_eps, P.t, st, want_f32));
-        t_is_f32 = want_f32;
-    } else {
-        UWIE_TRY(launch_trans_init(d_in, kind, P.A, s, (float)p->omega, 1e-6f, 1, P.t0, st));
-        UWIE_TRY(stage_guided(ctx, P, s, p, st, tune().select_generic ? nullptr : &t_is_f32));
-    }
+    UWIE_TRY(stage_guided(P, s, p, FuseT0Args{d_in, kind, P.A, (float)p->omega, 1e-6f, 1}, st, &t_is_f32));  // S6:170-180
     // fused tail: restore writes the planar image into P.F and feeds the selection's first histogram sweep
     SelectPlan plan;
     const double q[4] = {p->L_low, p->L_high, p->wb_percentile, 100 - p->wb_percentile};
@@ -346,12 +344,7 @@ int run_dict_dehaze(uwie_ctx *ctx, const uint8_t *d_in, Shape s, const uwie_para
 {
     if (!have_airlight)
         UWIE_TRY(launch_airlight(ctx, d_in, nullptr, P.gray, s, p->min_size, P.A, nullptr, P.scratch, st, p->gray_shift));
-    if (!p->gf_exact && p->gf_eps > 0.0 && guided_fused_takes(s, p->gf_ksize)) {
-        UWIE_TRY(launch_guided_fused(P.gray, d_in, nullptr, P.A, (float)p->omega, 1e-10f, 0, s, p->gf_ksize, p->gf_eps, P.t, st, false));
-    } else {
-        UWIE_TRY(launch_trans_init(d_in, nullptr, P.A, s, (float)p->omega, 1e-10f, 0, P.t0, st));  // ES:221-225
-        UWIE_TRY(stage_guided(ctx, P, s, p, st));
-    }
+    UWIE_TRY(stage_guided(P, s, p, FuseT0Args{d_in, nullptr, P.A, (float)p->omega, 1e-10f, 0}, st));  // ES:221-232
     SelectPlan plan;
     const double q[2] = {p->L_low, p->L_high};
     // the recovered image is clipped to [0, 1]: linear first digit, one collecting sweep (select_lin_*64);
@@ -481,9 +474,7 @@ static int run_float_six(uwie_ctx *ctx, const float *d_img, Shape s, const uwie_
         UWIE_TRY(launch_rgb2gray_u8(P.q, P.gray, (size_t)s.B * s.npx(), p->gray_shift, st));
         UWIE_TRY(launch_float_airlight<float>(x, P.gray, s, p->min_size, P.A, P.scratch, st));
         UWIE_TRY(launch_float_trans_init<float>(x, P.A, s, p->omega, (double)1e-6f, 1, P.t0, st));
-        int handled = 0;
-        if (!p->gf_exact) UWIE_TRY(launch_guided_fast(P.gray, P.t0, s, p->gf_ksize, p->gf_eps, P.t, &handled, st, false));
-        if (!handled) UWIE_TRY(launch_guided(P.gray, P.t0, s, p->gf_ksize, p->gf_eps, P.t, P.scratch, st));
+        UWIE_TRY(launch_guided_plan(plan_guided(s, {p->gf_ksize, p->gf_eps, p->gf_exact != 0}), s, P.gray, P.t0, P.t, P.scratch, st));
         UWIE_TRY((launch_float_restore<float, float>(x, P.A, P.t, s, y, 0, st)));
         UWIE_TRY(float_stretch(P, y, s, p->L_low, p->L_high, st));
         if (k == 3) {
@@ -522,13 +513,9 @@ static int run_float_dict(uwie_ctx *ctx, const T *d_img, Shape s, const uwie_par
     UWIE_TRY(launch_rgb2gray_u8(P.q, P.gray, (size_t)s.B * s.npx(), p->gray_shift, st));
     UWIE_TRY(launch_float_airlight<T>(d_img, P.gray, s, p->min_size, P.A, P.scratch, st));
     UWIE_TRY(launch_float_trans_init<T>(d_img, P.A, s, p->omega, 1e-10, 0, P.t0, st));  // ES:221-225: no clip
-    if constexpr (sizeof(T) == 4) {
-        int handled = 0;
-        if (!p->gf_exact) UWIE_TRY(launch_guided_fast(P.gray, P.t0, s, p->gf_ksize, p->gf_eps, P.t, &handled, st, false));
-        if (!handled) UWIE_TRY(launch_guided(P.gray, P.t0, s, p->gf_ksize, p->gf_eps, P.t, P.scratch, st));
-    } else {
-        UWIE_TRY(launch_guided_p64(P.gray, P.t0, s, p->gf_ksize, p->gf_eps, P.t, P.scratch, st));
-    }
+    GuidedRequest r{p->gf_ksize, p->gf_eps, p->gf_exact != 0};
+    r.t0_f64 = sizeof(T) == 8;  // float64 images: the exact-order kernels
+    UWIE_TRY(launch_guided_plan(plan_guided(s, r), s, P.gray, P.t0, P.t, P.scratch, st));
     UWIE_TRY((launch_float_restore<T, double>(d_img, P.A, P.t, s, P.F64, 1, st)));
     SelectPlan plan;
     const double q[2] = {p->L_low, p->L_high};
@@ -1430,20 +1417,19 @@ int uwie_guided_filter(uwie_ctx *ctx, const uint8_t *d_gray, const float *d_t0, 
     const Shape s{batch, H, W};
     UWIE_CHECK_WS(guided_ws_bytes(s));
     UWIE_REQUIRE(exact >= 0 && exact <= 2, "guided_filter: mode is 0 (fused float64), 1 (exact order) or 2 (fixed-point ring)");
-    int handled = 0;
-    if (exact != 1) UWIE_TRY(launch_guided_fast(d_gray, d_t0, s, ksize, eps, d_t, &handled, (hipStream_t)stream, exact == 2));
-    if (handled) return UWIE_OK;
-    return launch_guided(d_gray, d_t0, s, ksize, eps, d_t, d_workspace, (hipStream_t)stream);
+    GuidedRequest r{ksize, eps, exact == 1};
+    r.fx = exact == 2;
+    return launch_guided_plan(plan_guided(s, r), s, d_gray, d_t0, d_t, d_workspace, (hipStream_t)stream);
 }
 
 int uwie_guided_plan(int batch, int H, int W, int ksize, int *split_row0, int *split_rows)
 {
     UWIE_REQUIRE(split_row0 && split_rows, "guided_plan: NULL pointer");
     UWIE_CHECK_SHAPE(batch, H, W);
-    int iy0 = 0, band = 0, nb = 0, rows = 0;
-    const bool split = guided_split_plan(Shape{batch, H, W}, ksize, &iy0, &band, &nb, &rows);
-    *split_row0 = split ? iy0 : 0;
-    *split_rows = split ? rows : 0;
+    const GuidedPlan g = plan_guided(Shape{batch, H, W}, {ksize, 1.0});  // (any eps > 0; the default tuning outside a context)
+    const bool split = g.route == GF_SPLIT;
+    *split_row0 = split ? g.iy0 : 0;
+    *split_rows = split ? g.rows : 0;
     return UWIE_OK;
 }
 

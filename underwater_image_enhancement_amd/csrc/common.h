@@ -88,8 +88,7 @@ namespace uwie {
 // equivalent routes a stage takes (tests force the fallback routes through uwie_set_tuning; profiles/ scripts compare
 // them).  Environment variables UWIE_<NAME> are read ONCE, in uwie_create -- never per call.
 struct Tuning {
-    int gf_pipe = 1;            // guided filter: wavefront kernels of k_guided_pipe.hip (0: the LDS-tiled strip kernel)
-    int gf_split = 1;           // ... their split-ring form for large jobs (0: the general kernel alone)
+    int gf_split = 1;           // guided filter: the split-ring wavefront kernel for large jobs (0: the general kernel alone)
     int gf_bands = 0;           // ... bands per strip (0: chosen from the job's size)
     int select_generic = 0;     // percentile selection: the three-digit key sweeps alone
     int restore_store = 0;      // strategies 1-2 / dict dehazing: keep the restored image in planes instead of recomputing it
@@ -103,7 +102,6 @@ struct Tuning {
     int gf_fuse = 0;            // ... with t0 computed from the frame's bytes inside it (k_guided_split8: -0.08 ms per 4K x 64 step, opt-in; 0: k_trans_init + t0 plane)
     int rank_sweep = 1;         // strategies 1-2: the rank-counting restore sweep on jobs of >= 16 MP (0: the histogram sweep; 2: any size)
     int canny_fault_inject = 0; // tests only: k_canny_gradnms leaves out the root labels (the round-3 defect): uwie_device_status must report it
-    int exact_fused = 1;         // gf_exact = 1, k = 15: rows and columns of the first box filter in one kernel (0: separate passes)
     int entry_fuse = 1;         // frames with W % 8 == 0: the level-0 quadrant histograms come out of cast detection's chunk pass and the
                                 // gray plane out of the Canny pre-pass (0: k_q_hist<gray> + k_canny_strong as in rounds 3 - 4)
 };
@@ -268,22 +266,55 @@ int launch_trans_init(const uint8_t *d_in, const int32_t *d_kind, const float *d
 int launch_box_filter_f64(const double *d_src, double *d_dst, Shape s, int k, void *ws, hipStream_t st);
 int launch_guided(const uint8_t *d_gray, const float *d_t0, Shape s, int k, double eps, double *d_t, void *ws,
                   hipStream_t st);
+int launch_guided_p64(const uint8_t *d_gray, const double *d_t0, Shape s, int k, double eps, double *d_t, void *ws, hipStream_t st);
 
-bool guided_fast_handles(Shape s, int k);
-// k_guided_fast.hip: fused float64 guided filter (free summation order); *handled = 0 -> use launch_guided
-// ring_fx: the caller guarantees 0.1 <= t0 <= 1 (pre-clipped transmission) and accepts the fixed-point a/b ring
-int launch_guided_fast(const uint8_t *d_gray, const float *d_t0, Shape s, int k, double eps, double *d_t, int *handled,
-                       hipStream_t st, bool ring_fx = false);
-// k_guided_pipe.hip: software-pipelined wavefront kernel for k in {10, 15, 20}; ring 0 = float64, 1 = fixed-point int32
-bool guided_split_plan(Shape s, int k, int *iy0, int *band, int *nb, int *rows = nullptr);
-// out_f32: d_t is written as float32 (UWIE_INTER_F32T); only the pipe / split kernels do that, so *handled = 0 then means
-// "not taken, nothing written"
-int launch_guided_pipe(const uint8_t *d_gray, const float *d_t0, Shape s, int k, double eps, int ring, double *d_t,
-                       int *handled, hipStream_t st, bool out_f32 = false);
-// the same filter with t0 = 1 - omega * min_c(img / (A + eps)) [clipped] computed inside it from the u8 frame (round 4)
-bool guided_fused_takes(Shape s, int k);
-int launch_guided_fused(const uint8_t *d_gray, const uint8_t *d_rgb, const int32_t *d_kind, const float *d_A, float omega,
-                        float norm_eps, int pre_clip, Shape s, int k, double eps, double *d_t, hipStream_t st, bool out_f32);
+// The guided filter's routes (k_guided_pipe.hip): plan_guided is the one place that decides which kernels filter a job,
+// what they need of the workspace and how t comes out; launch_guided_plan runs a plan and never declines one.
+enum GuidedRoute {
+    GF_EXACT,  // k_guided.hip: cv2.boxFilter's summation order, six float64 planes of workspace (guided_ws_bytes)
+    GF_FAST,   // k_guided_fast<TH>: LDS strips (windows and frames the wavefront kernels do not take)
+    GF_PIPE,   // k_guided_pipe: the general wavefront kernel, float64 or fixed-point a/b ring
+    GF_SPLIT,  // k_guided_split (+ a k_guided_pipe border launch for even windows): large jobs
+    GF_FUSED,  // k_guided_split8: GF_SPLIT with t0 computed from the frame inside it (tuning gf_fuse)
+};
+struct GuidedRequest {
+    int k;
+    double eps;
+    bool exact = false;          // cv2.boxFilter's summation order (uwie_params.gf_exact)
+    bool fx = false;             // fixed-point a/b ring wanted; the caller guarantees 0.1 <= t0 <= 1 (pre-clipped transmission)
+    bool f32_ok = false;         // t may be written as float32
+    bool t0_from_frame = false;  // t0 may be computed from the u8 frame inside the filter
+    bool t0_f64 = false;         // t0 is float64: the exact-order kernels only
+};
+struct GuidedPlan {
+    GuidedRoute route;
+    int k;
+    double eps;
+    bool t_f32;    // t is written as float32
+    bool ring_fx;  // GF_PIPE: fixed-point a/b ring
+    bool t0_f64;   // GF_EXACT: float64 t0
+    bool t0;       // a t0 plane is read (every route but GF_FUSED)
+    bool planes;   // the six float64 planes are needed (GF_EXACT): depends on the request and the shape, never on tuning
+    int TH;        // GF_FAST: rows per step
+    int iy0, band, nb, rows;  // GF_SPLIT / GF_FUSED: rows [iy0, iy0 + rows) in nb bands of `band` rows
+    int pipe_bands;           // GF_PIPE and GF_SPLIT's border launch: bands per strip of the general kernel
+};
+GuidedPlan plan_guided(Shape s, const GuidedRequest &r);
+// t0 from the u8 frame: 1 - omega * min_c(img / (A + norm_eps)), clipped to [0.1, 1] with pre_clip (k_trans_init)
+struct FuseT0Args {
+    const uint8_t *rgb;    // [B][H][W][3]
+    const int32_t *kind;   // [B] cast kinds or nullptr
+    const float *A;        // [B][3]
+    float omega, norm_eps;
+    int pre_clip;
+};
+// d_t0: float32 (float64 for t0_f64 plans), not read by GF_FUSED, which computes it from *frame; d_t: float64, or float32
+// data for t_f32 plans; ws: the six planes of GF_EXACT
+int launch_guided_plan(const GuidedPlan &g, Shape s, const uint8_t *d_gray, const void *d_t0, double *d_t, void *ws, hipStream_t st,
+                       const FuseT0Args *frame = nullptr);
+// k_guided_fast.hip: the rows per step (8, 4, 2) of the k_guided_fast<TH> kernel that takes this job, 0 = none
+int guided_fast_th(Shape s, int k);
+int launch_guided_fast(const uint8_t *d_gray, const float *d_t0, Shape s, int k, int TH, double eps, double *d_t, hipStream_t st);
 
 // k_select.hip
 constexpr int kMaxPct = 4;  // percentiles per call
@@ -449,7 +480,6 @@ template <class T> int launch_float_trans_init(const T *d_x, const T *d_A, Shape
                                                hipStream_t st);
 template <class T, class OUT> int launch_float_restore(const T *d_x, const T *d_A, const double *d_t, Shape s, OUT *d_out, int planar,
                                                        hipStream_t st);
-int launch_guided_p64(const uint8_t *d_gray, const double *d_t0, Shape s, int k, double eps, double *d_t, void *ws, hipStream_t st);
 
 // k_tail.hip
 int launch_restore(const uint8_t *d_in, const int32_t *d_kind, const float *d_A, const double *d_t, Shape s,

@@ -841,7 +841,7 @@ static int launch_guided_t(const uint8_t *d_gray, const TP *d_t0, Shape s, int k
     const size_t n = (size_t)s.B * s.npx();
     double *rs = c.take<double>(n * 6);  // 4 row-sum planes + a + b
     double *pa = rs + 4 * n, *pb = rs + 5 * n;
-    if (k == 15 && s.H >= 16 && s.W >= 32 && tune().exact_fused) {
+    if (k == 15 && s.H >= 16 && s.W >= 32) {
         // rows and columns of the first filter in one kernel; the row chains' values at the strips' left edges first
         const int nstrips = cdiv(s.W, 16);
         {

@@ -340,33 +340,20 @@ bool fits(const FastGeom &g, int TH)
 
 }  // namespace
 
-// Whether launch_guided_fast will take this (shape, window) with one of the k_guided_fast<TH> kernels (the wavefront kernels
-// of k_guided_pipe.hip are tried first, but every shape they take is also taken here); if not, the exact-order path and its
-// six float64 planes of workspace are needed.
-bool guided_fast_handles(Shape s, int k)
+int guided_fast_th(Shape s, int k)
 {
-    return fits(make_fast_geom(s, k, 8), 8) || fits(make_fast_geom(s, k, 4), 4) || fits(make_fast_geom(s, k, 2), 2);
+    for (int TH = 8; TH >= 2; TH /= 2)
+        if (fits(make_fast_geom(s, k, TH), TH)) return TH;
+    return 0;
 }
 
-// Returns UWIE_OK and sets *handled = 0 when the window is too wide for the LDS-resident formulation (the caller
-// then uses the exact-order path).
-int launch_guided_fast(const uint8_t *d_gray, const float *d_t0, Shape s, int k, double eps, double *d_t, int *handled,
-                       hipStream_t st, bool ring_fx)
+int launch_guided_fast(const uint8_t *d_gray, const float *d_t0, Shape s, int k, int TH, double eps, double *d_t, hipStream_t st)
 {
-    *handled = 0;
-    // software-pipelined wavefront kernels (k_guided_pipe.hip) first; tuning gf_pipe = 0 keeps the LDS-tiled strip kernel
-    if (tune().gf_pipe) {
-        const int rcp = launch_guided_pipe(d_gray, d_t0, s, k, eps, ring_fx ? 1 : 0, d_t, handled, st);
-        if (rcp != UWIE_OK || *handled) return rcp;
-    }
-    const FastGeom g8 = make_fast_geom(s, k, 8), g4 = make_fast_geom(s, k, 4), g2 = make_fast_geom(s, k, 2);
-    int rc = UWIE_OK;
-    if (fits(g8, 8)) rc = launch_th<8>(d_gray, d_t0, s, g8, eps, d_t, st);
-    else if (fits(g4, 4)) rc = launch_th<4>(d_gray, d_t0, s, g4, eps, d_t, st);
-    else if (fits(g2, 2)) rc = launch_th<2>(d_gray, d_t0, s, g2, eps, d_t, st);
-    else return UWIE_OK;
-    if (rc == UWIE_OK) *handled = 1;
-    return rc;
+    const FastGeom g = make_fast_geom(s, k, TH);
+    UWIE_REQUIRE(fits(g, TH), "guided_fast: the job does not fit the strip kernel");
+    if (TH == 8) return launch_th<8>(d_gray, d_t0, s, g, eps, d_t, st);
+    if (TH == 4) return launch_th<4>(d_gray, d_t0, s, g, eps, d_t, st);
+    return launch_th<2>(d_gray, d_t0, s, g, eps, d_t, st);
 }
 
 }  // namespace uwie

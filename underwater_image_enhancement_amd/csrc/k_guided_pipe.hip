@@ -1157,14 +1157,6 @@ k_guided_split(const uint8_t *__restrict__ gray, const float *__restrict__ t0, T
 // The table is 3 KB: one per wavefront would cost the eighth wavefront of a CU (8 x 19.2 KB of ring and staging lines leave
 // 10 KB), so eight strips share a workgroup and ONE table.  Nothing else is shared: every wavefront keeps its own LDS
 // region and its own pace (one barrier, after the table is filled).  grid (ceil(strips * bands / 8), 1, B), block 512.
-struct FuseT0Args {
-    const uint8_t *rgb;    // [B][H][W][3]
-    const int32_t *kind;   // [B] cast kinds or nullptr
-    const float *A;        // [B][3]
-    float omega, norm_eps;
-    int pre_clip;
-};
-
 template <int K, typename TOut>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_guided_split8(const uint8_t *__restrict__ gray, FuseT0Args fz, TOut *__restrict__ tout, SplitGeom g, PipeConsts cs, int nstrips)
@@ -1253,22 +1245,12 @@ int launch_split(const uint8_t *d_gray, const float *d_t0, Shape s, const PipeCo
 
 // border != nullptr: {iy0, iy1, iband, nibands, is0, is1}: the launch covers everything around the interior block
 template <int K, bool FX, typename TOut>
-int launch_pipe(const uint8_t *d_gray, const float *d_t0, Shape s, const PipeConsts &cs, TOut *d_t, hipStream_t st,
+int launch_pipe(const uint8_t *d_gray, const float *d_t0, Shape s, const PipeConsts &cs, TOut *d_t, int nbands, hipStream_t st,
                 const int *border = nullptr)
 {
     using C = PipeCfg<K>;
     constexpr int lds = C::lds_bytes(FX);
     const int nstrips = cdiv(s.W, C::NV);
-    const int resident = 256 * std::max(1, std::min(8, (160 * 1024) / lds));
-    int nbands = 1;
-    if (tune().gf_bands > 0) nbands = tune().gf_bands;
-    else {
-        const long strips = (long)nstrips * s.B;
-        if (strips < 12L * resident) nbands = (int)cdiv((size_t)(12L * resident), (size_t)strips);
-        const int cap = std::max(1, s.H / (16 * (K - 1)));
-        nbands = std::min(nbands, std::max(cap, (int)cdiv((size_t)(3L * resident), (size_t)strips)));
-    }
-    nbands = std::max(1, std::min(nbands, s.H / std::max(UWIE_GF_MINBAND, 2 * K)));
     PipeGeom g{};
     g.H = s.H; g.W = s.W;
     g.band = cdiv(s.H, nbands);
@@ -1286,28 +1268,41 @@ int launch_pipe(const uint8_t *d_gray, const float *d_t0, Shape s, const PipeCon
     return UWIE_OK;
 }
 
-}  // namespace
+// Bands per strip of a k_guided_pipe launch: `forced` (tuning gf_bands), else chosen from the job's size
+int pipe_bands(Shape s, int k, bool fx, int forced)
+{
+    const int lds = k == 10 ? PipeCfg<10>::lds_bytes(fx) : k == 15 ? PipeCfg<15>::lds_bytes(fx) : PipeCfg<20>::lds_bytes(fx);
+    const int resident = 256 * std::max(1, std::min(8, (160 * 1024) / lds));
+    int nbands = 1;
+    if (forced > 0) nbands = forced;
+    else {
+        const long strips = (long)cdiv(s.W, kPipeSlots - 2 * (k - 1)) * s.B;
+        if (strips < 12L * resident) nbands = (int)cdiv((size_t)(12L * resident), (size_t)strips);
+        const int cap = std::max(1, s.H / (16 * (k - 1)));
+        nbands = std::min(nbands, std::max(cap, (int)cdiv((size_t)(3L * resident), (size_t)strips)));
+    }
+    return std::max(1, std::min(nbands, s.H / std::max(UWIE_GF_MINBAND, 2 * k)));
+}
 
 // Rows [*iy0, min(H, *iy0 + *nb * *band)) go to k_guided_split (float64 ring; k = 10, 15 or 20, an even W, a job large enough
-// to fill the chip with long bands); false = the general kernel alone.
+// to fill the chip with long bands); false = the general kernel alone.  forced: bands per strip (tuning gf_bands; tests: the
+// split kernel on small frames), 0 = chosen from the job's size.
 //   odd k:  every row -- the kernel reflects row indices itself, which is exact for a symmetric window;
 //   even k: the window [y - k/2, y + k/2 - 1] is not symmetric, so a virtual a/b row above row 0 built from reflected raw rows
 //           is NOT the a/b row cv2.boxFilter mirrors in: the split kernel takes the whole bands between row k and row
 //           H - (k - 2) (no reflection anywhere in them), the general kernel the rows above and below (launch_pipe, border).
-bool guided_split_plan(Shape s, int k, int *iy0, int *band, int *nb, int *rows)
+bool split_plan(Shape s, int k, int forced_bands, int *iy0, int *band, int *nb, int *rows)
 {
-    if (rows) *rows = 0;
-    if ((k != 10 && k != 15 && k != 20) || (s.W & 1) || !tune().gf_split) return false;
-    if (s.W < 2 * k || s.H < 4 * k || s.B > 65535 || s.npx() >= ((size_t)1 << 27)) return false;
+    const bool forced = forced_bands > 0;
+    if ((s.W & 1) || s.npx() >= ((size_t)1 << 27)) return false;
     const int RC = k, a = k / 2, Lb = k - 1 - a, NV = kPipeSlots - 2 * (k - 1);
     const bool odd = k & 1;
     *iy0 = odd ? 0 : 2 * a;
     const int periods = odd ? cdiv(s.H, RC) : (s.H - 2 * a - 2 * Lb) / RC;
     if (periods < 4) return false;
     const long strips = (long)cdiv(s.W, NV) * s.B;
-    const bool forced = tune().gf_bands > 0;  // (tests: the split kernel on small frames)
     int n;
-    if (forced) n = tune().gf_bands;
+    if (forced) n = forced_bands;
     else {
         // ~8 wavefronts per resident slot (256 CUs x 8) even out the tail; a band costs one extra ring period
         n = (int)cdiv((size_t)(8L * 2048), (size_t)strips);
@@ -1318,139 +1313,129 @@ bool guided_split_plan(Shape s, int k, int *iy0, int *band, int *nb, int *rows)
         const int per_band = cdiv(periods, n);
         *band = RC * per_band;
         *nb = cdiv(periods, per_band);  // the last band may be shorter (it stops at the image's last row)
-        if (rows) *rows = s.H;
+        *rows = s.H;
     } else {
         const int per_band = periods / n;  // whole periods only: the last band takes the periods that are left over
         *band = RC * per_band;
         *nb = periods / per_band;
-        if (rows) *rows = periods * RC;
+        *rows = periods * RC;
     }
     // small jobs (fewer long bands than half the chip holds): the general kernel cuts shorter bands
     return forced || strips * n >= 1024;
 }
 
-// The guided filter with the transmission's first half fused in (k_guided_split8): window 15, a frame the split kernel takes
-// whole, tuning gf_pipe / gf_split / gf_fuse on.  false = the caller materialises t0 (launch_trans_init) as before.
-bool guided_fused_takes(Shape s, int k)
+// Fixed-point a/b ring scales 2^Sa, 2^Sb for this eps; false = too wide an a/b range (tiny eps): the float64 ring.
+// |cov| <= sigma_p * sigma_I, sigma_p <= 0.45, sigma_I <= 0.5:  |a| <= 0.45 s / (s^2 + eps), s = sigma_I
+bool fx_scales(double eps, int *Sa, int *Sb)
 {
-    if (k != 15 || !tune().gf_pipe || !tune().gf_fuse) return false;
-    int iy0, band, nb, rows;
-    return guided_split_plan(s, k, &iy0, &band, &nb, &rows) && rows == s.H;
+    const double se = std::sqrt(eps);
+    const double amax = (se <= 0.5 ? 0.45 / (2.0 * se) : 0.225 / (0.25 + eps)) * 1.02;
+    const double hb = (0.45 + amax) * 1.02;  // |b - 0.55|
+    *Sa = (int)std::floor(std::log2(1073741824.0 / amax));
+    *Sb = (int)std::floor(std::log2(1073741824.0 / hb));
+    return *Sa >= 28 && *Sb >= 28;
 }
 
-int launch_guided_fused(const uint8_t *d_gray, const uint8_t *d_rgb, const int32_t *d_kind, const float *d_A, float omega,
-                        float norm_eps, int pre_clip, Shape s, int k, double eps, double *d_t, hipStream_t st, bool out_f32)
+PipeConsts pipe_consts(const GuidedPlan &g)
 {
-    UWIE_REQUIRE(guided_fused_takes(s, k) && eps > 0.0, "guided_fused: not a job for the fused kernel");
-    const double K2 = (double)k * k, scale = 1.0 / K2;
+    const double K2 = (double)g.k * g.k, scale = 1.0 / K2;
     PipeConsts cs{};
-    cs.Ek = 255.0 * K2 * K2 * eps;
+    cs.Ek = 255.0 * K2 * K2 * g.eps;
     cs.kaI = scale / 255.0;
     cs.kb = scale;
     cs.b0 = 0.0;
-    int iy0, band, nb, rows;
-    guided_split_plan(s, k, &iy0, &band, &nb, &rows);
-    const FuseT0Args fz{d_rgb, d_kind, d_A, omega, norm_eps, pre_clip};
-    if (out_f32) return launch_split8<15, float>(d_gray, fz, s, cs, reinterpret_cast<float *>(d_t), iy0, band, nb, s.H, st);
-    return launch_split8<15, double>(d_gray, fz, s, cs, d_t, iy0, band, nb, s.H, st);
+    int Sa, Sb;
+    if (g.ring_fx && fx_scales(g.eps, &Sa, &Sb)) {
+        const double fa = std::ldexp(1.0, Sa), fb = std::ldexp(1.0, Sb);
+        const double b0i = std::nearbyint(0.55 * fb);
+        cs.fxa = fa;
+        cs.fxb = scale * fb;
+        cs.magic_b = kMagic - b0i;
+        cs.kaI = scale / 255.0 / fa;
+        cs.kb = scale / fb;
+        cs.b0 = b0i / fb;
+    }
+    return cs;
 }
 
-// ring: 0 = float64 (split ring where guided_split_plan takes the job), 1 = fixed-point int32 (requires 0.1 <= t0 <= 1:
-// the caller's pre-clip, six_stadigy.py:174)
-int launch_guided_pipe(const uint8_t *d_gray, const float *d_t0, Shape s, int k, double eps, int ring, double *d_t,
-                       int *handled, hipStream_t st, bool out_f32)
+template <int K, typename TOut>
+int launch_pipe_plan(const GuidedPlan &g, const uint8_t *d_gray, const float *d_t0, Shape s, const PipeConsts &cs, TOut *d_t,
+                     hipStream_t st)
 {
-    *handled = 0;
-    if (out_f32 && (ring != 0 || (s.W & 1))) return UWIE_OK;  // float32 output: float64 ring, paired stores
-    if (s.W < 2 * k || s.H < 4 * k || s.B > 65535 || !(eps > 0.0)) return UWIE_OK;
-    if (k != 10 && k != 15 && k != 20) return UWIE_OK;
-    const double K2 = (double)k * k, scale = 1.0 / K2;
-    PipeConsts cs{};
-    cs.Ek = 255.0 * K2 * K2 * eps;
-    if (ring == 1) {
-        // |cov| <= sigma_p * sigma_I, sigma_p <= 0.45, sigma_I <= 0.5:  |a| <= 0.45 s / (s^2 + eps), s = sigma_I
-        const double se = std::sqrt(eps);
-        const double amax = (se <= 0.5 ? 0.45 / (2.0 * se) : 0.225 / (0.25 + eps)) * 1.02;
-        const double hb = (0.45 + amax) * 1.02;   // |b - 0.55|
-        const int Sa = (int)std::floor(std::log2(1073741824.0 / amax)), Sb = (int)std::floor(std::log2(1073741824.0 / hb));
-        if (Sa < 28 || Sb < 28) ring = 0;  // wide a/b range (tiny eps): keep float64
-        else {
-            const double fa = std::ldexp(1.0, Sa), fb = std::ldexp(1.0, Sb);
-            const double b0i = std::nearbyint(0.55 * fb);
-            cs.fxa = fa;
-            cs.fxb = scale * fb;
-            cs.magic_b = kMagic - b0i;
-            cs.kaI = scale / 255.0 / fa;
-            cs.kb = scale / fb;
-            cs.b0 = b0i / fb;
+    if constexpr (std::is_same<TOut, double>::value)  // (the fixed-point ring stores float64 t only)
+        if (g.ring_fx) return launch_pipe<K, true, double>(d_gray, d_t0, s, cs, d_t, g.pipe_bands, st);
+    if (g.route == GF_PIPE) return launch_pipe<K, false, TOut>(d_gray, d_t0, s, cs, d_t, g.pipe_bands, st);
+    UWIE_TRY_RC((launch_split<K, TOut>(d_gray, d_t0, s, cs, d_t, g.iy0, g.band, g.nb, g.iy0 + g.rows, st)));
+    if (K & 1) return UWIE_OK;
+    // even window: rows [0, iy0) and [iy0 + rows, H) around the split kernel's whole periods
+    const int border[6] = {g.iy0, g.iy0 + g.rows, g.band, 0, 0, 0};
+    return launch_pipe<K, false, TOut>(d_gray, d_t0, s, cs, d_t, g.pipe_bands, st, border);
+}
+
+// GF_PIPE / GF_SPLIT
+template <typename TOut>
+int launch_wave(const GuidedPlan &g, const uint8_t *d_gray, const float *d_t0, Shape s, TOut *d_t, hipStream_t st)
+{
+    const PipeConsts cs = pipe_consts(g);
+    if (g.k == 10) return launch_pipe_plan<10>(g, d_gray, d_t0, s, cs, d_t, st);
+    if (g.k == 15) return launch_pipe_plan<15>(g, d_gray, d_t0, s, cs, d_t, st);
+    return launch_pipe_plan<20>(g, d_gray, d_t0, s, cs, d_t, st);
+}
+
+}  // namespace
+
+GuidedPlan plan_guided(Shape s, const GuidedRequest &r)
+{
+    GuidedPlan g{};
+    g.k = r.k;
+    g.eps = r.eps;
+    g.t0 = true;
+    const bool free_order = !r.exact && !r.t0_f64 && r.k >= 1 && r.k <= 1024;
+    // the wavefront kernels (k_guided_pipe, k_guided_split, k_guided_split8): k = 10, 15, 20
+    const bool wave = free_order && (r.k == 10 || r.k == 15 || r.k == 20) && s.W >= 2 * r.k && s.H >= 4 * r.k && s.B <= 65535 &&
+                      r.eps > 0.0;
+    if (!wave) {
+        g.TH = free_order ? guided_fast_th(s, r.k) : 0;
+        g.route = g.TH ? GF_FAST : GF_EXACT;
+        g.t0_f64 = r.t0_f64;
+        g.planes = !g.TH;
+        return g;
+    }
+    const Tuning &tu = tune();
+    int Sa, Sb;
+    g.ring_fx = r.fx && fx_scales(r.eps, &Sa, &Sb);
+    g.t_f32 = r.f32_ok && !g.ring_fx && !(s.W & 1);  // float32 t: float64 ring, paired stores
+    g.pipe_bands = pipe_bands(s, r.k, g.ring_fx, tu.gf_bands);
+    g.route = GF_PIPE;
+    if (!g.ring_fx && tu.gf_split && split_plan(s, r.k, tu.gf_bands, &g.iy0, &g.band, &g.nb, &g.rows)) {
+        g.route = GF_SPLIT;
+        // the transmission's first half (S6:170-174) evaluated inside the filter: no t0 plane
+        if (r.k == 15 && r.t0_from_frame && !r.fx && tu.gf_fuse) {
+            g.route = GF_FUSED;
+            g.t0 = false;
         }
     }
-    if (ring == 0) {
-        cs.kaI = scale / 255.0;
-        cs.kb = scale;
-        cs.b0 = 0.0;
+    return g;
+}
+
+int launch_guided_plan(const GuidedPlan &g, Shape s, const uint8_t *d_gray, const void *d_t0, double *d_t, void *ws, hipStream_t st,
+                       const FuseT0Args *frame)
+{
+    const float *t0 = static_cast<const float *>(d_t0);
+    switch (g.route) {
+    case GF_EXACT:
+        UWIE_REQUIRE(ws, "guided filter: the exact-order kernels need the workspace's planes");
+        if (g.t0_f64) return launch_guided_p64(d_gray, static_cast<const double *>(d_t0), s, g.k, g.eps, d_t, ws, st);
+        return launch_guided(d_gray, t0, s, g.k, g.eps, d_t, ws, st);
+    case GF_FAST: return launch_guided_fast(d_gray, t0, s, g.k, g.TH, g.eps, d_t, st);
+    case GF_FUSED:
+        UWIE_REQUIRE(frame, "guided filter: the fused plan computes t0 from the frame");
+        if (g.t_f32) return launch_split8<15, float>(d_gray, *frame, s, pipe_consts(g), reinterpret_cast<float *>(d_t), g.iy0, g.band, g.nb, s.H, st);
+        return launch_split8<15, double>(d_gray, *frame, s, pipe_consts(g), d_t, g.iy0, g.band, g.nb, s.H, st);
+    default:
+        if (g.t_f32) return launch_wave(g, d_gray, t0, s, reinterpret_cast<float *>(d_t), st);
+        return launch_wave(g, d_gray, t0, s, d_t, st);
     }
-    // float64: the split-ring kernels.  Tuning gf_split = 0 keeps the general kernel.
-    if (ring == 0) {
-        int iy0, band, nb, rows;
-        if (out_f32) {
-            // UWIE_INTER_F32T: the same kernels with a float32 store (q is rounded once, after the clip)
-            float *d_tf = reinterpret_cast<float *>(d_t);
-            const bool split = guided_split_plan(s, k, &iy0, &band, &nb, &rows);
-            const int border[6] = {iy0, iy0 + rows, band, 0, 0, 0};
-            int rc = UWIE_OK;
-            switch (k) {
-            case 15:
-                rc = split ? launch_split<15, float>(d_gray, d_t0, s, cs, d_tf, iy0, band, nb, s.H, st)
-                           : launch_pipe<15, false, float>(d_gray, d_t0, s, cs, d_tf, st);
-                break;
-            case 20:
-                rc = split ? launch_split<20, float>(d_gray, d_t0, s, cs, d_tf, iy0, band, nb, iy0 + rows, st)
-                           : launch_pipe<20, false, float>(d_gray, d_t0, s, cs, d_tf, st);
-                if (rc == UWIE_OK && split) rc = launch_pipe<20, false, float>(d_gray, d_t0, s, cs, d_tf, st, border);
-                break;
-            default:
-                rc = split ? launch_split<10, float>(d_gray, d_t0, s, cs, d_tf, iy0, band, nb, iy0 + rows, st)
-                           : launch_pipe<10, false, float>(d_gray, d_t0, s, cs, d_tf, st);
-                if (rc == UWIE_OK && split) rc = launch_pipe<10, false, float>(d_gray, d_t0, s, cs, d_tf, st, border);
-                break;
-            }
-            if (rc == UWIE_OK) *handled = 1;
-            return rc;
-        }
-        if (guided_split_plan(s, k, &iy0, &band, &nb, &rows)) {
-            if (k == 15) {
-                UWIE_TRY_RC((launch_split<15, double>(d_gray, d_t0, s, cs, d_t, iy0, band, nb, s.H, st)));
-            } else {
-                // even window: rows [0, iy0) and [iy0 + rows, H) around the split kernel's whole periods
-                const int border[6] = {iy0, iy0 + rows, band, 0, 0, 0};
-                if (k == 20) {
-                    UWIE_TRY_RC((launch_split<20, double>(d_gray, d_t0, s, cs, d_t, iy0, band, nb, iy0 + rows, st)));
-                    UWIE_TRY_RC((launch_pipe<20, false, double>(d_gray, d_t0, s, cs, d_t, st, border)));
-                } else {
-                    UWIE_TRY_RC((launch_split<10, double>(d_gray, d_t0, s, cs, d_t, iy0, band, nb, iy0 + rows, st)));
-                    UWIE_TRY_RC((launch_pipe<10, false, double>(d_gray, d_t0, s, cs, d_t, st, border)));
-                }
-            }
-            *handled = 1;
-            return UWIE_OK;
-        }
-    }
-    int rc;
-#define UWIE_PIPE_CASE(KK)                                                                                   \
-    case KK:                                                                                                 \
-        rc = ring == 1 ? launch_pipe<KK, true, double>(d_gray, d_t0, s, cs, d_t, st)                         \
-                       : launch_pipe<KK, false, double>(d_gray, d_t0, s, cs, d_t, st);                       \
-        break;
-    switch (k) {
-        UWIE_PIPE_CASE(10)
-        UWIE_PIPE_CASE(15)
-        UWIE_PIPE_CASE(20)
-    default: return UWIE_OK;
-    }
-#undef UWIE_PIPE_CASE
-    if (rc == UWIE_OK) *handled = 1;
-    return rc;
 }
 
 }  // namespace uwie

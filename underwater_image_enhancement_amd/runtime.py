@@ -89,7 +89,7 @@ class Device:
 
     # ------------------------------------------------------------------ route selectors (uwie_set_tuning)
     def tune(self, **selectors):
-        """Set route selectors of this context (include/uwie.h: gf_pipe, gf_split, gf_bands, select_generic, restore_store,
+        """Set route selectors of this context (include/uwie.h: gf_split, gf_bands, select_generic, restore_store,
         lin_predict3, lin_cap, lin_no_predict, lin_predict_shift, q_hist, streams, canny_prepass, entry_fuse ...).  The selection / storage / quadtree
         selectors give the same bytes on every route, the gf_* ones the same transmission to 1e-11 (uwie.h); tests force the
         fallback routes with it."""
