@@ -309,6 +309,42 @@ int uwie_diff_gated_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_pa
                             void *d_workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * ReferenceLoss (deep_learning_parameters.py:170-196) and the L1 / MSE terms of CombinedLoss (vgg_16_UIE.py:272-303) on a
+ * module's output o and a reference r (the contract: DESIGN.md section 13): d_loss [2] float32 = {l1, l2} =
+ * {mean|o - r|, mean((o - r)^2)} over all N = batch * 3 * H * W values (torch's 'mean' reduction).  The float32 terms are
+ * summed in float64 in a fixed order, without atomics, and rounded once: the same inputs give the same bits on every run.
+ * The caller forms w1 * l1 + w2 * l2 on the device.  map:
+ *   UWIE_LOSS_IDENTITY  o = d_img, any layout; d_params, flags, d_out and d_saved are not read (NULL).
+ *   UWIE_LOSS_VGG       o = uwie_diff_enhance_f32 of (d_img, d_params, flags): d_out (NULL: not written) gets its bytes,
+ *                       d_saved (required) what uwie_diff_enhance_save_f32 leaves there.
+ *   UWIE_LOSS_GATED     o = uwie_diff_gated_f32 of (d_img, d_params), the same way (flags: 0).  An image without a valid
+ *                       sorted position sets UWIE_STATUS_DIFF_RANK and makes both values NaN.
+ * d_ref: float32 in d_img's layout.  Workspace: uwie_ref_loss_workspace_bytes(batch, H, W).
+ *   uwie_ref_loss_bwd_f32: the gradient of g1 * l1 + g2 * l2 (+ <d_grad_out, o>), with d_grad_loss [2] = {g1, g2} read on the
+ *     device (no host sync).  dL/do follows torch's autograd formulas in their order (MeanBackward0 -> AbsBackward0 with
+ *     sgn(0) = 0, MseLossBackward0, their sum, then d_grad_out when given), then the module's backward exactly as
+ *     uwie_diff_enhance_bwd_f32 / uwie_diff_gated_bwd_f32 with that gradient as grad_out.  The same arguments as the forward
+ *     (d_saved: the forward's); identity: d_grad_img (required) = dL/do; otherwise d_grad_img (NULL: skipped) and
+ *     d_grad_params (required) as in those entry points.  d_grad_img must not alias d_img, d_ref or d_grad_out.
+ */
+#define UWIE_LOSS_IDENTITY 0
+#define UWIE_LOSS_VGG 1
+#define UWIE_LOSS_GATED 2
+size_t uwie_ref_loss_workspace_bytes(int batch, int H, int W);
+int uwie_ref_loss_f32(uwie_ctx *ctx, int map, const float *d_img, const float *d_params, int flags, int planar, int batch, int H,
+                      int W, const float *d_ref, float *d_out, float *d_saved, float *d_loss, void *d_workspace,
+                      size_t workspace_bytes, void *stream);
+int uwie_ref_loss_bwd_f32(uwie_ctx *ctx, int map, const float *d_img, const float *d_params, int flags, int planar, int batch,
+                          int H, int W, const float *d_saved, const float *d_ref, const float *d_grad_out,
+                          const float *d_grad_loss, float *d_grad_img, float *d_grad_params, void *d_workspace,
+                          size_t workspace_bytes, void *stream);
+/*
+ * uwie_device_status without the wait: enqueues on `stream` a copy of the status word to d_bits (device memory, one uint32)
+ * and clears the word, so that a caller can bring it back together with its own results in one copy.
+ */
+int uwie_device_status_async(uwie_ctx *ctx, uint32_t *d_bits, void *stream);
+
+/*
  * vgg_16_UIE.extract_all_features (vgg_16_UIE.py:435-466) for uint8 frames: d_features [batch][79] float32 =
  * {mean, std, min, max, median} of each channel of img = u8/255, then mean(img), std(img), mean(img**2), zeros.
  * NumPy float32 arithmetic (pairwise sums over 8192-element buffers) reproduced bit for bit.

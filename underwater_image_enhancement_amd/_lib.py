@@ -12,6 +12,7 @@ CSRC = os.path.join(_HERE, "csrc")
 SURFACE_SIX, SURFACE_DICT = 0, 1
 STATUS_DIFF_RANK = 16  # include/uwie.h UWIE_STATUS_DIFF_RANK
 STATUS_CLASSIFY_NAN = 64  # include/uwie.h UWIE_STATUS_CLASSIFY_NAN
+LOSS_IDENTITY, LOSS_VGG, LOSS_GATED = 0, 1, 2  # include/uwie.h UWIE_LOSS_*
 FLIP_LR, FLIP_UD = 1, 2  # include/uwie.h UWIE_FLIP_LR, UWIE_FLIP_UD
 RESIZE_MAX_SIDE, RESIZE_MAX_SRC = 4096, 32768  # include/uwie.h UWIE_RESIZE_MAX_SIDE, UWIE_RESIZE_MAX_SRC
 INTER_F64, INTER_FX32, INTER_F32T = 0, 1, 2  # uwie_params.inter_dtype
@@ -110,6 +111,10 @@ SIGNATURES = {
     "uwie_diff_gated_save_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _SZ, _VP],
     "uwie_diff_gated_bwd_workspace_bytes": [_I, _I, _I],
     "uwie_diff_gated_bwd_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP],
+    "uwie_ref_loss_workspace_bytes": [_I, _I, _I],
+    "uwie_ref_loss_f32": [_VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP],
+    "uwie_ref_loss_bwd_f32": [_VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP],
+    "uwie_device_status_async": [_VP, _VP, _VP],
     "uwie_extract_features_u8": [_VP, _VP, _VP, _I, _I, _I, _VP, _SZ, _VP],
     "uwie_feature_extractor_count": [_I, _I],
     "uwie_workspace_bytes_feature_extractor": [_I, _I, _I],
@@ -153,6 +158,7 @@ _RESTYPES = {
     "uwie_workspace_bytes_select": ctypes.c_size_t,
     "uwie_diff_enhance_bwd_workspace_bytes": ctypes.c_size_t,
     "uwie_diff_gated_bwd_workspace_bytes": ctypes.c_size_t,
+    "uwie_ref_loss_workspace_bytes": ctypes.c_size_t,
     "uwie_workspace_bytes_feature_extractor": ctypes.c_size_t,
     "uwie_workspace_bytes_predict": ctypes.c_size_t,
     "uwie_model_destroy": None,

@@ -621,6 +621,16 @@ int uwie_device_status(uwie_ctx *ctx, void *stream, uint32_t *bits)
     return UWIE_OK;
 }
 
+int uwie_device_status_async(uwie_ctx *ctx, uint32_t *d_bits, void *stream)
+{
+    UWIE_REQUIRE(ctx && d_bits, "device_status_async: NULL pointer");
+    UWIE_SCOPE(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    UWIE_HIP_CHECK(hipMemcpyAsync(d_bits, ctx->d_status, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    UWIE_HIP_CHECK(hipMemsetAsync(ctx->d_status, 0, sizeof(uint32_t), st));
+    return UWIE_OK;
+}
+
 int uwie_profile_enable(uwie_ctx *ctx, int on)
 {
     UWIE_REQUIRE(ctx != nullptr, "profile_enable: NULL context");
@@ -1171,6 +1181,83 @@ int uwie_diff_gated_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_pa
     UWIE_CHECK_WS(diff_enhance_bwd_ws_bytes(s));
     return launch_diff_gated_bwd(d_img, planar ? 1 : 0, s, d_params, d_saved, d_grad_out, d_grad_img, d_grad_params, d_workspace,
                                  (hipStream_t)stream);
+}
+
+// ReferenceLoss: the forward workspace holds the selection and the loss partials; the backward's is the module backward's
+static size_t ref_loss_fwd_ws_bytes(Shape s)
+{
+    Carver c(nullptr);
+    c.take<char>(select_ws_bytes(s));
+    c.take<char>(refloss_ws_bytes(s));
+    return c.total();
+}
+
+size_t uwie_ref_loss_workspace_bytes(int batch, int H, int W)
+{
+    if (!shape_ok(batch, H, W)) return 0;
+    const Shape s{batch, H, W};
+    return std::max(ref_loss_fwd_ws_bytes(s), diff_enhance_bwd_ws_bytes(s));
+}
+
+static int ref_loss_check_map(int map, const float *d_params, const float *d_saved, int flags)
+{
+    UWIE_REQUIRE(map == UWIE_LOSS_IDENTITY || map == UWIE_LOSS_VGG || map == UWIE_LOSS_GATED,
+                 "ref_loss: map is UWIE_LOSS_IDENTITY, UWIE_LOSS_VGG or UWIE_LOSS_GATED");
+    if (map == UWIE_LOSS_IDENTITY) return UWIE_OK;
+    UWIE_REQUIRE(d_params && d_saved, "ref_loss: NULL pointer (d_params, d_saved)");
+    if (map == UWIE_LOSS_VGG) UWIE_REQUIRE((flags & ~3) == 0, "ref_loss: vgg flags are UWIE_DIFF_OMEGA | UWIE_DIFF_GAMMA");
+    else UWIE_REQUIRE(flags == 0, "ref_loss: gated flags are reserved (0)");
+    return UWIE_OK;
+}
+
+int uwie_ref_loss_f32(uwie_ctx *ctx, int map, const float *d_img, const float *d_params, int flags, int planar, int batch, int H,
+                      int W, const float *d_ref, float *d_out, float *d_saved, float *d_loss, void *d_workspace,
+                      size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE(ctx && d_img && d_ref && d_loss, "ref_loss: NULL pointer");
+    UWIE_TRY(ref_loss_check_map(map, d_params, d_saved, flags));
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_REQUIRE((const void *)d_out != (const void *)d_img && (const void *)d_out != (const void *)d_ref,
+                 "ref_loss: d_out must not alias d_img or d_ref");
+    const Shape s{batch, H, W};
+    UWIE_CHECK_WS(ref_loss_fwd_ws_bytes(s));
+    UWIE_SCOPE(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    Carver c(d_workspace);
+    void *sel_ws = c.take<char>(select_ws_bytes(s));
+    void *loss_ws = c.take<char>(refloss_ws_bytes(s));
+    const float *os = nullptr;
+    if (map != UWIE_LOSS_IDENTITY) {
+        SelectPlan plan;
+        if (map == UWIE_LOSS_VGG) UWIE_TRY(select_begin_stretch_ranks(s, d_params, 4, sel_ws, st, &plan));
+        else UWIE_TRY(select_begin_gated_ranks(s, d_params, 4, ctx->d_status, sel_ws, st, &plan));
+        UWIE_TRY(select_run(plan, d_img, planar ? 1 : 0, s, false, st));
+        os = (const float *)plan.os;
+    } else {
+        d_out = nullptr;
+        d_saved = nullptr;
+    }
+    return launch_refloss(map, d_img, planar ? 1 : 0, s, d_params, flags, os, d_ref, d_out, d_saved, d_loss, loss_ws, st);
+}
+
+int uwie_ref_loss_bwd_f32(uwie_ctx *ctx, int map, const float *d_img, const float *d_params, int flags, int planar, int batch,
+                          int H, int W, const float *d_saved, const float *d_ref, const float *d_grad_out,
+                          const float *d_grad_loss, float *d_grad_img, float *d_grad_params, void *d_workspace,
+                          size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE(ctx && d_img && d_ref && d_grad_loss, "ref_loss_bwd: NULL pointer");
+    UWIE_TRY(ref_loss_check_map(map, d_params, d_saved, flags));
+    UWIE_REQUIRE(map == UWIE_LOSS_IDENTITY ? d_grad_img != nullptr : d_grad_params != nullptr,
+                 "ref_loss_bwd: NULL pointer (identity: d_grad_img; vgg / gated: d_grad_params)");
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_REQUIRE(!d_grad_img || ((const void *)d_grad_img != (const void *)d_img && (const void *)d_grad_img != (const void *)d_ref &&
+                                 (const void *)d_grad_img != (const void *)d_grad_out),
+                 "ref_loss_bwd: d_grad_img must not alias d_img, d_ref or d_grad_out");
+    const Shape s{batch, H, W};
+    if (map != UWIE_LOSS_IDENTITY) UWIE_CHECK_WS(diff_enhance_bwd_ws_bytes(s));
+    UWIE_SCOPE(ctx);
+    return launch_refloss_bwd(map, d_img, planar ? 1 : 0, s, d_params, flags, d_saved, d_ref, d_grad_out, d_grad_loss, d_grad_img,
+                              d_grad_params, d_workspace, (hipStream_t)stream);
 }
 
 int uwie_extract_features_u8(uwie_ctx *ctx, const uint8_t *d_in, float *d_features, int batch, int H, int W,

@@ -421,6 +421,15 @@ int launch_diff_gated(const float *d_img, int planar, Shape s, const float *d_pa
                       hipStream_t st, float *d_saved = nullptr);
 int launch_diff_gated_bwd(const float *d_img, int planar, Shape s, const float *d_params, const float *d_saved,
                           const float *d_grad_out, float *d_grad_img, float *d_grad_params, void *ws, hipStream_t st);
+// k_diffenh.hip: ReferenceLoss (l1 = mean|o - r|, l2 = mean((o - r)^2)) fused into the module sweeps; map = UWIE_LOSS_*.
+// Forward: after the selection (d_os; not read for the identity map), writes d_loss [2] and optionally d_out / d_saved.
+// Backward: the module's backward with the loss gradient (d_grad_loss [2] on the device) in place of grad_out.
+size_t refloss_ws_bytes(Shape s);
+int launch_refloss(int map, const float *d_img, int planar, Shape s, const float *d_params, int flags, const float *d_os,
+                   const float *d_ref, float *d_out, float *d_saved, float *d_loss, void *ws, hipStream_t st);
+int launch_refloss_bwd(int map, const float *d_img, int planar, Shape s, const float *d_params, int flags, const float *d_saved,
+                       const float *d_ref, const float *d_grad_out, const float *d_grad_loss, float *d_grad_img,
+                       float *d_grad_params, void *ws, hipStream_t st);
 // float64 data (ES surface): first digit = f64_key(v) >> 53
 int select_begin64(Shape s, const double *q_percent, int nq, void *ws, hipStream_t st, SelectPlan *plan);
 int select_run64(const SelectPlan &plan, const double *d_vals, int planar, Shape s, bool pass1_done, hipStream_t st);

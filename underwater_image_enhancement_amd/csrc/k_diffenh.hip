@@ -28,6 +28,36 @@ namespace {
 
 __device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
 
+// The per-pixel forwards, shared by the inference kernels and the loss sweep (k_refloss_*): the clamp masks of the loss
+// backward recompute these values, so both must see the same bits.
+// vgg: v = clamp(stretch -> [dehaze] -> [gamma]) of one pixel's three channels (flags: UWIE_DIFF_OMEGA | UWIE_DIFF_GAMMA)
+__device__ __forceinline__ void vgg_px(const float (&x)[3], const float (&lo)[3], const float (&rng)[3], float omega, float gamma,
+                                       int flags, float (&v)[3])
+{
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = clamp01((x[c] - lo[c]) / rng[c]);
+    if (flags & 1) {
+        const float dark = fminf(fminf(v[0], v[1]), v[2]);
+        const float t = fminf(fmaxf(1.0f - omega * dark, 0.1f), 1.0f);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = clamp01((v[c] - 0.6f) / t + 0.6f);
+    }
+    if (flags & 2) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = pow_f32_fast(v[c] + 1e-8f, gamma);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = clamp01(v[c]);
+}
+
+// gated: one channel value; ok = false (no valid sorted position) gives NaN
+__device__ __forceinline__ float gated_px(float x, float lo, float rng, float u, float e, float om, bool ok)
+{
+    const float sv = clamp01((x - lo) / rng);
+    const float z = pow_f32_fast(sv + 1e-8f, e);
+    return ok ? clamp01(u * z + om * sv) : __builtin_nanf("");
+}
+
 // planar: img/out [B][3][n];  interleaved: [B][n][3].  os: [B*3][kSelOsStride] floats, entries 0/1 = p_low, p_high.
 __global__ void __launch_bounds__(256) k_diff_enhance(const float *__restrict__ img, int planar, int n,
                                                       const float *__restrict__ params, int flags,
@@ -50,27 +80,14 @@ __global__ void __launch_bounds__(256) k_diff_enhance(const float *__restrict__ 
     const float omega = pr[2], gamma = pr[3];
     const size_t base = (size_t)b * 3 * n;
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
-        float v[3];
+        float x[3], y[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) x[c] = planar ? img[base + (size_t)c * n + p] : img[base + (size_t)p * 3 + c];
+        vgg_px(x, lo, rng, omega, gamma, flags, y);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const float x = planar ? img[base + (size_t)c * n + p] : img[base + (size_t)p * 3 + c];
-            v[c] = clamp01((x - lo[c]) / rng[c]);
-        }
-        if (flags & 1) {
-            const float dark = fminf(fminf(v[0], v[1]), v[2]);
-            const float t = fminf(fmaxf(1.0f - omega * dark, 0.1f), 1.0f);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[c] = clamp01((v[c] - 0.6f) / t + 0.6f);
-        }
-        if (flags & 2) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[c] = pow_f32_fast(v[c] + 1e-8f, gamma);
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float y = clamp01(v[c]);
-            if (planar) out[base + (size_t)c * n + p] = y;
-            else out[base + (size_t)p * 3 + c] = y;
+            if (planar) out[base + (size_t)c * n + p] = y[c];
+            else out[base + (size_t)p * 3 + c] = y[c];
         }
     }
 }
@@ -102,9 +119,7 @@ __global__ void __launch_bounds__(256) k_diff_gated(const float *__restrict__ im
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const size_t i = planar ? base + (size_t)c * n + p : base + (size_t)p * 3 + c;
-            const float sv = clamp01((img[i] - lo[c]) / rng[c]);
-            const float z = pow_f32_fast(sv + 1e-8f, e);
-            out[i] = ok ? clamp01(u * z + om * sv) : __builtin_nanf("");
+            out[i] = gated_px(img[i], lo[c], rng[c], u, e, om, ok);
         }
     }
 }
@@ -116,6 +131,28 @@ __device__ __forceinline__ long long stretch_rank(float L, int n)
     if (!(pos > 0.0)) return 0;
     if (pos >= (double)(n - 1)) return n - 1;
     return (long long)pos;
+}
+
+// dL/d(out) of w1 * mean|out - ref| + w2 * mean((out - ref)^2) in torch's autograd order, given
+// g1 = dL/dl1, g2 = dL/dl2 (device scalars, read by every thread: no host sync):
+//   MeanBackward0 -> AbsBackward0: (g1 / N) * sgn(d), sgn(0) = sgn(NaN) = 0;  MseLossBackward0: ((2 / N) * d) * g2;  their sum.
+// nf = (float)N and norm = (float)(2.0 / N) as torch converts them; an upstream gradient on out (gout) is added last.
+struct LossGrad {
+    const float *gl;  // {g1, g2}
+    float nf, norm;
+};
+// the per-thread constants: q1 = g1 / N, norm, g2
+struct LossK {
+    float q1, norm, g2;
+};
+__device__ __forceinline__ LossK loss_k(const LossGrad &lg) { return LossK{lg.gl[0] / lg.nf, lg.norm, lg.gl[1]}; }
+
+__device__ __forceinline__ float refloss_grad(const LossK &k, float o, float r, const float *__restrict__ gout, size_t i)
+{
+    const float d = o - r;
+    const float sg = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
+    const float g = k.q1 * sg + (k.norm * d) * k.g2;
+    return gout ? gout[i] + g : g;
 }
 
 // Per-block partials: kPartD float64 sums and kPartU counts per (image, block).
@@ -159,11 +196,14 @@ __device__ __forceinline__ void store_partials(const double (&v)[kPartD], const 
 // Every pointwise term follows torch's backward formulas in operation order (clamp: pass where lo <= v <= hi; a / b:
 // grad / b and -grad * ((a / b) / b); min(dim): the first minimal channel; pow: grad * (g * y^(g - 1)) and
 // grad * (z * log(y))).  y^(g - 1) is z / y in float64, rounded once (z: the forward's pow, <= 1 ulp).
-template <int FLAGS>
-__global__ void __launch_bounds__(256) k_diff_enhance_bwd(const float *__restrict__ img, int planar, int n, int chunk,
-                                                          const float *__restrict__ params, const float *__restrict__ saved,
-                                                          const float *__restrict__ gout, float *__restrict__ gimg,
-                                                          double *__restrict__ part, uint32_t *__restrict__ cnt)
+// LOSS (k_refloss_bwd): g = (gout ? gout[i] : 0) + dL/d(out) of the reference loss, from out recomputed here and ref[i]
+// (refloss_grad); otherwise g = gout[i].
+template <int FLAGS, bool LOSS>
+__device__ __forceinline__ void diff_enhance_bwd_body(const float *__restrict__ img, int planar, int n, int chunk,
+                                                      const float *__restrict__ params, const float *__restrict__ saved,
+                                                      const float *__restrict__ gout, const float *__restrict__ ref,
+                                                      const LossGrad lg, float *__restrict__ gimg, double *__restrict__ part,
+                                                      uint32_t *__restrict__ cnt)
 {
     const int b = blockIdx.y;
     float lo[3], hi[3], rng[3];
@@ -174,6 +214,7 @@ __global__ void __launch_bounds__(256) k_diff_enhance_bwd(const float *__restric
         rng[c] = (hi[c] - lo[c]) + 1e-8f;
     }
     const float omega = params[b * 4 + 2], gamma = params[b * 4 + 3];
+    const LossK lk = LOSS ? loss_k(lg) : LossK{0.0f, 0.0f, 0.0f};
     double s_om = 0.0, s_ga = 0.0, s_x[3] = {0.0, 0.0, 0.0}, s_r[3] = {0.0, 0.0, 0.0};
     uint32_t k[kPartU];
 #pragma unroll
@@ -187,7 +228,8 @@ __global__ void __launch_bounds__(256) k_diff_enhance_bwd(const float *__restric
         for (int c = 0; c < 3; ++c) {
             const size_t i = planar ? base + (size_t)c * n + p : base + (size_t)p * 3 + c;
             x[c] = img[i];
-            g[c] = gout[i];
+            if (LOSS) g[c] = ref[i];  // replaced by the loss gradient once out is known
+            else g[c] = gout[i];
         }
         float s0[3], s[3];
 #pragma unroll
@@ -225,11 +267,13 @@ __global__ void __launch_bounds__(256) k_diff_enhance_bwd(const float *__restric
             if (FLAGS & 2) {
                 const float ye = y[c] + 1e-8f;
                 const float z = pow_f32_fast(ye, gamma);
+                if (LOSS) g[c] = refloss_grad(lk, clamp01(z), g[c], gout, planar ? base + (size_t)c * n + p : base + (size_t)p * 3 + c);
                 const float gz = (z >= 0.0f && z <= 1.0f) ? g[c] : 0.0f;
                 const float dz = gamma * (float)((double)z / (double)ye);
                 gy[c] = gamma == 0.0f ? 0.0f : gz * dz;
                 s_ga += (double)(gz * (z * logf(ye)));
             } else {
+                if (LOSS) g[c] = refloss_grad(lk, clamp01(y[c]), g[c], gout, planar ? base + (size_t)c * n + p : base + (size_t)p * 3 + c);
                 gy[c] = (y[c] >= 0.0f && y[c] <= 1.0f) ? g[c] : 0.0f;
             }
         }
@@ -268,15 +312,27 @@ __global__ void __launch_bounds__(256) k_diff_enhance_bwd(const float *__restric
     store_partials(v, k, part, cnt);
 }
 
+template <int FLAGS>
+__global__ void __launch_bounds__(256) k_diff_enhance_bwd(const float *__restrict__ img, int planar, int n, int chunk,
+                                                          const float *__restrict__ params, const float *__restrict__ saved,
+                                                          const float *__restrict__ gout, float *__restrict__ gimg,
+                                                          double *__restrict__ part, uint32_t *__restrict__ cnt)
+{
+    diff_enhance_bwd_body<FLAGS, false>(img, planar, n, chunk, params, saved, gout, nullptr, LossGrad{}, gimg, part, cnt);
+}
+
 // The gated module's backward sweep (same chunks, partials and counts as k_diff_enhance_bwd).  torch's graph, with v the
 // input of the final clamp and g its gradient after the clamp's mask: d use_gamma = g * z - g * s (MulBackward0 and
 // RsubBackward1), dz = g * use_gamma, d e = dz * (z * log(s + 1e-8)), ds = g * (1 - use_gamma) + dz * (e * (s + 1e-8)^(e - 1))
 // with (s + 1e-8)^(e - 1) = z / (s + 1e-8) in float64, rounded once.  d gamma = -d e * (r * r) (r = 1 / gamma) is formed
 // in the finish kernel.
-__global__ void __launch_bounds__(256) k_diff_gated_bwd(const float *__restrict__ img, int planar, int n, int chunk,
-                                                        const float *__restrict__ params, const float *__restrict__ saved,
-                                                        const float *__restrict__ gout, float *__restrict__ gimg,
-                                                        double *__restrict__ part, uint32_t *__restrict__ cnt)
+// LOSS: g as in diff_enhance_bwd_body, with out = the forward's value (gated_px).
+template <bool LOSS>
+__device__ __forceinline__ void diff_gated_bwd_body(const float *__restrict__ img, int planar, int n, int chunk,
+                                                    const float *__restrict__ params, const float *__restrict__ saved,
+                                                    const float *__restrict__ gout, const float *__restrict__ ref,
+                                                    const LossGrad lg, float *__restrict__ gimg, double *__restrict__ part,
+                                                    uint32_t *__restrict__ cnt)
 {
     const int b = blockIdx.y;
     float lo[3], hi[3], rng[3];
@@ -290,6 +346,7 @@ __global__ void __launch_bounds__(256) k_diff_gated_bwd(const float *__restrict_
     const bool ok0 = gated_rank(params[b * 4 + 0], n, &k0), ok1 = gated_rank(params[b * 4 + 1], n, &k1);
     const bool ok = ok0 && ok1;
     const float u = params[b * 4 + 2], e = 1.0f / params[b * 4 + 3], om = 1.0f - u;
+    const LossK lk = LOSS ? loss_k(lg) : LossK{0.0f, 0.0f, 0.0f};
     double s_u = 0.0, s_e = 0.0, s_x[3] = {0.0, 0.0, 0.0}, s_r[3] = {0.0, 0.0, 0.0};
     uint32_t k[kPartU];
 #pragma unroll
@@ -301,7 +358,8 @@ __global__ void __launch_bounds__(256) k_diff_gated_bwd(const float *__restrict_
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const size_t i = planar ? base + (size_t)c * n + p : base + (size_t)p * 3 + c;
-            const float x = img[i], g = gout[i];
+            const float x = img[i];
+            float g = LOSS ? 0.0f : gout[i];
             k[c * 4 + 0] += x < lo[c];
             k[c * 4 + 1] += x == lo[c];
             k[c * 4 + 2] += x < hi[c];
@@ -311,6 +369,8 @@ __global__ void __launch_bounds__(256) k_diff_gated_bwd(const float *__restrict_
             const float ye = sv + 1e-8f;
             const float z = pow_f32_fast(ye, e);
             const float v = u * z + om * sv;
+            // out = gated_px's value; an image without a valid position (!ok) gets NaN gradients below whatever g is
+            if (LOSS) g = refloss_grad(lk, clamp01(v), ref[i], gout, i);
             const float gv = (v >= 0.0f && v <= 1.0f) ? g : 0.0f;
             s_u += (double)(gv * z) - (double)(gv * sv);
             const float gz = gv * u;
@@ -327,6 +387,34 @@ __global__ void __launch_bounds__(256) k_diff_gated_bwd(const float *__restrict_
     }
     const double v[kPartD] = {s_u, s_e, s_x[0], s_x[1], s_x[2], s_r[0], s_r[1], s_r[2]};
     store_partials(v, k, part, cnt);
+}
+
+__global__ void __launch_bounds__(256) k_diff_gated_bwd(const float *__restrict__ img, int planar, int n, int chunk,
+                                                        const float *__restrict__ params, const float *__restrict__ saved,
+                                                        const float *__restrict__ gout, float *__restrict__ gimg,
+                                                        double *__restrict__ part, uint32_t *__restrict__ cnt)
+{
+    diff_gated_bwd_body<false>(img, planar, n, chunk, params, saved, gout, nullptr, LossGrad{}, gimg, part, cnt);
+}
+
+// The backward sweeps with the reference loss's gradient in place of grad_out (k_refloss_*'s forward values)
+template <int FLAGS>
+__global__ void __launch_bounds__(256) k_diff_enhance_loss_bwd(const float *__restrict__ img, int planar, int n, int chunk,
+                                                               const float *__restrict__ params, const float *__restrict__ saved,
+                                                               const float *__restrict__ gout, const float *__restrict__ ref,
+                                                               const LossGrad lg, float *__restrict__ gimg,
+                                                               double *__restrict__ part, uint32_t *__restrict__ cnt)
+{
+    diff_enhance_bwd_body<FLAGS, true>(img, planar, n, chunk, params, saved, gout, ref, lg, gimg, part, cnt);
+}
+
+__global__ void __launch_bounds__(256) k_diff_gated_loss_bwd(const float *__restrict__ img, int planar, int n, int chunk,
+                                                             const float *__restrict__ params, const float *__restrict__ saved,
+                                                             const float *__restrict__ gout, const float *__restrict__ ref,
+                                                             const LossGrad lg, float *__restrict__ gimg,
+                                                             double *__restrict__ part, uint32_t *__restrict__ cnt)
+{
+    diff_gated_bwd_body<true>(img, planar, n, chunk, params, saved, gout, ref, lg, gimg, part, cnt);
 }
 
 // One block per (plane c, image b): the plane's partials in block order, then the element each order statistic's gradient
@@ -470,6 +558,146 @@ __global__ void __launch_bounds__(256) k_diff_enhance_bwd_finish(const float *__
     }
 }
 
+// ------------------------------------------------------------------ ReferenceLoss
+// l1 = mean|o - r|, l2 = mean((o - r)^2) of the module's output o and a reference r, fused into the forward (k_refloss_identity / _vgg / _gated): o is formed in
+// registers (vgg_px / gated_px, the inference kernels' bits) and written only when asked.  The float32 terms |d| and d * d
+// are summed in float64: per thread, then store_partials' fixed wave / block order, then k_refloss_finish.
+enum { kMapIdentity = 0, kMapVgg = 1, kMapGated = 2 };  // UWIE_LOSS_*
+constexpr int kLossPart = 2;                              // per-block float64 partials: sum |d|, sum d * d
+
+template <int MAP, int FLAGS>
+__device__ __forceinline__ void refloss_fwd_body(const float *__restrict__ img, int planar, int n, int chunk,
+                                                 const float *__restrict__ params, const float *__restrict__ os,
+                                                 const float *__restrict__ ref, float *__restrict__ out, float *__restrict__ saved,
+                                                 double *__restrict__ part)
+{
+    const int b = blockIdx.y;
+    float lo[3] = {0.0f, 0.0f, 0.0f}, rng[3] = {1.0f, 1.0f, 1.0f};
+    float a0 = 0.0f, a1 = 0.0f, om = 0.0f;  // vgg: omega, gamma; gated: use_gamma, 1 / gamma, 1 - use_gamma
+    bool ok = true;
+    if (MAP != kMapIdentity) {
+        if (saved && blockIdx.x == 0 && threadIdx.x < 6) {  // as the _save_f32 forwards leave it
+            const int c = threadIdx.x >> 1, q = threadIdx.x & 1;
+            saved[(b * 3 + c) * 2 + q] = os[(size_t)(b * 3 + c) * kSelOsStride + q];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float *o = os + (size_t)(b * 3 + c) * kSelOsStride;
+            lo[c] = o[0];
+            rng[c] = (o[1] - o[0]) + 1e-8f;
+        }
+        const float *pr = params + b * 4;
+        if (MAP == kMapVgg) {
+            a0 = pr[2];
+            a1 = pr[3];
+        } else {
+            int k0, k1;
+            const bool ok0 = gated_rank(pr[0], n, &k0), ok1 = gated_rank(pr[1], n, &k1);
+            ok = ok0 && ok1;
+            a0 = pr[2];
+            a1 = 1.0f / pr[3];
+            om = 1.0f - a0;
+        }
+    }
+    double s1 = 0.0, s2 = 0.0;
+    const size_t base = (size_t)b * 3 * n;
+    const int p0 = blockIdx.x * chunk;
+    const int p1 = min(p0 + chunk, n);
+    for (int p = p0 + (int)threadIdx.x; p < p1; p += 256) {
+        size_t i[3];
+        float x[3], o[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            i[c] = planar ? base + (size_t)c * n + p : base + (size_t)p * 3 + c;
+            x[c] = img[i[c]];
+        }
+        if (MAP == kMapVgg) {
+            vgg_px(x, lo, rng, a0, a1, FLAGS, o);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[c] = MAP == kMapGated ? gated_px(x[c], lo[c], rng[c], a0, a1, om, ok) : x[c];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float d = o[c] - ref[i[c]];
+            s1 += (double)fabsf(d);
+            s2 += (double)(d * d);
+            if (MAP != kMapIdentity && out) out[i[c]] = o[c];
+        }
+    }
+    // the block's totals: wave sums, then the four waves in order (store_partials' order)
+    __shared__ double sd[4][kLossPart];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s1 += __shfl_xor(s1, o);
+        s2 += __shfl_xor(s2, o);
+    }
+    if (lane == 0) {
+        sd[wid][0] = s1;
+        sd[wid][1] = s2;
+    }
+    __syncthreads();
+    if (threadIdx.x < kLossPart) {
+        const int q = threadIdx.x;
+        part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kLossPart + q] = ((sd[0][q] + sd[1][q]) + sd[2][q]) + sd[3][q];
+    }
+}
+
+#define UWIE_REFLOSS_FWD_ARGS                                                                                            \
+    const float *__restrict__ img, int planar, int n, int chunk, const float *__restrict__ params, const float *__restrict__ os, \
+        const float *__restrict__ ref, float *__restrict__ out, float *__restrict__ saved, double *__restrict__ part
+// the three maps: identity (o = img), the vgg module (flags), the gated module
+__global__ void __launch_bounds__(256) k_refloss_identity(UWIE_REFLOSS_FWD_ARGS)
+{
+    refloss_fwd_body<kMapIdentity, 0>(img, planar, n, chunk, params, os, ref, out, saved, part);
+}
+template <int FLAGS>
+__global__ void __launch_bounds__(256) k_refloss_vgg(UWIE_REFLOSS_FWD_ARGS)
+{
+    refloss_fwd_body<kMapVgg, FLAGS>(img, planar, n, chunk, params, os, ref, out, saved, part);
+}
+__global__ void __launch_bounds__(256) k_refloss_gated(UWIE_REFLOSS_FWD_ARGS)
+{
+    refloss_fwd_body<kMapGated, 0>(img, planar, n, chunk, params, os, ref, out, saved, part);
+}
+#undef UWIE_REFLOSS_FWD_ARGS
+
+// One block: slot j of the nslots per-block partials goes to thread j % 256 (in slot order), then a fixed LDS tree.
+// loss[0] = (float)(sum |d| / N), loss[1] = (float)(sum d * d / N): one rounding each.
+__global__ void __launch_bounds__(256) k_refloss_finish(const double *__restrict__ part, int nslots, double count,
+                                                        float *__restrict__ loss)
+{
+    __shared__ double rd[kLossPart][256];
+    const int tid = threadIdx.x;
+    double v0 = 0.0, v1 = 0.0;
+    for (int j = tid; j < nslots; j += 256) {
+        v0 += part[(size_t)j * kLossPart];
+        v1 += part[(size_t)j * kLossPart + 1];
+    }
+    rd[0][tid] = v0;
+    rd[1][tid] = v1;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) {
+            rd[0][tid] += rd[0][tid + w];
+            rd[1][tid] += rd[1][tid + w];
+        }
+        __syncthreads();
+    }
+    if (tid < kLossPart) loss[tid] = (float)(rd[tid][0] / count);
+}
+
+// The identity map's gradient: grad[i] = (gout ? gout[i] : 0) + dL/do[i], elementwise over all N = B * 3 * n values
+__global__ void __launch_bounds__(256) k_refloss_identity_bwd(const float *__restrict__ o, const float *__restrict__ ref,
+                                                              const float *__restrict__ gout, const LossGrad lg, size_t total,
+                                                              float *__restrict__ grad)
+{
+    const LossK lk = loss_k(lg);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        grad[i] = refloss_grad(lk, o[i], ref[i], gout, i);
+}
+
 // pixels per block of the backward sweep and the cap on blocks per image (the partials' size)
 constexpr int kBwdPxPerBlock = 2048, kBwdMaxBlocks = 512;
 struct BwdGeom {
@@ -550,6 +778,85 @@ int launch_diff_gated_bwd(const float *d_img, int planar, Shape s, const float *
     UWIE_LAUNCH_CHECK();
     UWIE_LAUNCH(k_diff_enhance_bwd_finish<true>, dim3(3, s.B), dim3(256), 0, st, d_img, planar, n, g.chunk, g.gx, d_params,
                 d_saved, part, cnt, d_grad_img, d_grad_params);
+    UWIE_LAUNCH_CHECK();
+    return UWIE_OK;
+}
+
+// ------------------------------------------------------------------ ReferenceLoss launchers
+size_t refloss_ws_bytes(Shape s)
+{
+    const BwdGeom g = bwd_geom(s);
+    Carver c(nullptr);
+    c.take<double>((size_t)s.B * g.gx * kLossPart);
+    return c.total();
+}
+
+static LossGrad loss_grad_args(Shape s, const float *d_grad_loss)
+{
+    const long long N = (long long)s.B * 3 * (long long)s.npx();
+    return LossGrad{d_grad_loss, (float)N, (float)(2.0 / (double)N)};
+}
+
+int launch_refloss(int map, const float *d_img, int planar, Shape s, const float *d_params, int flags, const float *d_os,
+                   const float *d_ref, float *d_out, float *d_saved, float *d_loss, void *ws, hipStream_t st)
+{
+    const int n = (int)s.npx();
+    const BwdGeom g = bwd_geom(s);
+    Carver c(ws);
+    double *part = c.take<double>((size_t)s.B * g.gx * kLossPart);
+    const dim3 grid(g.gx, s.B);
+#define UWIE_REFLOSS_FWD(K) UWIE_LAUNCH(K, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_os, d_ref, d_out, d_saved, part)
+    if (map == kMapIdentity) UWIE_REFLOSS_FWD(k_refloss_identity);
+    else if (map == kMapGated) UWIE_REFLOSS_FWD(k_refloss_gated);
+    else switch (flags & 3) {
+        case 0: UWIE_REFLOSS_FWD(k_refloss_vgg<0>); break;
+        case 1: UWIE_REFLOSS_FWD(k_refloss_vgg<1>); break;
+        case 2: UWIE_REFLOSS_FWD(k_refloss_vgg<2>); break;
+        default: UWIE_REFLOSS_FWD(k_refloss_vgg<3>); break;
+        }
+#undef UWIE_REFLOSS_FWD
+    UWIE_LAUNCH_CHECK();
+    const double count = (double)s.B * 3.0 * (double)s.npx();
+    UWIE_LAUNCH(k_refloss_finish, dim3(1), dim3(256), 0, st, (const double *)part, s.B * g.gx, count, d_loss);
+    UWIE_LAUNCH_CHECK();
+    return UWIE_OK;
+}
+
+int launch_refloss_bwd(int map, const float *d_img, int planar, Shape s, const float *d_params, int flags, const float *d_saved,
+                       const float *d_ref, const float *d_grad_out, const float *d_grad_loss, float *d_grad_img,
+                       float *d_grad_params, void *ws, hipStream_t st)
+{
+    const LossGrad lg = loss_grad_args(s, d_grad_loss);
+    if (map == kMapIdentity) {
+        const size_t total = (size_t)s.B * 3 * s.npx();
+        UWIE_LAUNCH(k_refloss_identity_bwd, dim3(grid_for(total)), dim3(256), 0, st, d_img, d_ref, d_grad_out, lg, total, d_grad_img);
+        UWIE_LAUNCH_CHECK();
+        return UWIE_OK;
+    }
+    const int n = (int)s.npx();
+    const BwdGeom g = bwd_geom(s);
+    Carver c(ws);
+    double *part = c.take<double>((size_t)s.B * g.gx * kPartD);
+    uint32_t *cnt = c.take<uint32_t>((size_t)s.B * g.gx * kPartU);
+    const dim3 grid(g.gx, s.B);
+    if (map == kMapGated) {
+        UWIE_LAUNCH(k_diff_gated_loss_bwd, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_ref, lg,
+                    d_grad_img, part, cnt);
+    } else {
+        switch (flags & 3) {
+        case 0: UWIE_LAUNCH(k_diff_enhance_loss_bwd<0>, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_ref, lg, d_grad_img, part, cnt); break;
+        case 1: UWIE_LAUNCH(k_diff_enhance_loss_bwd<1>, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_ref, lg, d_grad_img, part, cnt); break;
+        case 2: UWIE_LAUNCH(k_diff_enhance_loss_bwd<2>, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_ref, lg, d_grad_img, part, cnt); break;
+        default: UWIE_LAUNCH(k_diff_enhance_loss_bwd<3>, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_ref, lg, d_grad_img, part, cnt); break;
+        }
+    }
+    UWIE_LAUNCH_CHECK();
+    if (map == kMapGated)
+        UWIE_LAUNCH(k_diff_enhance_bwd_finish<true>, dim3(3, s.B), dim3(256), 0, st, d_img, planar, n, g.chunk, g.gx, d_params,
+                    d_saved, part, cnt, d_grad_img, d_grad_params);
+    else
+        UWIE_LAUNCH(k_diff_enhance_bwd_finish<false>, dim3(3, s.B), dim3(256), 0, st, d_img, planar, n, g.chunk, g.gx, d_params,
+                    d_saved, part, cnt, d_grad_img, d_grad_params);
     UWIE_LAUNCH_CHECK();
     return UWIE_OK;
 }

@@ -327,6 +327,54 @@ class Device:
                                                self.stream()))
         return grad_img, grad_params
 
+    # ------------------------------------------------------------------ ReferenceLoss (uwie_ref_loss_*)
+    def ref_loss_f32(self, map_: int, img, params, ref, planar: bool, flags: int = 0, want_out: bool = False,
+                     status: bool = False):
+        """l1, l2 of o (map_: _lib.LOSS_IDENTITY: o = img; LOSS_VGG / LOSS_GATED: the module's output of img, params) against
+        ref.  Returns (out or None, saved float32 [B,3,2] or None (identity), buf float32 [4]): buf[0], buf[1] = l1, l2 and,
+        with ``status``, buf[2] = the device status word (uwie_device_status_async, cleared on the device) as uint32 bits, so
+        that one copy brings back all three."""
+        assert img.dtype == torch.float32 and ref.dtype == torch.float32 and img.dim() == 4
+        assert tuple(ref.shape) == tuple(img.shape)
+        B = img.shape[0]
+        H, W = (img.shape[2], img.shape[3]) if planar else (img.shape[1], img.shape[2])
+        assert img.shape[1 if planar else 3] == 3
+        img, ref = img.contiguous(), ref.contiguous()
+        ws = self.workspace(self.lib.uwie_ref_loss_workspace_bytes(B, H, W))
+        buf = self.empty((4,), torch.float32)
+        out = saved = None
+        if map_ != _lib.LOSS_IDENTITY:
+            assert params.dtype == torch.float32 and tuple(params.shape) == (B, 4)
+            params = params.contiguous()
+            saved = self.empty((B, 3, 2), torch.float32)
+            out = self.empty(tuple(img.shape), torch.float32) if want_out else None
+        check(self.lib.uwie_ref_loss_f32(self._ctx, int(map_), _ptr(img), _ptr(params), int(flags), int(planar), B, H, W, _ptr(ref),
+                                         _ptr(out), _ptr(saved), _ptr(buf), _ptr(ws), ws.numel(), self.stream()))
+        if status:
+            check(self.lib.uwie_device_status_async(self._ctx, ctypes.c_void_p(buf.data_ptr() + 8), self.stream()))
+        return out, saved, buf
+
+    def ref_loss_bwd_f32(self, map_: int, img, params, saved, ref, grad_loss, planar: bool, flags: int = 0, grad_out=None,
+                         want_img: bool = True):
+        """Gradient of ref_loss_f32 given grad_loss float32 [2] = dL/dl1, dL/dl2 on the device (and grad_out = dL/d(out) when
+        the output was kept and used): (grad_img or None, grad_params float32 [B,4] or None for the identity map)."""
+        B = img.shape[0]
+        H, W = (img.shape[2], img.shape[3]) if planar else (img.shape[1], img.shape[2])
+        img, ref, grad_loss = img.contiguous(), ref.contiguous(), grad_loss.contiguous()
+        assert grad_loss.dtype == torch.float32 and grad_loss.numel() == 2
+        if grad_out is not None:
+            assert grad_out.dtype == torch.float32 and tuple(grad_out.shape) == tuple(img.shape)
+            grad_out = grad_out.contiguous()
+        identity = map_ == _lib.LOSS_IDENTITY
+        ws = self.workspace(self.lib.uwie_ref_loss_workspace_bytes(B, H, W))
+        grad_img = self.empty(tuple(img.shape), torch.float32) if want_img or identity else None
+        grad_params = None if identity else self.empty((B, 4), torch.float32)
+        check(self.lib.uwie_ref_loss_bwd_f32(self._ctx, int(map_), _ptr(img), _ptr(None if identity else params.contiguous()),
+                                             int(flags), int(planar), B, H, W, _ptr(saved), _ptr(ref), _ptr(grad_out),
+                                             _ptr(grad_loss), _ptr(grad_img), _ptr(grad_params), _ptr(ws), ws.numel(),
+                                             self.stream()))
+        return grad_img, grad_params
+
     def extract_features_u8(self, frames):
         """frames: uint8 cuda tensor [B,H,W,3] -> float32 [B,79] (vgg_16_UIE.extract_all_features per frame)."""
         B, H, W = self._bhw(frames)
