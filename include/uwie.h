@@ -345,6 +345,33 @@ int uwie_ref_loss_bwd_f32(uwie_ctx *ctx, int map, const float *d_img, const floa
 int uwie_device_status_async(uwie_ctx *ctx, uint32_t *d_bits, void *stream);
 
 /*
+ * PerceptualLoss (vgg_16_UIE.py:257-269; the contract: DESIGN.md section 14): d_loss [1] float32 =
+ * mse_loss(F(pred), F(target)) with F = torchvision vgg16().features[:16] (conv1_1 ... relu3_3).  d_pred, d_target:
+ * float32 (batch, 3, H, W), H and W >= 4 (both max-pools non-empty).  precision:
+ *   UWIE_VGG_F32  float32 throughout (torch's float32 module, free summation order inside each convolution)
+ *   UWIE_VGG_F16  torch.autocast's float16 contract: inputs, weights and biases rounded to float16, each convolution
+ *                 accumulates in float32 and rounds its output (after the bias) to float16, ReLU and max-pool on float16,
+ *                 the loss in float32; the backward rounds dL/dF and every data-gradient to float16 and returns float32.
+ * The loss sums float32 terms in float64 in a fixed order (no atomics) and rounds once: the same inputs give the same bits.
+ * uwie_vgg_create packs torchvision's 14 tensors, float32 on the device, flat in features.N order (weight then bias of
+ * convs 0, 2, 5, 7, 10, 12, 14; UWIE_VGG_PARAMS floats in all) into a handle of one precision; d_params is not kept.
+ * uwie_perceptual_f32 keeps what the backward needs in the workspace (uwie_perceptual_workspace_bytes): the workspace must
+ * stay untouched until the last uwie_perceptual_bwd_f32 of that forward, which gives d_grad_pred (float32, d_pred's shape)
+ * = g * dloss/dpred with g = d_grad_loss[0] read on the device (no host sync).  target gets no gradient.
+ */
+#define UWIE_VGG_F32 0
+#define UWIE_VGG_F16 1
+#define UWIE_VGG_PARAMS 1735488
+typedef struct uwie_vgg uwie_vgg;
+int uwie_vgg_create(uwie_ctx *ctx, const float *d_params, int precision, uwie_vgg **out_vgg);
+void uwie_vgg_destroy(uwie_vgg *vgg);
+size_t uwie_perceptual_workspace_bytes(int batch, int H, int W, int precision);
+int uwie_perceptual_f32(uwie_ctx *ctx, const uwie_vgg *vgg, const float *d_pred, const float *d_target, int batch, int H, int W,
+                        float *d_loss, void *d_workspace, size_t workspace_bytes, void *stream);
+int uwie_perceptual_bwd_f32(uwie_ctx *ctx, const uwie_vgg *vgg, int batch, int H, int W, const float *d_grad_loss, float *d_grad_pred,
+                            void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
  * vgg_16_UIE.extract_all_features (vgg_16_UIE.py:435-466) for uint8 frames: d_features [batch][79] float32 =
  * {mean, std, min, max, median} of each channel of img = u8/255, then mean(img), std(img), mean(img**2), zeros.
  * NumPy float32 arithmetic (pairwise sums over 8192-element buffers) reproduced bit for bit.

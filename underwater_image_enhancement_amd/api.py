@@ -21,6 +21,8 @@ process is never reported as a successful pass-through.
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 
@@ -596,10 +598,11 @@ def _module_loss(module, images, params, references, keep_out: bool, status: boo
     raise TypeError(f"expected a DifferentiableEnhancement or GatedDifferentiableEnhancement, got {type(module).__name__}")
 
 
-def _read_loss(dev: Device, buf, x=None, pt=None):
+def _read_loss(dev: Device, buf, x=None, pt=None, extra=None):
     """The one host read of a fused call: buf = {l1, l2, status bits} -> (l1, l2) as Python floats.  A flagged sorted position
-    raises the reference's exception (first), any other status bit UwieError."""
-    host = buf[:3].cpu()
+    raises the reference's exception (first), any other status bit UwieError.  ``extra`` (a device float32 [1], e.g. the
+    perceptual loss) comes back in the same copy, as a third value."""
+    host = (buf[:3] if extra is None else torch.cat([buf[:3], extra.reshape(1)])).cpu()
     bits = int(host[2:3].view(torch.int32).item()) & 0xFFFFFFFF
     if bits & _lib.STATUS_DIFF_RANK and pt is not None:
         _raise_rank_error(pt[:, :2].detach().cpu().numpy(), x.shape[2] * x.shape[3])
@@ -607,6 +610,8 @@ def _read_loss(dev: Device, buf, x=None, pt=None):
     if bits:
         raise _lib.UwieError(f"device status 0x{bits:x}: the results of the calls since the last check are not valid "
                              "(include/uwie.h UWIE_STATUS_*)")
+    if extra is not None:
+        return float(host[0]), float(host[1]), float(host[3])
     return float(host[0]), float(host[1])
 
 
@@ -670,6 +675,226 @@ class ReferenceLoss(torch.nn.Module):
         dev, (l1, l2), x, pt = _module_loss(module, images, params, references, False, True, sink)
         v1, v2 = _read_loss(dev, sink[0], x, pt if isinstance(module, GatedDifferentiableEnhancement) else None)
         return self.l1_weight * l1 + self.l2_weight * l2, {"l1": v1, "l2": v2}
+
+
+# ------------------------------------------------------------------ PerceptualLoss / CombinedLoss (vgg_16_UIE.py:257-303, N10)
+VGG16_CHECKPOINT = "vgg16-397923af.pth"  # torchvision's file name for vgg16(pretrained=True)
+_VGG_CONVS = ((0, 3, 64), (2, 64, 64), (5, 64, 128), (7, 128, 128), (10, 128, 256), (12, 256, 256), (14, 256, 256))
+
+
+def _vgg_tensors(weights):
+    """The 14 float32 CPU tensors of vgg16().features[:16] (weight, bias of convs 0, 2, 5, 7, 10, 12, 14) from ``weights``: a
+    state dict with keys ``N.weight`` / ``N.bias`` or ``features.N.weight`` / ..., a path to one (torch.load,
+    weights_only=True), or None: torchvision's cached checkpoint under torch.hub.get_dir()/checkpoints (never downloaded)."""
+    if weights is None:
+        path = os.path.join(torch.hub.get_dir(), "checkpoints", VGG16_CHECKPOINT)
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"no VGG16 weights at {path} (pass weights=, or place torchvision's {VGG16_CHECKPOINT} "
+                                    "there; nothing is downloaded)")
+        weights = path
+    if isinstance(weights, (str, os.PathLike)):
+        weights = torch.load(weights, map_location="cpu", weights_only=True)
+    out = []
+    for i, cin, cout in _VGG_CONVS:
+        for name, shape in (("weight", (cout, cin, 3, 3)), ("bias", (cout,))):
+            key = f"{i}.{name}"
+            if key not in weights:
+                key = f"features.{i}.{name}"
+            if key not in weights:
+                raise ValueError(f"VGG16 weights: missing key '{i}.{name}' (or 'features.{i}.{name}')")
+            t = torch.as_tensor(weights[key])
+            if tuple(t.shape) != shape:
+                raise ValueError(f"VGG16 weights: '{key}' has shape {tuple(t.shape)}, expected {shape}")
+            out.append(t.detach().to(device="cpu", dtype=torch.float32).contiguous())
+    return out
+
+
+def vgg16_features16(weights=None) -> torch.nn.Sequential:
+    """torchvision's ``vgg16().features[:16]`` (conv1_1 ... relu3_3) in plain torch.nn, frozen, in eval mode, on the CPU:
+    the module PerceptualLoss computes and falls back to.  ``weights`` as in PerceptualLoss."""
+    nn = torch.nn
+    tensors = _vgg_tensors(weights)
+    layers = []
+    for i, cin, cout in _VGG_CONVS:
+        if i in (5, 10):
+            layers.append(nn.MaxPool2d(kernel_size=2, stride=2, padding=0, dilation=1, ceil_mode=False))
+        layers += [nn.Conv2d(cin, cout, kernel_size=3, padding=1), nn.ReLU(inplace=True)]
+    seq = nn.Sequential(*layers)
+    with torch.no_grad():
+        for k, (i, _, _) in enumerate(_VGG_CONVS):
+            seq[i].weight.copy_(tensors[2 * k])
+            seq[i].bias.copy_(tensors[2 * k + 1])
+    for p in seq.parameters():
+        p.requires_grad = False
+    return seq.eval()
+
+
+class PerceptualFunction(torch.autograd.Function):
+    """``loss = PerceptualFunction.apply(pred, target, crit, dev, precision, sink)``: mse_loss(F(pred), F(target)) on the
+    device (uwie_perceptual_f32), 0-dim float32; ``pred`` gets the gradient, ``target`` none.  ``sink`` (a list or None)
+    receives the device buffer {loss}.  The device status word is left as it is (the kernels set no bit)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, crit, dev, precision, sink=None):
+        h = crit._handle(dev, precision)
+        buf, ws = dev.perceptual_f32(h, precision, pred, target)
+        ctx.dev, ctx.crit, ctx.handle, ctx.ws, ctx.shape = dev, crit, h, ws, tuple(pred.shape)
+        if sink is not None:
+            sink.append(buf)
+        return buf[0]
+
+    @staticmethod
+    def backward(ctx, grad):
+        if grad is None or not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        return (ctx.dev.perceptual_bwd_f32(ctx.handle, ctx.shape, ctx.ws, grad),) + (None,) * 5
+
+
+class PerceptualLoss(torch.nn.Module):
+    """``vgg_16_UIE.PerceptualLoss`` (:257-269): ``crit(pred, target) = mse_loss(F(pred), F(target))`` with F =
+    vgg16().features[:16], a 0-dim loss with ``grad_fn``.
+
+    float32 ``(B, 3, H, W)`` ROCm tensors of one shape, with a ``target`` that does not require grad, take the device kernels
+    (k_vgg.hip): the float32 route, or inside ``torch.autocast("cuda", dtype=torch.float16)`` autocast's float16 route.  Other
+    inputs -- CPU tensors, other dtypes or shapes, a bfloat16 autocast region, a target that requires grad -- go through
+    ``vgg16_features16`` in torch.  ``H`` or ``W`` below 4 raises RuntimeError (a max-pool output would be empty), as torch
+    does.  ``weights``: a state dict (``N.weight`` or ``features.N.weight`` keys), a path, or None for torchvision's cached
+    ``vgg16-397923af.pth`` (FileNotFoundError when it is absent; nothing is downloaded).
+
+    The weights are a frozen copy, read once: they are not parameters or buffers of this module (``state_dict()``,
+    ``.to()`` and ``load_state_dict`` do not see them; make a new PerceptualLoss for other weights).  The kernels take them
+    packed per GPU and precision (uwie_vgg_create).  ``device`` (a GPU index) packs both precisions there at construction;
+    otherwise each is packed on the inputs' GPU at its first use.  Packing and ``close()`` (also run by ``__del__``)
+    synchronise that GPU: do not let either happen inside a CUDA graph capture.
+    """
+
+    def __init__(self, weights=None, device: int | None = None):
+        super().__init__()
+        self._tensors = _vgg_tensors(weights)
+        self.device = device
+        self._torch = {}
+        self._handles = {}
+        if device is not None:
+            dev = get_device(device)
+            for precision in (_lib.VGG_F32, _lib.VGG_F16):
+                self._handle(dev, precision)
+
+    def close(self):
+        for (index, _), h in list(self._handles.items()):
+            get_device(index).vgg_destroy(h)
+        self._handles.clear()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    def _handle(self, dev: Device, precision: int):
+        key = (dev.index, precision)
+        if key not in self._handles:
+            self._handles[key] = dev.vgg_create(torch.cat([t.reshape(-1) for t in self._tensors]), precision)
+        return self._handles[key]
+
+    def features(self, device=None) -> torch.nn.Sequential:
+        """The torch module of these weights (vgg16_features16) on ``device`` (default: CPU), cached."""
+        key = str(torch.device("cpu") if device is None else torch.device(device))
+        if key not in self._torch:
+            state = {f"{i}.{n}": self._tensors[2 * k + j] for k, (i, _, _) in enumerate(_VGG_CONVS) for j, n in enumerate(("weight", "bias"))}
+            self._torch[key] = vgg16_features16(state).to(key)
+        return self._torch[key]
+
+    @staticmethod
+    def _route(pred, target):
+        """_lib.VGG_F32 / VGG_F16 for inputs the kernels take, None for the torch route."""
+        if not (isinstance(pred, torch.Tensor) and isinstance(target, torch.Tensor) and pred.is_cuda and target.is_cuda
+                and pred.device == target.device and pred.dtype == torch.float32 and target.dtype == torch.float32
+                and pred.dim() == 4 and pred.shape[1] == 3 and tuple(pred.shape) == tuple(target.shape)
+                and pred.shape[0] > 0 and not target.requires_grad):
+            return None
+        if torch.is_autocast_enabled("cuda"):
+            return _lib.VGG_F16 if torch.get_autocast_dtype("cuda") == torch.float16 else None
+        return _lib.VGG_F32
+
+    @staticmethod
+    def _check_size(x):
+        H, W = int(x.shape[2]), int(x.shape[3])
+        if H < 4 or W < 4:  # torch's max_pool2d message for the pool whose output is empty
+            h, w, c = (H, W, 64) if H < 2 or W < 2 else (H // 2, W // 2, 128)
+            raise RuntimeError(f"Given input size: ({c}x{h}x{w}). Calculated output size: ({c}x{h // 2}x{w // 2}). "
+                               "Output size is too small")
+
+    def _torch_loss(self, pred, target):
+        vgg = self.features(pred.device if isinstance(pred, torch.Tensor) else None)
+        return torch.nn.functional.mse_loss(vgg(pred), vgg(target))
+
+    def _device_loss(self, pred, target, precision, sink=None):
+        self._check_size(pred)
+        dev = get_device(pred.device.index)
+        return PerceptualFunction.apply(pred.contiguous(), target.contiguous(), self, dev, precision, sink)
+
+    def forward(self, pred, target):
+        precision = self._route(pred, target)
+        if precision is None:
+            return self._torch_loss(pred, target)
+        return self._device_loss(pred, target, precision)
+
+
+class CombinedLoss(torch.nn.Module):
+    """``vgg_16_UIE.CombinedLoss`` (:272-303), ImprovedTrainer's criterion: ``total, parts = crit(enhanced, reference)`` with
+    ``total = l1_weight * L1 + l2_weight * MSE + perceptual_weight * PerceptualLoss`` and ``parts = {'l1', 'l2',
+    'perceptual'}`` as Python floats, all three from one host read on the device route (the reference makes three .item()
+    calls).  L1 and MSE take ReferenceLoss's kernels, the perceptual term PerceptualLoss's; inputs those do not take go
+    through torch as in the reference.
+
+    ``crit.through(module, images, params, references)``: the same for ``module(images, params)`` (either enhancement
+    module), with L1 / MSE fused into the module's sweeps (``module.with_loss``) and the perceptual gradient entering the
+    module's fused backward as its ``grad_out``.
+    """
+
+    def __init__(self, l1_weight=0.3, l2_weight=0.5, perceptual_weight=0.2, weights=None, device: int | None = None):
+        super().__init__()
+        self.l1_weight = l1_weight
+        self.l2_weight = l2_weight
+        self.perceptual_weight = perceptual_weight
+        self.perceptual_loss = PerceptualLoss(weights, device)
+
+    def _total(self, l1, l2, p):
+        return self.l1_weight * l1 + self.l2_weight * l2 + self.perceptual_weight * p
+
+    def forward(self, enhanced, reference):
+        precision = PerceptualLoss._route(enhanced, reference)
+        if precision is None or not ReferenceLoss._takes(enhanced, reference):
+            l1 = torch.nn.functional.l1_loss(enhanced, reference)
+            l2 = torch.nn.functional.mse_loss(enhanced, reference)
+            p = self.perceptual_loss(enhanced, reference)
+            return self._total(l1, l2, p), {"l1": l1.item(), "l2": l2.item(), "perceptual": p.item()}
+        PerceptualLoss._check_size(enhanced)
+        dev = get_device(enhanced.device.index)
+        sink = []
+        enhanced, reference = enhanced.contiguous(), reference.contiguous()
+        l1, l2 = RefLossFunction.apply(enhanced, reference, dev, sink)
+        p = self.perceptual_loss._device_loss(enhanced, reference, precision, sink)
+        host = torch.cat([sink[0][:2], sink[1][:1]]).cpu()
+        return self._total(l1, l2, p), {"l1": float(host[0]), "l2": float(host[1]), "perceptual": float(host[2])}
+
+    def through(self, module, images, params, references):
+        """``crit(module(images, params), references)`` with L1 / MSE fused into the module's step: ``(total, parts)``, one
+        host read per call (the three values and the device status together).  Errors as ``ReferenceLoss.through``."""
+        if isinstance(references, torch.Tensor) and references.requires_grad:
+            return self(module(images, params), references)
+        sink = []
+        dev, (out, l1, l2), x, pt = _module_loss(module, images, params, references, True, True, sink)
+        ref = _loss_reference(dev, x, references)
+        precision = PerceptualLoss._route(out, ref)
+        if precision is None:
+            p = self.perceptual_loss(out, ref)
+            v1, v2 = _read_loss(dev, sink[0], x, pt if isinstance(module, GatedDifferentiableEnhancement) else None)
+            return self._total(l1, l2, p), {"l1": v1, "l2": v2, "perceptual": p.item()}
+        psink = []
+        p = self.perceptual_loss._device_loss(out, ref, precision, psink)
+        v1, v2, vp = _read_loss(dev, sink[0], x, pt if isinstance(module, GatedDifferentiableEnhancement) else None, psink[0][:1])
+        return self._total(l1, l2, p), {"l1": v1, "l2": v2, "perceptual": vp}
 
 
 QUALITY_KEYS = ("contrast", "sharpness", "entropy", "saturation", "brightness", "edge_density", "colorfulness", "naturalness")

@@ -1260,6 +1260,92 @@ int uwie_ref_loss_bwd_f32(uwie_ctx *ctx, int map, const float *d_img, const floa
                               d_grad_params, d_workspace, (hipStream_t)stream);
 }
 
+// PerceptualLoss (k_vgg.hip)
+struct uwie_vgg {
+    int device;
+    VggNet net;  // device pointers into blob
+    void *blob;
+};
+
+static bool perceptual_shape_ok(int batch, int H, int W)
+{
+    return shape_ok(batch, H, W) && H >= 4 && W >= 4 && (long long)batch * H * W <= (1ll << 28);
+}
+
+int uwie_vgg_create(uwie_ctx *ctx, const float *d_params, int precision, uwie_vgg **out_vgg)
+{
+    UWIE_REQUIRE(ctx && d_params && out_vgg, "vgg_create: NULL pointer");
+    *out_vgg = nullptr;
+    UWIE_REQUIRE(precision == UWIE_VGG_F32 || precision == UWIE_VGG_F16, "vgg_create: precision is UWIE_VGG_F32 or UWIE_VGG_F16");
+    static_assert(UWIE_VGG_PARAMS > 0, "");
+    if (vgg_param_count() != (size_t)UWIE_VGG_PARAMS) {
+        set_error("vgg_create: internal parameter count %zu differs from UWIE_VGG_PARAMS", vgg_param_count());
+        return UWIE_E_INVALID;
+    }
+    UWIE_SCOPE(ctx);
+    void *blob = nullptr;
+    UWIE_HIP_CHECK(hipMalloc(&blob, vgg_blob_bytes(precision)));
+    VggNet net{};
+    int rc = vgg_pack(d_params, precision, blob, &net, nullptr);
+    hipError_t e = rc == UWIE_OK ? hipStreamSynchronize(nullptr) : hipSuccess;
+    if (rc != UWIE_OK || e != hipSuccess) {
+        (void)hipFree(blob);
+        if (e != hipSuccess) set_error("vgg_create: packing failed: %s", hipGetErrorString(e));
+        return rc != UWIE_OK ? rc : UWIE_E_HIP;
+    }
+    *out_vgg = new uwie_vgg{ctx->device, net, blob};
+    return UWIE_OK;
+}
+
+void uwie_vgg_destroy(uwie_vgg *vgg)
+{
+    if (!vgg) return;
+    int prev = -1;
+    const bool switch_dev = hipGetDevice(&prev) == hipSuccess && prev != vgg->device && hipSetDevice(vgg->device) == hipSuccess;
+    (void)hipFree(vgg->blob);
+    if (switch_dev) (void)hipSetDevice(prev);
+    delete vgg;
+}
+
+size_t uwie_perceptual_workspace_bytes(int batch, int H, int W, int precision)
+{
+    if (!perceptual_shape_ok(batch, H, W) || (precision != UWIE_VGG_F32 && precision != UWIE_VGG_F16)) return 0;
+    return perceptual_ws_bytes(Shape{batch, H, W}, precision);
+}
+
+static int perceptual_check(uwie_ctx *ctx, const uwie_vgg *vgg, int batch, int H, int W)
+{
+    UWIE_REQUIRE(vgg->device == ctx->device, "perceptual: the network lives on another device");
+    UWIE_REQUIRE(shape_ok(batch, H, W) && (long long)batch * H * W <= (1ll << 28), "perceptual: batch/H/W out of range");
+    if (H < 4 || W < 4) {
+        set_error("perceptual: H and W must be >= 4 (got %d x %d): a max-pool output would be empty", H, W);
+        return UWIE_E_INVALID;
+    }
+    return UWIE_OK;
+}
+
+int uwie_perceptual_f32(uwie_ctx *ctx, const uwie_vgg *vgg, const float *d_pred, const float *d_target, int batch, int H, int W,
+                        float *d_loss, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE(ctx && vgg && d_pred && d_target && d_loss, "perceptual: NULL pointer");
+    UWIE_TRY(perceptual_check(ctx, vgg, batch, H, W));
+    const Shape s{batch, H, W};
+    UWIE_CHECK_WS(perceptual_ws_bytes(s, vgg->net.precision));
+    UWIE_SCOPE(ctx);
+    return launch_perceptual(vgg->net, d_pred, d_target, s, d_loss, d_workspace, (hipStream_t)stream);
+}
+
+int uwie_perceptual_bwd_f32(uwie_ctx *ctx, const uwie_vgg *vgg, int batch, int H, int W, const float *d_grad_loss, float *d_grad_pred,
+                            void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE(ctx && vgg && d_grad_loss && d_grad_pred, "perceptual_bwd: NULL pointer");
+    UWIE_TRY(perceptual_check(ctx, vgg, batch, H, W));
+    const Shape s{batch, H, W};
+    UWIE_CHECK_WS(perceptual_ws_bytes(s, vgg->net.precision));
+    UWIE_SCOPE(ctx);
+    return launch_perceptual_bwd(vgg->net, s, d_grad_loss, d_grad_pred, d_workspace, (hipStream_t)stream);
+}
+
 int uwie_extract_features_u8(uwie_ctx *ctx, const uint8_t *d_in, float *d_features, int batch, int H, int W,
                              void *d_workspace, size_t workspace_bytes, void *stream)
 {

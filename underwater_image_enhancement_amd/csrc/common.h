@@ -430,6 +430,21 @@ int launch_refloss(int map, const float *d_img, int planar, Shape s, const float
 int launch_refloss_bwd(int map, const float *d_img, int planar, Shape s, const float *d_params, int flags, const float *d_saved,
                        const float *d_ref, const float *d_grad_out, const float *d_grad_loss, float *d_grad_img,
                        float *d_grad_params, void *ws, hipStream_t st);
+// k_vgg.hip: PerceptualLoss, vgg16().features[:16].  A VggNet holds the packed weights of one
+// precision (UWIE_VGG_F32 / UWIE_VGG_F16): w0 = conv1_1 [64][3][3][3] float32; for layers 1..6 wf [Cout][9][Cin] and the
+// data-gradient's rotated wb [Cin][9][Cout] in the element type; bias [Cout] float32 for all seven.
+struct VggNet {
+    int precision;
+    const float *w0;
+    const void *wf[7], *wb[7];
+    const float *bias[7];
+};
+size_t vgg_param_count();
+size_t vgg_blob_bytes(int precision);
+int vgg_pack(const float *d_params, int precision, void *blob, VggNet *net, hipStream_t st);
+size_t perceptual_ws_bytes(Shape s, int precision);
+int launch_perceptual(const VggNet &net, const float *d_pred, const float *d_target, Shape s, float *d_loss, void *ws, hipStream_t st);
+int launch_perceptual_bwd(const VggNet &net, Shape s, const float *d_grad_loss, float *d_grad_pred, void *ws, hipStream_t st);
 // float64 data (ES surface): first digit = f64_key(v) >> 53
 int select_begin64(Shape s, const double *q_percent, int nq, void *ws, hipStream_t st, SelectPlan *plan);
 int select_run64(const SelectPlan &plan, const double *d_vals, int planar, Shape s, bool pass1_done, hipStream_t st);

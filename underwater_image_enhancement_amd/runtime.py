@@ -375,6 +375,46 @@ class Device:
                                              self.stream()))
         return grad_img, grad_params
 
+    # ------------------------------------------------------------------ PerceptualLoss (uwie_perceptual_*)
+    def vgg_create(self, params, precision: int):
+        """A uwie_vgg handle of ``precision`` (_lib.VGG_F32 / VGG_F16) from torchvision's 14 tensors flattened in features.N
+        order (float32, _lib.VGG_PARAMS values).  The caller owns it (vgg_destroy)."""
+        flat = params.to(device=self.torch_device, dtype=torch.float32).contiguous()
+        assert flat.numel() == _lib.VGG_PARAMS
+        torch.cuda.synchronize(self.index)  # the packing runs on the null stream
+        h = ctypes.c_void_p()
+        check(self.lib.uwie_vgg_create(self._ctx, _ptr(flat), int(precision), ctypes.byref(h)))
+        return h
+
+    def vgg_destroy(self, handle):
+        torch.cuda.synchronize(self.index)
+        self.lib.uwie_vgg_destroy(handle)
+
+    def perceptual_f32(self, vgg, precision: int, pred, target):
+        """mse_loss(F(pred), F(target)) on the device.  Returns (buf float32 [1] = the loss, ws = this call's workspace, which
+        holds what perceptual_bwd_f32 needs: keep it untouched until then).  The perceptual kernels set no status bit, so
+        this call neither reads nor clears the device status word: bits pending from earlier calls stay for their checks."""
+        assert pred.dtype == torch.float32 and target.dtype == torch.float32 and pred.dim() == 4 and pred.shape[1] == 3
+        assert tuple(pred.shape) == tuple(target.shape)
+        B, _, H, W = (int(v) for v in pred.shape)
+        n = self.lib.uwie_perceptual_workspace_bytes(B, H, W, int(precision))
+        if n == 0:
+            raise _lib.UwieError(f"perceptual: batch/H/W out of range ({B}, {H}, {W})")
+        ws = torch.empty(int(n), dtype=torch.uint8, device=self.torch_device)
+        buf = self.empty((1,), torch.float32)
+        check(self.lib.uwie_perceptual_f32(self._ctx, vgg, _ptr(pred.contiguous()), _ptr(target.contiguous()), B, H, W, _ptr(buf),
+                                           _ptr(ws), ws.numel(), self.stream()))
+        return buf, ws
+
+    def perceptual_bwd_f32(self, vgg, shape, ws, grad_loss):
+        """dloss/dpred * grad_loss (float32 [1] on the device) from the workspace of perceptual_f32: float32 ``shape``."""
+        B, _, H, W = (int(v) for v in shape)
+        grad_loss = grad_loss.to(device=self.torch_device, dtype=torch.float32).reshape(1).contiguous()
+        out = self.empty(tuple(shape), torch.float32)
+        check(self.lib.uwie_perceptual_bwd_f32(self._ctx, vgg, B, H, W, _ptr(grad_loss), _ptr(out), _ptr(ws), ws.numel(),
+                                               self.stream()))
+        return out
+
     def extract_features_u8(self, frames):
         """frames: uint8 cuda tensor [B,H,W,3] -> float32 [B,79] (vgg_16_UIE.extract_all_features per frame)."""
         B, H, W = self._bhw(frames)
