@@ -372,6 +372,38 @@ int uwie_perceptual_bwd_f32(uwie_ctx *ctx, const uwie_vgg *vgg, int batch, int H
                             void *d_workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * ImprovedVGGParameterNet.forward in eval mode (vgg_16_UIE.py:135-255; the contract: DESIGN.md section 15), float32, no
+ * autograd: vgg16().features[:23] (conv1_1 ... relu3_3, pool3, conv4_1 ... relu4_3) -> the global average of relu4_3
+ * per (image, channel), written twice (avgpool and the reference's "maxpool", also an AdaptiveAvgPool2d) -> [the 79
+ * features] -> feature_fusion (Linear, BatchNorm1d with running statistics, ReLU; twice) -> attention product ->
+ * four heads -> sigmoid(raw) * (max - min) + min.  hidden_dim is 256.
+ * d_params: the state dict's float tensors, float32 on the device, flat in state-dict order without num_batches_tracked:
+ *   vgg_features.N.weight, .bias for N = 0, 2, 5, 7, 10, 12, 14, 17, 19, 21;
+ *   feature_fusion.0.weight [512][Din], .0.bias, .1.weight, .1.bias, .1.running_mean, .1.running_var,
+ *   feature_fusion.4.weight [256][512], .4.bias, .5.weight, .5.bias, .5.running_mean, .5.running_var;
+ *   attention.0.weight [64][256], .0.bias, attention.2.weight [256][64], .2.bias;
+ *   param_heads.K.0.weight [128][256], .0.bias, .3.weight [1][128], .3.bias for K = omega, gamma, L_low, L_high;
+ * Din = 1103 with use_features, 1024 without; UWIE_PARAM_NET_PARAMS(use_features) floats in all.  d_params is not kept.
+ * uwie_param_net_f32: d_img float32 (batch, 3, H, W), H and W >= 8 (pool3 non-empty); d_features [batch][79] (required
+ * for a use_features net, not read otherwise); d_out [batch][4] = omega, gamma, L_low, L_high; d_pooled (NULL: not
+ * written) [batch][1024], the pooled vector.  Deterministic: the same inputs give the same bits.
+ */
+#define UWIE_PARAM_NET_PARAMS(use_features) ((use_features) ? 8500100 : 8459652)
+typedef struct uwie_param_net uwie_param_net;
+int uwie_param_net_create(uwie_ctx *ctx, const float *d_params, int use_features, uwie_param_net **out_net);
+void uwie_param_net_destroy(uwie_param_net *net);
+size_t uwie_param_net_workspace_bytes(int batch, int H, int W);
+int uwie_param_net_f32(uwie_ctx *ctx, const uwie_param_net *net, const float *d_img, const float *d_features, int batch, int H, int W,
+                       float *d_out, float *d_pooled, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * u8.astype(float32) / 255.0 of n bytes in any layout (each value (float)v / 255.0f, IEEE division): the float image of
+ * EnhancementPredictor.enhance_image (use_trained_model.py:48-51) for decoded frames, kept in their [H][W][3] layout.
+ * d_in 4-byte aligned, d_out 16-byte aligned; no workspace.
+ */
+int uwie_u8_to_f32(uwie_ctx *ctx, const uint8_t *d_in, float *d_out, size_t n, void *stream);
+
+/*
  * vgg_16_UIE.extract_all_features (vgg_16_UIE.py:435-466) for uint8 frames: d_features [batch][79] float32 =
  * {mean, std, min, max, median} of each channel of img = u8/255, then mean(img), std(img), mean(img**2), zeros.
  * NumPy float32 arithmetic (pairwise sums over 8192-element buffers) reproduced bit for bit.

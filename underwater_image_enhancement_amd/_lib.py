@@ -14,6 +14,7 @@ STATUS_DIFF_RANK = 16  # include/uwie.h UWIE_STATUS_DIFF_RANK
 STATUS_CLASSIFY_NAN = 64  # include/uwie.h UWIE_STATUS_CLASSIFY_NAN
 LOSS_IDENTITY, LOSS_VGG, LOSS_GATED = 0, 1, 2  # include/uwie.h UWIE_LOSS_*
 VGG_F32, VGG_F16, VGG_PARAMS = 0, 1, 1735488  # include/uwie.h UWIE_VGG_F32, UWIE_VGG_F16, UWIE_VGG_PARAMS
+PARAM_NET_PARAMS = {True: 8500100, False: 8459652}  # include/uwie.h UWIE_PARAM_NET_PARAMS(use_features)
 FLIP_LR, FLIP_UD = 1, 2  # include/uwie.h UWIE_FLIP_LR, UWIE_FLIP_UD
 RESIZE_MAX_SIDE, RESIZE_MAX_SRC = 4096, 32768  # include/uwie.h UWIE_RESIZE_MAX_SIDE, UWIE_RESIZE_MAX_SRC
 INTER_F64, INTER_FX32, INTER_F32T = 0, 1, 2  # uwie_params.inter_dtype
@@ -121,6 +122,11 @@ SIGNATURES = {
     "uwie_perceptual_workspace_bytes": [_I, _I, _I, _I],
     "uwie_perceptual_f32": [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _SZ, _VP],
     "uwie_perceptual_bwd_f32": [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _SZ, _VP],
+    "uwie_param_net_create": [_VP, _VP, _I, ctypes.POINTER(_VP)],
+    "uwie_param_net_destroy": [_VP],
+    "uwie_param_net_workspace_bytes": [_I, _I, _I],
+    "uwie_param_net_f32": [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _SZ, _VP],
+    "uwie_u8_to_f32": [_VP, _VP, _VP, _SZ, _VP],
     "uwie_extract_features_u8": [_VP, _VP, _VP, _I, _I, _I, _VP, _SZ, _VP],
     "uwie_feature_extractor_count": [_I, _I],
     "uwie_workspace_bytes_feature_extractor": [_I, _I, _I],
@@ -170,6 +176,8 @@ _RESTYPES = {
     "uwie_model_destroy": None,
     "uwie_perceptual_workspace_bytes": ctypes.c_size_t,
     "uwie_vgg_destroy": None,
+    "uwie_param_net_workspace_bytes": ctypes.c_size_t,
+    "uwie_param_net_destroy": None,
 }
 
 _lib = None

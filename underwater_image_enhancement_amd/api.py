@@ -897,6 +897,310 @@ class CombinedLoss(torch.nn.Module):
         return self._total(l1, l2, p), {"l1": v1, "l2": v2, "perceptual": vp}
 
 
+# ------------------------------------------------------------------ ImprovedVGGParameterNet / EnhancementPredictor (N11)
+PARAM_KEYS = ("omega", "gamma", "L_low", "L_high")  # param_heads order (vgg_16_UIE.py:186-191)
+PARAM_RANGES = {"omega": (0.3, 0.9), "gamma": (1.0, 1.5), "L_low": (2.0, 15.0), "L_high": (60.0, 95.0)}  # :193-198
+PREDICTOR_CLIP = {"omega": (0.1, 0.9), "gamma": (0.5, 3.0), "L_low": (1.0, 30.0), "L_high": (65.0, 99.0)}  # use_trained_model.py:74-77
+_PN_CONVS = _VGG_CONVS + ((17, 256, 512), (19, 512, 512), (21, 512, 512))
+
+
+def param_net_layout(use_features: bool = True, hidden_dim: int = 256):
+    """``(key, shape)`` of every float tensor of ``ImprovedVGGParameterNet``'s state dict, in state-dict order without
+    ``num_batches_tracked``: the order ``uwie_param_net_create`` takes them in (include/uwie.h)."""
+    if hidden_dim != 256:
+        raise ValueError(f"hidden_dim={hidden_dim}: the device network is built for hidden_dim=256 (use_trained_model.py:20)")
+    h = hidden_dim
+    out = []
+    for i, cin, cout in _PN_CONVS:
+        out += [(f"vgg_features.{i}.weight", (cout, cin, 3, 3)), (f"vgg_features.{i}.bias", (cout,))]
+
+    def bn(prefix, c):
+        return [(f"{prefix}.{n}", (c,)) for n in ("weight", "bias", "running_mean", "running_var")]
+
+    out += [("feature_fusion.0.weight", (2 * h, 1024 + (79 if use_features else 0))), ("feature_fusion.0.bias", (2 * h,))]
+    out += bn("feature_fusion.1", 2 * h)
+    out += [("feature_fusion.4.weight", (h, 2 * h)), ("feature_fusion.4.bias", (h,))] + bn("feature_fusion.5", h)
+    out += [("attention.0.weight", (h // 4, h)), ("attention.0.bias", (h // 4,)), ("attention.2.weight", (h, h // 4)),
+            ("attention.2.bias", (h,))]
+    for k in PARAM_KEYS:
+        out += [(f"param_heads.{k}.0.weight", (h // 2, h)), (f"param_heads.{k}.0.bias", (h // 2,)),
+                (f"param_heads.{k}.3.weight", (1, h // 2)), (f"param_heads.{k}.3.bias", (1,))]
+    return out
+
+
+def _param_net_state(weights, use_features: bool = True, hidden_dim: int = 256):
+    """The validated float32 CPU tensors of ``param_net_layout`` from ``weights``: a state dict, a checkpoint dict holding
+    one under ``'model_state_dict'`` (use_trained_model.py:23), or a path to either (torch.load, weights_only=True)."""
+    layout = param_net_layout(use_features, hidden_dim)
+    if isinstance(weights, (str, os.PathLike)):
+        weights = torch.load(weights, map_location="cpu", weights_only=True)
+    if "model_state_dict" in weights:
+        weights = weights["model_state_dict"]
+    out = {}
+    for key, shape in layout:
+        if key not in weights:
+            raise ValueError(f"ImprovedVGGParameterNet weights: missing key '{key}'")
+        t = torch.as_tensor(weights[key])
+        if tuple(t.shape) != shape:
+            raise ValueError(f"ImprovedVGGParameterNet weights: '{key}' has shape {tuple(t.shape)}, expected {shape}")
+        out[key] = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
+    return out
+
+
+class _ParamNetTorch(torch.nn.Module):
+    """``vgg_16_UIE.ImprovedVGGParameterNet`` restated in plain torch.nn (no torchvision): the same modules under the same
+    state-dict keys, the same forward."""
+
+    def __init__(self, use_features: bool = True, hidden_dim: int = 256):
+        super().__init__()
+        nn = torch.nn
+        self.use_features = use_features
+        layers, cin = [], 3
+        for v in (64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512):
+            if v == "M":
+                layers.append(nn.MaxPool2d(kernel_size=2, stride=2, padding=0, dilation=1, ceil_mode=False))
+            else:
+                layers += [nn.Conv2d(cin, v, kernel_size=3, padding=1), nn.ReLU(inplace=True)]
+                cin = v
+        self.vgg_features = nn.Sequential(*layers)  # vgg16().features[:23]
+        self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
+        self.maxpool = nn.AdaptiveAvgPool2d((1, 1))  # sic (vgg_16_UIE.py:158)
+        h = hidden_dim
+        self.feature_fusion = nn.Sequential(nn.Linear(1024 + (79 if use_features else 0), 2 * h), nn.BatchNorm1d(2 * h),
+                                            nn.ReLU(inplace=True), nn.Dropout(0.4), nn.Linear(2 * h, h), nn.BatchNorm1d(h),
+                                            nn.ReLU(inplace=True), nn.Dropout(0.3))
+        self.attention = nn.Sequential(nn.Linear(h, h // 4), nn.ReLU(inplace=True), nn.Linear(h // 4, h), nn.Sigmoid())
+        self.param_heads = nn.ModuleDict({k: nn.Sequential(nn.Linear(h, h // 2), nn.ReLU(inplace=True), nn.Dropout(0.2),
+                                                           nn.Linear(h // 2, 1)) for k in PARAM_KEYS})
+        self.param_ranges = dict(PARAM_RANGES)
+
+    def forward(self, img_tensor, feature_tensor=None, return_pooled: bool = False):
+        B = img_tensor.size(0)
+        vgg_feat = self.vgg_features(img_tensor)
+        pooled = torch.cat([self.avgpool(vgg_feat).view(B, -1), self.maxpool(vgg_feat).view(B, -1)], dim=1)
+        combined = pooled
+        if self.use_features and feature_tensor is not None:
+            if isinstance(feature_tensor, list):
+                feature_tensor = torch.stack(feature_tensor)
+            combined = torch.cat([pooled, feature_tensor.float().to(img_tensor.device)], dim=1)
+        fused = self.feature_fusion(combined)
+        fused = fused * self.attention(fused)
+        params = {}
+        for name, head in self.param_heads.items():
+            lo, hi = self.param_ranges[name]
+            params[name] = torch.sigmoid(head(fused)) * (hi - lo) + lo
+        if return_pooled:
+            params["pooled"] = pooled
+        return params
+
+
+def param_net_torch(weights, use_features: bool = True, hidden_dim: int = 256) -> torch.nn.Module:
+    """``ImprovedVGGParameterNet`` with ``weights`` in plain torch.nn, frozen, in eval mode, on the CPU: the module
+    ``VGGParameterNet`` falls back to.  ``weights`` as in VGGParameterNet."""
+    state = _param_net_state(weights, use_features, hidden_dim)
+    net = _ParamNetTorch(use_features, hidden_dim)
+    missing, unexpected = net.load_state_dict(state, strict=False)
+    assert not unexpected and all(k.endswith("num_batches_tracked") for k in missing)
+    for p in net.parameters():
+        p.requires_grad = False
+    return net.eval()
+
+
+class VGGParameterNet:
+    """``vgg_16_UIE.ImprovedVGGParameterNet`` (:135-255) in eval mode on the device: ``net(img_tensor, feature_tensor)``
+    returns the reference's dict of four ``(B, 1)`` float32 tensors (``omega``, ``gamma``, ``L_low``, ``L_high``);
+    ``return_pooled=True`` adds ``'pooled'``, the ``[B, 1024]`` vector after the two global poolings.
+
+    ``weights``: a state dict, a checkpoint dict with ``'model_state_dict'`` (use_trained_model.py:23), or a path to either
+    (``torch.load(weights_only=True)``).  A missing key or a wrong shape is a ValueError naming the key; ``hidden_dim`` other
+    than 256 is a ValueError.  float32 ``(B, 3, H, W)`` ROCm tensors outside an autocast region take the kernels (k_vgg.hip,
+    k_param_net.hip); CPU tensors, other dtypes and autocast regions go through ``param_net_torch``.  ``H`` or ``W`` below
+    8 raises RuntimeError (pool3's output would be empty), as torch does.  A ``use_features`` net called without features
+    raises RuntimeError, as the reference's Linear does.  Inference only: the device route carries no gradient.
+
+    The weights are a frozen copy, packed once per GPU (uwie_param_net_create; ``device`` packs at construction).  Packing
+    and ``close()`` (also run by ``__del__``) synchronise that GPU."""
+
+    def __init__(self, weights, use_features: bool = True, device: int | None = None, hidden_dim: int = 256):
+        self.use_features = bool(use_features)
+        self._state = _param_net_state(weights, self.use_features, hidden_dim)
+        self.device = device
+        self._torch = {}
+        self._handles = {}
+        if device is not None:
+            self._handle(get_device(device))
+
+    def close(self):
+        for index, h in list(self._handles.items()):
+            get_device(index).param_net_destroy(h)
+        self._handles.clear()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    def state_dict(self):
+        return dict(self._state)
+
+    def _handle(self, dev: Device):
+        if dev.index not in self._handles:
+            flat = torch.cat([t.reshape(-1) for t in self._state.values()])
+            self._handles[dev.index] = dev.param_net_create(flat, self.use_features)
+        return self._handles[dev.index]
+
+    def torch_module(self, device=None) -> torch.nn.Module:
+        """The torch module of these weights (param_net_torch) on ``device`` (default: CPU), cached."""
+        key = str(torch.device("cpu") if device is None else torch.device(device))
+        if key not in self._torch:
+            self._torch[key] = param_net_torch(self._state, self.use_features).to(key)
+        return self._torch[key]
+
+    @staticmethod
+    def _takes(img) -> bool:
+        return (isinstance(img, torch.Tensor) and img.is_cuda and img.dtype == torch.float32 and img.dim() == 4
+                and img.shape[1] == 3 and img.shape[0] > 0 and not torch.is_autocast_enabled("cuda"))
+
+    @staticmethod
+    def _check_size(img):
+        H, W = int(img.shape[2]), int(img.shape[3])
+        if H < 8 or W < 8:  # torch's max_pool2d message for the pool whose output is empty
+            c, h, w = ((64, H, W) if H < 2 or W < 2 else (128, H // 2, W // 2) if H < 4 or W < 4 else (256, H // 4, W // 4))
+            raise RuntimeError(f"Given input size: ({c}x{h}x{w}). Calculated output size: ({c}x{h // 2}x{w // 2}). "
+                               "Output size is too small")
+
+    def _device_forward(self, dev: Device, img, features, want_pooled: bool = False):
+        """(float32 [B,4], pooled or None) on ``dev`` for a float32 [B,3,H,W] ``img`` there and float32 [B,79] ``features``."""
+        self._check_size(img)
+        feats = None
+        if self.use_features:
+            if features is None:
+                raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({img.shape[0]}x1024 and 1103x512): this "
+                                   "network was built with use_features=True and needs the 79 features")
+            if isinstance(features, list):
+                features = torch.stack(features)
+            feats = features.to(device=dev.torch_device, dtype=torch.float32)
+            if tuple(feats.shape) != (img.shape[0], 79):
+                raise RuntimeError(f"features: expected ({img.shape[0]}, 79), got {tuple(feats.shape)}")
+        return dev.param_net_f32(self._handle(dev), img.contiguous(), feats, want_pooled)
+
+    def forward(self, img_tensor, feature_tensor=None, return_pooled: bool = False):
+        if not self._takes(img_tensor):
+            dev = img_tensor.device if isinstance(img_tensor, torch.Tensor) else None
+            return self.torch_module(dev)(img_tensor, feature_tensor, return_pooled=return_pooled)
+        dev = get_device(img_tensor.device.index)
+        out, pooled = self._device_forward(dev, img_tensor, feature_tensor, return_pooled)
+        params = {k: out[:, i:i + 1] for i, k in enumerate(PARAM_KEYS)}
+        if return_pooled:
+            params["pooled"] = pooled
+        return params
+
+    __call__ = forward
+
+
+class EnhancementPredictor:
+    """``use_trained_model.EnhancementPredictor`` (:13-111) on the device, without torchvision or cv2: the network is
+    ``VGGParameterNet`` (use_features=True), the VGG input ``vgg_input``, the features ``extract_all_features``, the
+    enhancement ``DifferentiableEnhancement``.
+
+    Images are uint8 RGB frames, or float32 / float64 images equal to ``u8.astype(dtype) / 255`` in their own dtype (what
+    ``process_single_image`` makes, and NumPy's ``frame / 255``); any other float image raises ``UnsupportedInputError``.
+    For such an image every step of the reference sees the frame's own values: ``(img * 255).astype(uint8)`` gives the
+    frame back, and its float32 cast is ``u8.astype(float32) / 255`` for both dtypes.  ``predict_parameters(img)`` returns the reference's dict of six
+    Python floats (clamped as :70-79); for a ``[B,H,W,3]`` batch, one float64 array per key.  ``enhance_image(img, params)``
+    returns float32 HxWx3, clipped to [0, 1] with NaN and infinities replaced as :101-111.  ``enhance_batch(frames)`` runs
+    the whole chain for a batch as one device pipeline (no host read between the stages) and returns ``[B,H,W,3]`` float32
+    on the device, equal to B ``enhance_image`` calls bit for bit."""
+
+    def __init__(self, weights, input_size: int = 224, device: int | None = None):
+        self.input_size = int(input_size)
+        self.device = device
+        self.model = VGGParameterNet(weights, use_features=True, device=device)
+        self.enhancer = DifferentiableEnhancement()
+        self.enhancer.device = device
+
+    @staticmethod
+    def _frame_u8(img):
+        """The uint8 frame(s) behind ``img``: a uint8 array or tensor as it is, a float32 / float64 image equal to
+        ``u8.astype(dtype) / 255`` as ``(img * 255).astype(uint8)`` (_preprocess_for_vgg's quantisation,
+        use_trained_model.py:41)."""
+        if isinstance(img, torch.Tensor) and img.dtype == torch.uint8:
+            return img
+        x = img.detach().cpu().numpy() if isinstance(img, torch.Tensor) else np.asarray(img)
+        if x.dtype == np.uint8:
+            return x
+        if x.dtype not in (np.float32, np.float64):
+            if x.dtype.kind == "f":
+                raise UnsupportedInputError(f"EnhancementPredictor takes float32 or float64 images, got {x.dtype}")
+            raise TypeError(f"expected uint8 frames or float images u8 / 255, got {x.dtype}")
+        k = x.dtype.type(255)
+        with np.errstate(invalid="ignore"):
+            u8 = (x * k).astype(np.uint8)
+        if not np.array_equal(u8.astype(x.dtype) / k, x):
+            raise UnsupportedInputError("EnhancementPredictor takes uint8 frames or float images that are exactly u8 / 255")
+        return u8
+
+    @classmethod
+    def _frames(cls, img, dev: Device):
+        """(uint8 [B,H,W,3] on ``dev``, single) from a frame or a batch, uint8 or exactly u8 / 255."""
+        batch, _, single = _as_batch_u8(cls._frame_u8(img), dev)
+        return batch, single
+
+    def _raw(self, dev: Device, u8):
+        """The network's float32 [B,4] (omega, gamma, L_low, L_high) for uint8 frames on the device."""
+        _, _, x = dev.resize_rgb(u8, self.input_size, self.input_size, want_u8=False, want_f32=False,
+                                 norm=(IMAGENET_MEAN, IMAGENET_STD))
+        feats = dev.extract_features_u8(u8)
+        return self.model._device_forward(dev, x, feats)[0]
+
+    def _clamped(self, dev: Device, u8):
+        """float32 [B,4] (omega, gamma, L_low, L_high) on the device = float32(np.clip(float(v), lo, hi)) of the network's
+        outputs: the reference's float64 clip (:74-77), then the float32 tensor of enhance_image (:96-103).  NaN stays NaN."""
+        raw = self._raw(dev, u8).double()
+        lo = torch.tensor([PREDICTOR_CLIP[k][0] for k in PARAM_KEYS], dtype=torch.float64, device=dev.torch_device)
+        hi = torch.tensor([PREDICTOR_CLIP[k][1] for k in PARAM_KEYS], dtype=torch.float64, device=dev.torch_device)
+        return torch.minimum(torch.maximum(raw, lo), hi).float()
+
+    @staticmethod
+    def _enhance(dev: Device, u8, cols):
+        """DifferentiableEnhancement of u8 / 255 ([B,H,W,3] float32) with float32 [B,4] = L_low, L_high, omega, gamma."""
+        return dev.diff_enhance_f32(dev.u8_to_f32(u8), cols, planar=False)
+
+    def predict_parameters(self, img):
+        dev = get_device(self.device)
+        u8, single = self._frames(img, dev)
+        raw = self._raw(dev, u8).double().cpu().numpy()
+        dev.check_status()
+        params = {}
+        for i, k in enumerate(PARAM_KEYS):
+            lo, hi = PREDICTOR_CLIP[k]
+            params[k] = np.clip(raw[:, i], lo, hi)  # float(np.clip(float(v), lo, hi)), elementwise
+        params["guided_radius"] = np.full(raw.shape[0], 15.0)
+        params["use_gamma"] = np.full(raw.shape[0], 1.0)
+        return {k: float(v[0]) for k, v in params.items()} if single else params
+
+    def enhance_image(self, img, params=None):
+        dev = get_device(self.device)
+        u8, single = self._frames(img, dev)
+        if not single:
+            raise ValueError(f"enhance_image takes one HxWx3 image, got {tuple(u8.shape)} (enhance_batch takes batches)")
+        if params is None:
+            params = self.predict_parameters(img)
+        cols = dev.tensor(np.array([[params["L_low"], params["L_high"], params["omega"], params["gamma"]]], np.float32))
+        out = np.clip(self._enhance(dev, u8, cols)[0].cpu().numpy(), 0.0, 1.0)
+        if not np.isfinite(out).all():
+            out = np.clip(np.nan_to_num(out, nan=0.0, posinf=1.0, neginf=0.0), 0.0, 1.0)
+        return out
+
+    def enhance_batch(self, frames):
+        dev = get_device(self.device)
+        u8, _ = self._frames(frames, dev)
+        clipped = self._clamped(dev, u8)
+        out = self._enhance(dev, u8, clipped[:, [2, 3, 0, 1]].contiguous()).clamp_(0.0, 1.0)
+        return torch.nan_to_num_(out, nan=0.0, posinf=1.0, neginf=0.0).clamp_(0.0, 1.0)
+
+
 QUALITY_KEYS = ("contrast", "sharpness", "entropy", "saturation", "brightness", "edge_density", "colorfulness", "naturalness")
 
 

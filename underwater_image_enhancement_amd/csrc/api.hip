@@ -1346,6 +1346,91 @@ int uwie_perceptual_bwd_f32(uwie_ctx *ctx, const uwie_vgg *vgg, int batch, int H
     return launch_perceptual_bwd(vgg->net, s, d_grad_loss, d_grad_pred, d_workspace, (hipStream_t)stream);
 }
 
+// ImprovedVGGParameterNet (k_param_net.hip)
+struct uwie_param_net {
+    int device;
+    ParamNet net;  // device pointers into blob
+    void *blob;
+};
+
+static bool param_net_shape_ok(int batch, int H, int W)
+{
+    return shape_ok(batch, H, W) && H >= 8 && W >= 8 && (long long)batch * H * W <= (1ll << 28);
+}
+
+int uwie_param_net_create(uwie_ctx *ctx, const float *d_params, int use_features, uwie_param_net **out_net)
+{
+    UWIE_REQUIRE(ctx && d_params && out_net, "param_net_create: NULL pointer");
+    *out_net = nullptr;
+    const int uf = use_features ? 1 : 0;
+    if (param_net_count(uf) != (size_t)UWIE_PARAM_NET_PARAMS(uf)) {
+        set_error("param_net_create: internal parameter count %zu differs from UWIE_PARAM_NET_PARAMS", param_net_count(uf));
+        return UWIE_E_INVALID;
+    }
+    UWIE_SCOPE(ctx);
+    void *blob = nullptr, *scratch = nullptr;
+    UWIE_HIP_CHECK(hipMalloc(&blob, param_net_blob_bytes(uf)));
+    hipError_t e = hipMalloc(&scratch, param_net_scratch_floats() * sizeof(float));
+    if (e != hipSuccess) {
+        (void)hipFree(blob);
+        set_error("param_net_create: %s", hipGetErrorString(e));
+        return UWIE_E_HIP;
+    }
+    ParamNet net{};
+    const int rc = param_net_pack(d_params, uf, blob, static_cast<float *>(scratch), &net, nullptr);
+    e = rc == UWIE_OK ? hipStreamSynchronize(nullptr) : hipSuccess;
+    (void)hipFree(scratch);  // the data-gradient copy of conv4_x: not needed for inference
+    if (rc != UWIE_OK || e != hipSuccess) {
+        (void)hipFree(blob);
+        if (e != hipSuccess) set_error("param_net_create: packing failed: %s", hipGetErrorString(e));
+        return rc != UWIE_OK ? rc : UWIE_E_HIP;
+    }
+    *out_net = new uwie_param_net{ctx->device, net, blob};
+    return UWIE_OK;
+}
+
+void uwie_param_net_destroy(uwie_param_net *net)
+{
+    if (!net) return;
+    int prev = -1;
+    const bool switch_dev = hipGetDevice(&prev) == hipSuccess && prev != net->device && hipSetDevice(net->device) == hipSuccess;
+    (void)hipFree(net->blob);
+    if (switch_dev) (void)hipSetDevice(prev);
+    delete net;
+}
+
+size_t uwie_param_net_workspace_bytes(int batch, int H, int W)
+{
+    if (!param_net_shape_ok(batch, H, W)) return 0;
+    return param_net_ws_bytes(Shape{batch, H, W});
+}
+
+int uwie_param_net_f32(uwie_ctx *ctx, const uwie_param_net *net, const float *d_img, const float *d_features, int batch, int H, int W,
+                       float *d_out, float *d_pooled, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE(ctx && net && d_img && d_out, "param_net: NULL pointer");
+    UWIE_REQUIRE(net->device == ctx->device, "param_net: the network lives on another device");
+    UWIE_REQUIRE(shape_ok(batch, H, W) && (long long)batch * H * W <= (1ll << 28), "param_net: batch/H/W out of range");
+    if (H < 8 || W < 8) {
+        set_error("param_net: H and W must be >= 8 (got %d x %d): pool3's output would be empty", H, W);
+        return UWIE_E_INVALID;
+    }
+    UWIE_REQUIRE(d_features || net->net.din == 1024, "param_net: a use_features network needs d_features [batch][79]");
+    const Shape s{batch, H, W};
+    UWIE_CHECK_WS(param_net_ws_bytes(s));
+    UWIE_SCOPE(ctx);
+    return launch_param_net(net->net, d_img, d_features, s, d_out, d_pooled, d_workspace, (hipStream_t)stream);
+}
+
+int uwie_u8_to_f32(uwie_ctx *ctx, const uint8_t *d_in, float *d_out, size_t n, void *stream)
+{
+    UWIE_REQUIRE(ctx && d_in && d_out, "u8_to_f32: NULL pointer");
+    UWIE_REQUIRE(((uintptr_t)d_in & 3) == 0 && ((uintptr_t)d_out & 15) == 0, "u8_to_f32: d_in must be 4-byte, d_out 16-byte aligned");
+    if (n == 0) return UWIE_OK;
+    UWIE_SCOPE(ctx);
+    return launch_u8_to_f32(d_in, n, d_out, (hipStream_t)stream);
+}
+
 int uwie_extract_features_u8(uwie_ctx *ctx, const uint8_t *d_in, float *d_features, int batch, int H, int W,
                              void *d_workspace, size_t workspace_bytes, void *stream)
 {

@@ -445,6 +445,29 @@ int vgg_pack(const float *d_params, int precision, void *blob, VggNet *net, hipS
 size_t perceptual_ws_bytes(Shape s, int precision);
 int launch_perceptual(const VggNet &net, const float *d_pred, const float *d_target, Shape s, float *d_loss, void *ws, hipStream_t st);
 int launch_perceptual_bwd(const VggNet &net, Shape s, const float *d_grad_loss, float *d_grad_pred, void *ws, hipStream_t st);
+// k_vgg.hip: one more float32 3x3 conv packed as k_vgg_conv reads it (wf [Cout][9][Cin]; wb_scratch receives the rotated
+// data-gradient copy, Cout * 9 * Cin floats, and may be freed after the stream has run)
+int vgg_pack_conv_f32(const float *src, int Cout, int Cin, float *wf, float *wb_scratch, float *bias, hipStream_t st);
+// k_vgg.hip: ImprovedVGGParameterNet's trunk, features[:23] in float32: conv1_1 ... relu3_3, pool3, conv4_1 ... relu4_3
+// into X or Y (both B * H * W * 64 floats, used as a ping-pong); returns relu4_3's buffer [B][H/8][W/8][512]
+int launch_param_trunk(const VggNet &net, const float *const wf4[3], const float *const bias4[3], const float *img, Shape s, float *X,
+                       float *Y, float **relu43, hipStream_t st);
+// k_param_net.hip: ImprovedVGGParameterNet
+struct ParamNet {
+    VggNet trunk;  // UWIE_VGG_F32, layers 0 .. 6
+    const float *wf4[3], *bias4[3];
+    int din;                           // 1103 (use_features) or 1024
+    const float *lw[6], *lb[6];        // fusion.0, fusion.4, attention.0, attention.2, heads.0 (4 x 128 rows), heads.3 ([4][128])
+    const float *bn[2];                // [4][C] = weight, bias, running_mean, running_var of fusion.1 / fusion.5
+};
+size_t param_net_count(int use_features);
+size_t param_net_blob_bytes(int use_features);
+int param_net_pack(const float *d_params, int use_features, void *blob, float *scratch, ParamNet *net, hipStream_t st);
+size_t param_net_scratch_floats();
+size_t param_net_ws_bytes(Shape s);
+int launch_param_net(const ParamNet &net, const float *img, const float *feat, Shape s, float *out, float *pooled, void *ws,
+                     hipStream_t st);
+int launch_u8_to_f32(const uint8_t *d_in, size_t n, float *d_out, hipStream_t st);
 // float64 data (ES surface): first digit = f64_key(v) >> 53
 int select_begin64(Shape s, const double *q_percent, int nq, void *ws, hipStream_t st, SelectPlan *plan);
 int select_run64(const SelectPlan &plan, const double *d_vals, int planar, Shape s, bool pass1_done, hipStream_t st);

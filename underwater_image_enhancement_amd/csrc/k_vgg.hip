@@ -558,4 +558,47 @@ int launch_perceptual_bwd(const VggNet &net, Shape s, const float *d_grad_loss, 
                                          : perceptual_bwd<float>(net, s, d_grad_loss, d_grad_pred, ws, st);
 }
 
+// ---------------------------------------------------------------- ImprovedVGGParameterNet's trunk
+int vgg_pack_conv_f32(const float *src, int Cout, int Cin, float *wf, float *wb_scratch, float *bias, hipStream_t st)
+{
+    const size_t nw = (size_t)Cout * 9 * Cin;
+    UWIE_LAUNCH(k_vgg_pack<float>, dim3(grid_for(nw + Cout, 1024)), dim3(256), 0, st, src, Cout, Cin, wf, wb_scratch, bias);
+    UWIE_LAUNCH_CHECK();
+    return UWIE_OK;
+}
+
+int launch_param_trunk(const VggNet &net, const float *const wf4[3], const float *const bias4[3], const float *img, Shape s, float *X,
+                       float *Y, float **relu43, hipStream_t st)
+{
+    static const char *const name4[3] = {"vgg conv4_1", "vgg conv4_2", "vgg conv4_3"};
+    const int B = s.B, H3 = s.H / 4, W3 = s.W / 4, H4 = H3 / 2, W4 = W3 / 2;
+    Acts A{};
+    A.X = X;
+    A.Y = Y;
+    const void *a6;  // relu3_2, in Y
+    VGG_TRY(trunk<float>(net, img, s, A, false, &a6, st));
+    VGG_TRY((conv<float, EPI_POOL>(net, 6, false, a6, X, B, H3, W3, st)));  // conv3_3 + relu3_3 + pool3 (no indices)
+    float *in = X, *out = Y;
+    for (int l = 0; l < 3; ++l) {
+        ConvArgs a{};
+        a.x = in;
+        a.w = wf4[l];
+        a.bias = bias4[l];
+        a.y = out;
+        a.B = B;
+        a.H = H4;
+        a.W = W4;
+        a.Cin = l ? 512 : 256;
+        a.Cout = 512;
+        a.M = B * H4 * W4;
+        VGG_LAUNCH(name4[l], (k_vgg_conv<float, EPI_RELU>), dim3(cdiv(a.M, kTile), a.Cout / kTile), dim3(256), st, a);
+        UWIE_LAUNCH_CHECK();
+        float *t = in;
+        in = out;
+        out = t;
+    }
+    *relu43 = in;
+    return UWIE_OK;
+}
+
 }  // namespace uwie

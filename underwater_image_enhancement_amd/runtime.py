@@ -415,6 +415,47 @@ class Device:
                                                self.stream()))
         return out
 
+    # ------------------------------------------------------------------ ImprovedVGGParameterNet (uwie_param_net_*)
+    def param_net_create(self, params, use_features: bool):
+        """A uwie_param_net handle from the state dict's float tensors flattened in state-dict order (float32,
+        _lib.PARAM_NET_PARAMS[use_features] values; include/uwie.h lists the order).  The caller owns it (param_net_destroy)."""
+        flat = params.to(device=self.torch_device, dtype=torch.float32).contiguous()
+        assert flat.numel() == _lib.PARAM_NET_PARAMS[bool(use_features)]
+        torch.cuda.synchronize(self.index)  # the packing runs on the null stream
+        h = ctypes.c_void_p()
+        check(self.lib.uwie_param_net_create(self._ctx, _ptr(flat), int(bool(use_features)), ctypes.byref(h)))
+        return h
+
+    def param_net_destroy(self, handle):
+        torch.cuda.synchronize(self.index)
+        self.lib.uwie_param_net_destroy(handle)
+
+    def param_net_f32(self, net, img, features=None, want_pooled: bool = False):
+        """The eval-mode forward: img float32 cuda [B,3,H,W], features float32 cuda [B,79] or None.  Returns (float32 [B,4] =
+        omega, gamma, L_low, L_high, float32 [B,1024] pooled vector or None).  Sets no status bit."""
+        assert img.dtype == torch.float32 and img.dim() == 4 and img.shape[1] == 3
+        B, _, H, W = (int(v) for v in img.shape)
+        if features is not None:
+            assert features.dtype == torch.float32 and tuple(features.shape) == (B, 79)
+            features = features.contiguous()
+        n = self.lib.uwie_param_net_workspace_bytes(B, H, W)
+        if n == 0:
+            raise _lib.UwieError(f"param_net: batch/H/W out of range ({B}, {H}, {W})")
+        ws = torch.empty(int(n), dtype=torch.uint8, device=self.torch_device)
+        out = self.empty((B, 4), torch.float32)
+        pooled = self.empty((B, 1024), torch.float32) if want_pooled else None
+        check(self.lib.uwie_param_net_f32(self._ctx, net, _ptr(img.contiguous()), _ptr(features), B, H, W, _ptr(out), _ptr(pooled),
+                                          _ptr(ws), ws.numel(), self.stream()))
+        return out, pooled
+
+    def u8_to_f32(self, frames):
+        """uint8 cuda tensor of any shape -> float32 of that shape, u8.astype(float32) / 255.0 (uwie_u8_to_f32)."""
+        assert frames.dtype == torch.uint8
+        frames = frames.contiguous()
+        out = self.empty(tuple(frames.shape), torch.float32)
+        check(self.lib.uwie_u8_to_f32(self._ctx, _ptr(frames), _ptr(out), frames.numel(), self.stream()))
+        return out
+
     def extract_features_u8(self, frames):
         """frames: uint8 cuda tensor [B,H,W,3] -> float32 [B,79] (vgg_16_UIE.extract_all_features per frame)."""
         B, H, W = self._bhw(frames)
