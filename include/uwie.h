@@ -447,7 +447,13 @@ int uwie_resize_rgb_u8(uwie_ctx *ctx, const uwie_frame_desc *d_desc, int batch, 
  * weights8 (host pointer, optional): weights in the order contrast, sharpness, entropy, saturation, brightness,
  * edge_density, colorfulness, naturalness (NULL: the reference defaults).  d_scores: [batch][9] float64 = the eight
  * scores in that order, then the weighted total.  Integer-derived parts are exact; float statistics are evaluated in
- * float64 (NumPy: float32 pairwise): 2e-3 on the 0..100 scores.
+ * float64 (NumPy: float32 pairwise): 2e-3 on the 0..100 scores against the float32 reference, whose own distance from a
+ * float64 evaluation is at most 4.2e-5 per score on frames up to 1080p.  Against that float64 evaluation
+ * (tests/quality_ref.py): 1e-9 for every score when d_f32 is NULL (functions of integer sums and histograms only); with
+ * d_f32 the colourfulness reads float32 values and is held to 7e-6.  A NaN in d_f32 gives NaN colourfulness and a NaN total.
+ * Deterministic: a frame's nine numbers are the same bits in every run and at every position of every batch (integer
+ * atomics, and per-block float64 partials added in block order; the grid depends on H * W only).
+ * Workspace: uwie_workspace_bytes(batch, H, W, NULL) (it includes the partials' [batch][blocks][4] float64 slab).
  */
 int uwie_quality_scores(uwie_ctx *ctx, const uint8_t *d_u8, const float *d_f32, int batch, int H, int W, int gray_shift,
                         const double *weights8, double *d_scores, void *d_workspace, size_t workspace_bytes, void *stream);

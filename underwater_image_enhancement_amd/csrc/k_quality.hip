@@ -1,14 +1,21 @@
 // quality_assessment.QualityAssessment (quality_assessment.py:15-286): the eight no-reference scores and their weighted
 // sum, as device reductions, so that picking the best of N strategies (main.py:130-146) does not leave the GPU.
 //   k_qa_maps    one pass over the quantised frame: gray plane (RGB2GRAY), histograms of gray, HSV saturation and LAB
-//                lightness, and the four colourfulness sums (from the float image when given, else from u8/255)
+//                lightness, and the four colourfulness sums: exact integer sums of r - g and r + g - 2b when the frame is
+//                u8 / 255, one float64 partial per block from the float image when one is given
 //   k_qa_lap     3x3 Laplacian of the gray plane (BORDER_REFLECT_101) as exact integer sums of l and l*l
 //   Canny        the quadtree's kernels on one full-frame region per image -> edge count
 //   k_qa_finish  scores in float64 from the histograms / sums
 // Integer-derived quantities (gray, S, L, Canny, the threshold counts) are exact.  The floating statistics are
 // evaluated in float64 from histograms and exact integer sums instead of NumPy's float32 pairwise sums, and the
-// Laplacian uses l/255 for the sum of float32(g/255) terms: stated tolerance 2e-3 on the 0..100 scores
-// (tests/test_gpu_stages.py).
+// Laplacian uses l/255 for the sum of float32(g/255) terms: 2e-3 on the 0..100 scores against the float32 oracle
+// (tests/test_gpu_stages.py); the measured distance of that oracle from a float64 evaluation is in DESIGN.md section 2.
+// Against the float64 evaluation (tests/quality_ref.py) every score of a u8 frame is held to 1e-9; colourfulness from a
+// float image reads float32 values and is held to twice the oracle's own measured distance (tests/test_gpu_quality.py).
+// Determinism: every cross-block sum is an integer atomic (exact in any order) or a per-block partial that k_qa_finish
+// adds in block order, and the grid depends on the frame size only.  The scores of a frame are therefore the same bits
+// in every run, at every position of every batch; for a u8 frame they do not depend on the grid either.  A NaN in the
+// float image gives NaN colourfulness and a NaN total, like np.clip and the reference's weighted sum.
 #include "common.h"
 #include "devutil.h"
 
@@ -32,17 +39,20 @@ __device__ __forceinline__ double wave_sum_f64(double v)
     return v;
 }
 
-// grid (nblk, B), block 256.  hist: [B][3][256] (gray, S, L); csum: [B][4] doubles (sum rg, yb, rg^2, yb^2).
+// grid (nblk, B), block 256.  hist: [B][3][256] (gray, S, L).  The colourfulness sums (rg, yb, rg^2, yb^2) go to
+// cpart: [B][nblk][4] doubles, one row per block, when fimg is given; else to isum: [B][4] int64 of 255 * rg = r - g and
+// 510 * yb = r + g - 2b (|sum of squares| <= 510^2 * npx: 64 bits hold any frame the library takes).
 __global__ void __launch_bounds__(256) k_qa_maps(const LabTables *__restrict__ T, const uint8_t *__restrict__ in,
                                                  const float *__restrict__ fimg, int npx, int shift,
                                                  uint8_t *__restrict__ gray, uint32_t *__restrict__ hist,
-                                                 double *__restrict__ csum)
+                                                 double *__restrict__ cpart, unsigned long long *__restrict__ isum)
 {
     __shared__ uint32_t h[3][256];
     __shared__ int s_sdiv[256];
     __shared__ uint16_t s_gamma[256], s_cbrt[3072];
     __shared__ int s_fwd[3];
     __shared__ double s_red[4][4];
+    __shared__ long long s_ired[4][4];
     const int b = blockIdx.y, tid = threadIdx.x;
     for (int i = tid; i < 768; i += 256) (&h[0][0])[i] = 0;
     s_sdiv[tid] = tid ? __double2int_rn((double)(255 << 12) / (double)tid) : 0;  // RGB2HSV_b's sdiv_table
@@ -56,6 +66,7 @@ __global__ void __launch_bounds__(256) k_qa_maps(const LabTables *__restrict__ T
     constexpr int Lscale = (116 * 255 + 50) / 100;
     constexpr int Lshift = -((16 * 255 * (1 << 15) + 50) / 100);
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    long long i0 = 0, i1 = 0, i2 = 0, i3 = 0;
     for (int p = blockIdx.x * 256 + tid; p < npx; p += gridDim.x * 256) {
         const uint32_t r = img[(size_t)p * 3], gg = img[(size_t)p * 3 + 1], bl = img[(size_t)p * 3 + 2];
         const uint32_t gv = gray_fixed(r, gg, bl, shift);
@@ -68,21 +79,33 @@ __global__ void __launch_bounds__(256) k_qa_maps(const LabTables *__restrict__ T
         atomicAdd(&h[0][gv], 1u);
         atomicAdd(&h[1][sat], 1u);
         atomicAdd(&h[2][L], 1u);
-        float fr, fg, fb;
         if (fi) {
-            fr = fi[(size_t)p * 3]; fg = fi[(size_t)p * 3 + 1]; fb = fi[(size_t)p * 3 + 2];
+            const float fr = fi[(size_t)p * 3], fg = fi[(size_t)p * 3 + 1], fb = fi[(size_t)p * 3 + 2];
+            const float rg = fr - fg, yb = 0.5f * (fr + fg) - fb;  // quality_assessment.py:158-159
+            a0 += (double)rg; a1 += (double)yb; a2 += (double)rg * (double)rg; a3 += (double)yb * (double)yb;
         } else {
-            fr = px_norm(r); fg = px_norm(gg); fb = px_norm(bl);
+            const int rg = (int)r - (int)gg, yb = (int)r + (int)gg - 2 * (int)bl;
+            i0 += rg; i1 += yb; i2 += rg * rg; i3 += yb * yb;
         }
-        const float rg = fr - fg, yb = 0.5f * (fr + fg) - fb;  // quality_assessment.py:158-159
-        a0 += (double)rg; a1 += (double)yb; a2 += (double)rg * (double)rg; a3 += (double)yb * (double)yb;
     }
-    a0 = wave_sum_f64(a0); a1 = wave_sum_f64(a1); a2 = wave_sum_f64(a2); a3 = wave_sum_f64(a3);
-    if ((tid & 63) == 0) {
-        s_red[tid >> 6][0] = a0; s_red[tid >> 6][1] = a1; s_red[tid >> 6][2] = a2; s_red[tid >> 6][3] = a3;
+    if (fi) {  // thread, wave and block sums in a fixed order; the blocks' rows are added by k_qa_finish
+        a0 = wave_sum_f64(a0); a1 = wave_sum_f64(a1); a2 = wave_sum_f64(a2); a3 = wave_sum_f64(a3);
+        if ((tid & 63) == 0) {
+            s_red[tid >> 6][0] = a0; s_red[tid >> 6][1] = a1; s_red[tid >> 6][2] = a2; s_red[tid >> 6][3] = a3;
+        }
+        __syncthreads();
+        if (tid < 4)
+            cpart[((size_t)b * gridDim.x + blockIdx.x) * 4 + tid] = (s_red[0][tid] + s_red[1][tid]) + (s_red[2][tid] + s_red[3][tid]);
+    } else {
+        i0 = (long long)wave_sum_u64((uint64_t)i0); i1 = (long long)wave_sum_u64((uint64_t)i1);
+        i2 = (long long)wave_sum_u64((uint64_t)i2); i3 = (long long)wave_sum_u64((uint64_t)i3);
+        if ((tid & 63) == 0) {
+            s_ired[tid >> 6][0] = i0; s_ired[tid >> 6][1] = i1; s_ired[tid >> 6][2] = i2; s_ired[tid >> 6][3] = i3;
+        }
+        __syncthreads();
+        if (tid < 4)
+            atomicAdd(&isum[b * 4 + tid], (unsigned long long)(s_ired[0][tid] + s_ired[1][tid] + s_ired[2][tid] + s_ired[3][tid]));
     }
-    __syncthreads();
-    if (tid < 4) atomicAdd(&csum[b * 4 + tid], (s_red[0][tid] + s_red[1][tid]) + (s_red[2][tid] + s_red[3][tid]));
     for (int i = tid; i < 768; i += 256) {
         const uint32_t c = (&h[0][0])[i];
         if (c) atomicAdd(&hist[(size_t)b * 768 + i], c);
@@ -113,14 +136,37 @@ __global__ void __launch_bounds__(256) k_qa_lap(const uint8_t *__restrict__ gray
         atomicAdd(&lsum[b * 2 + tid], (unsigned long long)(s_red[0][tid] + s_red[1][tid] + s_red[2][tid] + s_red[3][tid]));
 }
 
-__device__ __forceinline__ double clip100(double v) { return fmin(fmax(v, 0.0), 100.0); }
+// np.clip(v, 0, 100): a NaN stays a NaN (fmin / fmax alone would turn it into 0)
+__device__ __forceinline__ double clip100(double v) { return v != v ? v : fmin(fmax(v, 0.0), 100.0); }
 
-__global__ void k_qa_finish(const uint32_t *__restrict__ hist, const double *__restrict__ csum,
-                            const unsigned long long *__restrict__ lsum, const uint32_t *__restrict__ edges, int B,
-                            int npx, QaWeights wt, double *__restrict__ out)
+// sum((x - m)^2) / n of integers x with sum s1 and sum of squares s2, without the cancellation of s2 / n - (s1 / n)^2:
+// m = floor(s1 / n) is an integer, so the shifted sums stay exact integers and the correction (r / n)^2 is below 1.
+__device__ __forceinline__ double int_variance(long long s1, long long s2, long long n)
 {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
+    long long m = s1 / n;
+    if (s1 - m * n < 0) --m;
+    const long long r = s1 - m * n;  // 0 <= r < n
+    const long long t = s2 - 2 * m * s1 + n * m * m;  // sum((x - m)^2) >= 0
+    const double rn = (double)r / (double)n;
+    return fmax((double)t / (double)n - rn * rn, 0.0);
+}
+
+// grid B, block 64: the wave adds the blocks' colourfulness rows (lane l takes rows l, l + 64, ... in that order, then a
+// fixed butterfly), lane 0 evaluates the scores.  nblk == 0: the integer sums of a u8 frame are in isum instead.
+__global__ void __launch_bounds__(64) k_qa_finish(const uint32_t *__restrict__ hist, const double *__restrict__ cpart, int nblk,
+                                                  const unsigned long long *__restrict__ isum,
+                                                  const unsigned long long *__restrict__ lsum, const uint32_t *__restrict__ edges,
+                                                  int npx, QaWeights wt, double *__restrict__ out)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    double cs[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k = lane; k < nblk; k += 64) {
+        const double *row = cpart + ((size_t)b * nblk + k) * 4;
+        cs[0] += row[0]; cs[1] += row[1]; cs[2] += row[2]; cs[3] += row[3];
+    }
+    if (nblk)
+        for (int i = 0; i < 4; ++i) cs[i] = wave_sum_f64(cs[i]);
+    if (lane) return;
     const uint32_t *hg = hist + (size_t)b * 768, *hs = hg + 256, *hl = hg + 512;
     const double n = (double)npx;
     double mg = 0.0, ms = 0.0, mL = 0.0, ent = 0.0, dark = 0.0, bright = 0.0, oversat = 0.0;
@@ -146,9 +192,16 @@ __global__ void k_qa_finish(const uint32_t *__restrict__ hist, const double *__r
     vg /= n;
     const double l1 = (double)(long long)lsum[b * 2], l2 = (double)(long long)lsum[b * 2 + 1];
     const double vlap = (l2 - l1 * l1 / n) / n / (255.0 * 255.0);
-    const double *cs = csum + b * 4;
-    const double mrg = cs[0] / n, myb = cs[1] / n;
-    const double vrg = fmax(cs[2] / n - mrg * mrg, 0.0), vyb = fmax(cs[3] / n - myb * myb, 0.0);
+    double mrg, myb, vrg, vyb;
+    if (nblk) {
+        mrg = cs[0] / n; myb = cs[1] / n;
+        vrg = cs[2] / n - mrg * mrg; vyb = cs[3] / n - myb * myb;
+        vrg = vrg < 0.0 ? 0.0 : vrg; vyb = vyb < 0.0 ? 0.0 : vyb;  // keeps a NaN
+    } else {
+        const long long *is = reinterpret_cast<const long long *>(isum) + b * 4;
+        mrg = (double)is[0] / (255.0 * n); myb = (double)is[1] / (510.0 * n);
+        vrg = int_variance(is[0], is[2], npx) / (255.0 * 255.0); vyb = int_variance(is[1], is[3], npx) / (510.0 * 510.0);
+    }
     double sc[8];
     sc[0] = clip100(sqrt(vg) / 0.5 * 100.0);                                        // quality_assessment.py:25-31
     sc[1] = clip100(vlap / 0.5 * 100.0);                                            // :45-52
@@ -169,11 +222,15 @@ __global__ void k_qa_finish(const uint32_t *__restrict__ hist, const double *__r
 struct QaBufs {
     uint8_t *gray;
     uint32_t *hist, *edges;
-    double *csum;
-    unsigned long long *lsum;
+    double *cpart;
+    unsigned long long *isum, *lsum;
     Region *regs;
     void *canny;
 };
+
+// blocks per image of k_qa_maps / k_qa_lap: a function of the frame size alone, so a frame's float partials are summed
+// in the same order whatever batch it is part of
+int qa_blocks(Shape s) { return grid_for(s.npx(), 1024); }
 
 QaBufs carve_qa(Carver &c, Shape s)
 {
@@ -181,7 +238,8 @@ QaBufs carve_qa(Carver &c, Shape s)
     q.gray = c.take<uint8_t>((size_t)s.B * s.npx());
     q.hist = c.take<uint32_t>((size_t)s.B * 768);
     q.edges = c.take<uint32_t>(s.B);
-    q.csum = c.take<double>((size_t)s.B * 4);
+    q.cpart = c.take<double>((size_t)s.B * qa_blocks(s) * 4);
+    q.isum = c.take<unsigned long long>((size_t)s.B * 4);
     q.lsum = c.take<unsigned long long>((size_t)s.B * 2);
     q.regs = c.take<Region>(s.B);
     q.canny = c.take<char>(canny_ws_bytes(s));
@@ -245,10 +303,10 @@ int launch_quality_scores(uwie_ctx *ctx, const uint8_t *d_u8, const float *d_f32
     QaWeights wt;
     for (int i = 0; i < 8; ++i) wt.w[i] = weights8[i];
     UWIE_HIP_CHECK(hipMemsetAsync(q.hist, 0, sizeof(uint32_t) * (size_t)s.B * 768, st));
-    UWIE_HIP_CHECK(hipMemsetAsync(q.csum, 0, sizeof(double) * (size_t)s.B * 4, st));
+    UWIE_HIP_CHECK(hipMemsetAsync(q.isum, 0, sizeof(unsigned long long) * (size_t)s.B * 4, st));
     UWIE_HIP_CHECK(hipMemsetAsync(q.lsum, 0, sizeof(unsigned long long) * (size_t)s.B * 2, st));
-    const dim3 grid(grid_for(s.npx(), 1024), s.B);
-    UWIE_LAUNCH(k_qa_maps, grid, dim3(256), 0, st, ctx->d_lab, d_u8, d_f32, npx, gray_shift, q.gray, q.hist, q.csum);
+    const dim3 grid(qa_blocks(s), s.B);
+    UWIE_LAUNCH(k_qa_maps, grid, dim3(256), 0, st, ctx->d_lab, d_u8, d_f32, npx, gray_shift, q.gray, q.hist, q.cpart, q.isum);
     UWIE_LAUNCH_CHECK();
     UWIE_LAUNCH(k_qa_lap, grid, dim3(256), 0, st, q.gray, s.H, s.W, q.lsum);
     UWIE_LAUNCH_CHECK();
@@ -256,7 +314,8 @@ int launch_quality_scores(uwie_ctx *ctx, const uint8_t *d_u8, const float *d_f32
     if (rc != UWIE_OK) return rc;
     rc = launch_canny(q.gray, s, q.regs, s.B, s.H, s.W, 50, 150, q.edges, nullptr, q.canny, st);
     if (rc != UWIE_OK) return rc;
-    UWIE_LAUNCH(k_qa_finish, dim3(cdiv(s.B, 64)), dim3(64), 0, st, q.hist, q.csum, q.lsum, q.edges, s.B, npx, wt, d_scores);
+    UWIE_LAUNCH(k_qa_finish, dim3(s.B), dim3(64), 0, st, q.hist, q.cpart, d_f32 ? (int)grid.x : 0, q.isum, q.lsum, q.edges, npx, wt,
+                d_scores);
     UWIE_LAUNCH_CHECK();
     return UWIE_OK;
 }
