@@ -205,3 +205,54 @@ def test_a_small_training_loop_recovers_omega_and_gamma(dev):
           f"|gamma error| {(ga - ga_t).abs().max().item():.2e}")
     assert last * 100 <= first
     assert (om - om_t).abs().max().item() < 0.02 and (ga - ga_t).abs().max().item() < 0.02
+
+
+def _exact_params(B):
+    """Values float16 holds exactly, so every form below denotes the same float32 numbers."""
+    return {"L_low": np.full((B, 1), 5.0), "L_high": np.full((B, 1), 95.0), "omega": np.full((B, 1), 0.75),
+            "gamma": np.full((B, 1), 1.25)}
+
+
+@pytest.mark.parametrize("keys", [("omega", "gamma"), ("omega",), ("gamma",), ()])
+def test_inference_parameter_forms_give_the_binding_bytes(dev, keys):
+    """Python floats, NumPy float64, CPU float64 tensors and device float16 tensors all go through the one column builder:
+    each gives exactly the bytes of the Device binding with hand-built float32 [B,4] columns."""
+    import torch
+
+    import underwater_image_enhancement_amd as uw
+
+    B, H, W = 2, 5, 7  # 35 pixels: an odd plane, not a multiple of any tile
+    x = dev.tensor(np.random.default_rng(21).random((B, 3, H, W), dtype=np.float32))
+    full = _exact_params(B)
+    base = {k: v for k, v in full.items() if k in ("L_low", "L_high") + keys}
+    pt = dev.tensor(np.concatenate([full["L_low"], full["L_high"], full["omega"] if "omega" in keys else np.zeros((B, 1)),
+                                    full["gamma"] if "gamma" in keys else np.ones((B, 1))], axis=1).astype(np.float32))
+    want = dev.diff_enhance_f32(x, pt, True, "omega" in keys, "gamma" in keys)
+    forms = {"floats": {k: float(v[0, 0]) for k, v in base.items()},
+             "numpy float64": {k: v.astype(np.float64) for k, v in base.items()},
+             "cpu float64 tensors": {k: torch.from_numpy(v.astype(np.float64)) for k, v in base.items()},
+             "device float16 tensors": {k: torch.from_numpy(v).to(device=dev.torch_device, dtype=torch.float16)
+                                        for k, v in base.items()}}
+    enh = uw.DifferentiableEnhancement()
+    for name, params in forms.items():
+        with torch.no_grad():
+            got = enh(x, params)
+        assert got.dtype == torch.float32 and got.grad_fn is None, name
+        assert torch.equal(got.view(torch.int32), want.view(torch.int32)), f"{name}, keys {keys}"
+
+
+def test_a_float64_torch_image_is_a_value_error_with_and_without_grad(dev):
+    import torch
+
+    import underwater_image_enhancement_amd as uw
+
+    B = 2
+    x = torch.from_numpy(np.random.default_rng(22).random((B, 3, 5, 7))).to(dev.torch_device)
+    params = {k: torch.from_numpy(v.astype(np.float32)).to(dev.torch_device) for k, v in _exact_params(B).items()}
+    enh = uw.DifferentiableEnhancement()
+    with torch.no_grad(), pytest.raises(ValueError, match="float32 image batch"):
+        enh(x, params)
+    for requires in (False, True):  # grad mode on: the inference branch, then the grad branch
+        params["omega"].requires_grad_(requires)
+        with pytest.raises(ValueError, match="float32 image batch"):
+            enh(x, params)

@@ -27,7 +27,12 @@ import numpy as np
 import torch
 
 from . import _lib
+# the enhancement modules and ReferenceLoss live in modules.py; this module re-exports them
+from .modules import (DifferentiableEnhancement, DiffEnhanceFunction, DiffEnhanceLossFunction,  # noqa: F401
+                      GatedDifferentiableEnhancement, GatedDiffEnhanceFunction, GatedDiffEnhanceLossFunction, ReferenceLoss,
+                      RefLossFunction, _loss_reference, _module_loss, _raise_rank_error, _read_loss)
 from .runtime import Device, get_device
+
 
 class UnsupportedInputError(ValueError):
     """The float image is not u8-derived: this build has no device path for it (see the module docstring)."""
@@ -202,479 +207,6 @@ def process_batch(frames, filenames=None, device: int | None = None, compute=Non
         stats["processed_images" if good else "failed_images"] += 1
         stats["total_outputs"] += len(DRIVER_STRATEGIES)
     return outs, rows, stats
-
-
-# ------------------------------------------------------------------ vgg_16_UIE.DifferentiableEnhancement (N3)
-class DiffEnhanceFunction(torch.autograd.Function):
-    """``out = DiffEnhanceFunction.apply(img, params, flags, planar, dev)``: the device forward with its backward.
-
-    ``img``: float32 ``[B,3,H,W]`` (planar) or ``[B,H,W,3]`` on ``dev``; ``params``: float32 ``[B,4]`` =
-    ``L_low, L_high, omega, gamma``; ``flags``: ``UWIE_DIFF_OMEGA (1) | UWIE_DIFF_GAMMA (2)``.  The gradient is the one
-    torch autograd gives the reference module on the CPU: ``params`` gets ``0, 0, d omega,
-    d gamma``; ``img`` gets its gradient only when it requires one (otherwise the kernel skips that write).
-    """
-
-    @staticmethod
-    def forward(ctx, img, params, flags, planar, dev):
-        out, saved = dev.diff_enhance_save_f32(img, params, planar, flags)
-        ctx.save_for_backward(img, params, saved)
-        ctx.flags, ctx.planar, ctx.dev = flags, planar, dev
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        img, params, saved = ctx.saved_tensors
-        grad_img, grad_params = ctx.dev.diff_enhance_bwd_f32(img, params, saved, grad_out.float().contiguous(), ctx.planar,
-                                                             ctx.flags, want_img=ctx.needs_input_grad[0])
-        return grad_img, (grad_params if ctx.needs_input_grad[1] else None), None, None, None
-
-
-class DifferentiableEnhancement:
-    """``vgg_16_UIE.DifferentiableEnhancement`` (vgg_16_UIE.py:24-128) on the device, forward and backward.
-
-    ``forward(img, params)``: ``img`` is ``(B, 3, H, W)`` float32 (NumPy or torch ROCm tensor), ``params`` a dict of
-    ``(B, 1)``-shaped values with the reference's keys: ``L_low`` and ``L_high`` are required, ``omega`` and ``gamma``
-    optional (a missing key skips that stage, vgg_16_UIE.py:48,52).
-
-    Differentiable: with grad mode on and ``img`` or a parameter tensor requiring grad, the output carries a ``grad_fn``
-    and ``loss.backward()`` runs the gradient kernels (``DiffEnhanceFunction``).  ``omega`` and ``gamma`` get the
-    gradient torch autograd gives the reference on the CPU, in their own dtype and device (float16 / bfloat16 values
-    from an autocast head are cast to float32 first, as torch's type promotion does in the reference); ``L_low`` and
-    ``L_high`` get none (the reference reads them with ``.item()``); ``img`` gets one when it requires it.  Otherwise
-    the forward alone runs, as for inference.
-    """
-
-    device: int | None = None
-
-    @staticmethod
-    def _wants_grad(img, params) -> bool:
-        if not torch.is_grad_enabled():
-            return False
-        vals = [img] + [params[k] for k in ("L_low", "L_high", "omega", "gamma") if k in params]
-        return any(isinstance(v, torch.Tensor) and v.requires_grad for v in vals)
-
-    def _forward_grad(self, dev: Device, img, params):
-        x = img.to(dev.torch_device)
-        if x.dtype != torch.float32:
-            raise ValueError(f"expected a float32 image batch, got {x.dtype}")
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError(f"expected a (B, 3, H, W) image batch, got {tuple(x.shape)}")
-        B = x.shape[0]
-        cols = []
-        for key, default in (("L_low", None), ("L_high", None), ("omega", 0.0), ("gamma", 1.0)):
-            if key in params:
-                v = params[key]
-                v = (v.to(device=dev.torch_device, dtype=torch.float32) if isinstance(v, torch.Tensor)
-                     else torch.as_tensor(np.asarray(v, dtype=np.float32), device=dev.torch_device))
-                if key in ("L_low", "L_high"):
-                    v = v.detach()  # sorted positions: no gradient (vgg_16_UIE.py:78-79 reads them with .item())
-                cols.append(torch.broadcast_to(v.reshape(-1), (B,)))
-            elif default is None:
-                raise KeyError(key)
-            else:
-                cols.append(torch.full((B,), default, dtype=torch.float32, device=dev.torch_device))
-        flags = (1 if "omega" in params else 0) | (2 if "gamma" in params else 0)
-        return DiffEnhanceFunction.apply(x, torch.stack(cols, dim=1).contiguous(), flags, True, dev)
-
-    def forward(self, img, params):
-        dev = get_device(self.device)
-        if self._wants_grad(img, params):
-            return self._forward_grad(dev, img, params)
-        was_numpy = not hasattr(img, "data_ptr")
-        x = dev.tensor(np.ascontiguousarray(img, dtype=np.float32)) if was_numpy else img
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError(f"expected a (B, 3, H, W) image batch, got {tuple(x.shape)}")
-        B = x.shape[0]
-        cols = []
-        for key, default in (("L_low", None), ("L_high", None), ("omega", 0.0), ("gamma", 1.0)):
-            if key in params:
-                v = params[key]
-                v = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
-                cols.append(np.broadcast_to(np.asarray(v, dtype=np.float32).reshape(-1), (B,)))
-            elif default is None:
-                raise KeyError(key)
-            else:
-                cols.append(np.full((B,), default, np.float32))
-        pt = dev.tensor(np.ascontiguousarray(np.stack(cols, axis=1)))
-        out = dev.diff_enhance_f32(x, pt, planar=True, has_omega="omega" in params, has_gamma="gamma" in params)
-        return out.cpu().numpy() if was_numpy else out
-
-    __call__ = forward
-
-    def with_loss(self, images, params, references):
-        """``(out, l1, l2)``: the module's output (the inference forward's bytes) with ``l1 = mean|out - references|`` and
-        ``l2 = mean((out - references)^2)`` from the same sweep (ReferenceLoss).  With grad mode on,
-        ``out``, ``l1`` and ``l2`` all carry the graph: a term of the caller's on ``out`` (CombinedLoss's perceptual loss)
-        adds its gradient in the same backward.  ``references``: float32, ``images``' shape (ValueError otherwise)."""
-        return _with_loss(self, images, params, references)
-
-    def enhance_image(self, img, params):
-        """``EnhancementPredictor.enhance_image(img, params)`` (use_trained_model.py:83-111) with explicit parameters:
-        ``img`` HxWx3 RGB float in [0, 1], ``params`` a dict of Python floats with ``omega, gamma, L_low, L_high``."""
-        dev = get_device(self.device)
-        x = np.ascontiguousarray(np.asarray(img, dtype=np.float32))
-        if x.ndim != 3 or x.shape[2] != 3:
-            raise ValueError(f"expected an HxWx3 image, got {x.shape}")
-        pt = dev.tensor(np.array([[params["L_low"], params["L_high"], params["omega"], params["gamma"]]], np.float32))
-        out = dev.diff_enhance_f32(dev.tensor(x[None]), pt, planar=False)[0].cpu().numpy()
-        return np.clip(out, 0.0, 1.0)
-
-
-# ------------------------------------------------------------------ deep_learning_parameters.DifferentiableEnhancement
-class GatedDiffEnhanceFunction(torch.autograd.Function):
-    """``out = GatedDiffEnhanceFunction.apply(img, params, planar, dev)``: the gated module's device forward with its backward.
-
-    ``img``: float32 ``[B,3,H,W]`` (planar) or ``[B,H,W,3]`` on ``dev``; ``params``: float32 ``[B,4]`` =
-    ``L_low, L_high, use_gamma, gamma``.  The gradient is the one torch autograd gives the reference module on the CPU
-    (DESIGN.md section 10): ``params`` gets ``0, 0, d use_gamma, d gamma``; ``img`` gets its gradient only when it requires
-    one.  An image without a valid sorted position gets NaN and sets UWIE_STATUS_DIFF_RANK: this function does not check
-    it (``GatedDifferentiableEnhancement`` does).
-    """
-
-    @staticmethod
-    def forward(ctx, img, params, planar, dev):
-        out, saved = dev.diff_gated_save_f32(img, params, planar)
-        ctx.save_for_backward(img, params, saved)
-        ctx.planar, ctx.dev = planar, dev
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        img, params, saved = ctx.saved_tensors
-        grad_img, grad_params = ctx.dev.diff_gated_bwd_f32(img, params, saved, grad_out.float().contiguous(), ctx.planar,
-                                                           want_img=ctx.needs_input_grad[0])
-        return grad_img, (grad_params if ctx.needs_input_grad[1] else None), None, None
-
-
-def _raise_rank_error(L, n: int):
-    """Raise what ``color_stretch`` (deep_learning_parameters.py:73-77) raises first for ``L`` float32 ``[B,2]``: per image
-    ``int(L_low / 100.0 * n)``, ``int(L_high / 100.0 * n)`` (ValueError for NaN, OverflowError for inf), then the two
-    indexings (IndexError outside ``[-n, n - 1]``, ValueError beyond int64: torch's messages)."""
-    for lo, hi in np.asarray(L, dtype=np.float32).reshape(-1, 2):
-        ks = [int(float(v) / 100.0 * n) for v in (lo, hi)]
-        for k in ks:
-            if not -2**63 <= k < 2**63:
-                raise ValueError("Overflow when unpacking long long")
-            if not -n <= k < n:
-                raise IndexError(f"index {k} is out of bounds for dimension 0 with size {n}")
-
-
-class GatedDifferentiableEnhancement:
-    """``deep_learning_parameters.DifferentiableEnhancement`` (deep_learning_parameters.py:24-90) on the device, forward and
-    backward: the module ``EndToEndTrainer`` trains through.
-
-    ``forward(img, params)``: ``img`` is ``(B, 3, H, W)`` float32 (NumPy or torch ROCm tensor), ``params`` a dict of
-    ``(B, 1)``-shaped values with all four of the reference's keys, ``L_low``, ``L_high``, ``use_gamma`` and ``gamma`` (a
-    missing one raises ``KeyError``).  Per plane: stretch between the sorted positions ``int(L / 100.0 * n)`` (Python's
-    indexing rules, no clamp), then ``clamp(use_gamma * pow(s + 1e-8, 1.0 / gamma) + (1 - use_gamma) * s, 0, 1)``.
-
-    Differentiable: with grad mode on and ``img`` or a parameter tensor requiring grad, the output carries a ``grad_fn``
-    and ``loss.backward()`` runs the gradient kernels (``GatedDiffEnhanceFunction``).  ``use_gamma`` and ``gamma`` get the
-    gradient torch autograd gives the reference on the CPU, in their own dtype and device; ``L_low`` and ``L_high`` get none
-    (the reference reads them with ``.item()``); ``img`` gets one when it requires it.  Otherwise the forward alone runs,
-    with the same output bytes.
-
-    Errors: each call waits for the device once, after the forward.  A sorted position the reference could not index raises
-    the exception the reference raises there: ``IndexError`` (outside ``[-n, n - 1]``), ``ValueError`` (NaN ``L``, or a
-    position beyond int64), ``OverflowError`` (infinite ``L``).  Every other device status bit still raises ``UwieError``.
-    """
-
-    device: int | None = None
-    KEYS = ("L_low", "L_high", "use_gamma", "gamma")
-
-    @staticmethod
-    def _wants_grad(img, params) -> bool:
-        if not torch.is_grad_enabled():
-            return False
-        vals = [img] + [params[k] for k in GatedDifferentiableEnhancement.KEYS]
-        return any(isinstance(v, torch.Tensor) and v.requires_grad for v in vals)
-
-    @staticmethod
-    def _image(dev: Device, img):
-        x = img.to(dev.torch_device) if isinstance(img, torch.Tensor) else dev.tensor(np.ascontiguousarray(img, dtype=np.float32))
-        if x.dtype != torch.float32:
-            raise ValueError(f"expected a float32 image batch, got {x.dtype}")
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError(f"expected a (B, 3, H, W) image batch, got {tuple(x.shape)}")
-        return x
-
-    def forward(self, img, params):
-        vals = [params[k] for k in self.KEYS]  # KeyError in the reference's order
-        dev = get_device(self.device)
-        was_numpy = not isinstance(img, torch.Tensor)
-        grad = self._wants_grad(img, params)
-        x = self._image(dev, img)
-        B = x.shape[0]
-        cols = []
-        for key, v in zip(self.KEYS, vals):
-            v = (v.to(device=dev.torch_device, dtype=torch.float32) if isinstance(v, torch.Tensor)
-                 else torch.as_tensor(np.asarray(v, dtype=np.float32), device=dev.torch_device))
-            if key in ("L_low", "L_high") or not grad:
-                v = v.detach()  # sorted positions: no gradient (deep_learning_parameters.py:73-74 reads them with .item())
-            cols.append(torch.broadcast_to(v.reshape(-1), (B,)))
-        pt = torch.stack(cols, dim=1).contiguous()
-        if grad:
-            out = GatedDiffEnhanceFunction.apply(x, pt, True, dev)
-        else:
-            out = dev.diff_gated_f32(x, pt, planar=True)
-        if dev.check_status(allow=_lib.STATUS_DIFF_RANK) & _lib.STATUS_DIFF_RANK:
-            _raise_rank_error(pt[:, :2].detach().cpu().numpy(), x.shape[2] * x.shape[3])
-            raise _lib.UwieError("diff_gated: the device flagged a sorted position that the host finds valid")
-        return out.detach().cpu().numpy() if was_numpy and not grad else out
-
-    __call__ = forward
-
-    def with_loss(self, images, params, references):
-        """``(out, l1, l2)``: the module's output (the inference forward's bytes) with ``l1 = mean|out - references|`` and
-        ``l2 = mean((out - references)^2)`` from the same sweep (ReferenceLoss).  With grad mode on,
-        ``out``, ``l1`` and ``l2`` all carry the graph: a term of the caller's on ``out`` (CombinedLoss's perceptual loss)
-        adds its gradient in the same backward.  ``references``: float32, ``images``' shape (ValueError otherwise).
-        Waits once per call, as forward does, and raises what forward raises for an unindexable sorted position."""
-        return _with_loss(self, images, params, references)
-
-
-# ------------------------------------------------------------------ ReferenceLoss (deep_learning_parameters.py:170-196, N9)
-def _loss_backward(ctx, map_, img, params, saved, ref, grad_l1, grad_l2, grad_out=None):
-    """The shared backward of the three loss functions: dL/dl1, dL/dl2 go to the kernel as a device [2] (zeros for an
-    unused output), grad_out (dL/d(out), or None) as the upstream gradient of the kept output."""
-    dev = ctx.dev
-    z = None
-    if grad_l1 is None or grad_l2 is None:
-        z = torch.zeros((), dtype=torch.float32, device=dev.torch_device)
-    gl = torch.stack([(z if grad_l1 is None else grad_l1).float().reshape(()),
-                      (z if grad_l2 is None else grad_l2).float().reshape(())])
-    return dev.ref_loss_bwd_f32(map_, img, params, saved, ref, gl, ctx.planar, ctx.flags,
-                                grad_out=None if grad_out is None else grad_out.float(),
-                                want_img=ctx.needs_input_grad[0])
-
-
-class RefLossFunction(torch.autograd.Function):
-    """``l1, l2 = RefLossFunction.apply(o, ref, dev, sink)``: ``mean|o - ref|`` and ``mean((o - ref)^2)`` on the device
-    (uwie_ref_loss_f32, identity map), 0-dim float32.  ``o``, ``ref``: float32 ``(B, 3, H, W)`` on ``dev``.  The backward
-    gives ``o`` the gradient torch CPU autograd gives it, bit for bit; ``ref`` gets none.  ``sink`` (a list or None)
-    receives the device buffer whose first two words are l1, l2."""
-
-    @staticmethod
-    def forward(ctx, o, ref, dev, sink=None):
-        _, _, buf = dev.ref_loss_f32(_lib.LOSS_IDENTITY, o, None, ref, True)
-        ctx.save_for_backward(o, ref)
-        ctx.dev, ctx.planar, ctx.flags = dev, True, 0
-        ctx.set_materialize_grads(False)
-        if sink is not None:
-            sink.append(buf)
-        return buf[0], buf[1]
-
-    @staticmethod
-    def backward(ctx, grad_l1, grad_l2):
-        o, ref = ctx.saved_tensors
-        if grad_l1 is None and grad_l2 is None:
-            return None, None, None, None
-        grad_o, _ = _loss_backward(ctx, _lib.LOSS_IDENTITY, o, None, None, ref, grad_l1, grad_l2)
-        return grad_o, None, None, None
-
-
-class _ModuleLossFunction(torch.autograd.Function):
-    """The fused module step: ``[out,] l1, l2 = F.apply(img, params, ref, flags, planar, keep_out, status, dev, sink)``."""
-
-    MAP = None
-
-    @classmethod
-    def _run(cls, ctx, img, params, ref, flags, planar, keep_out, status, dev, sink):
-        out, saved, buf = dev.ref_loss_f32(cls.MAP, img, params, ref, planar, flags, want_out=keep_out, status=status)
-        ctx.save_for_backward(img, params, saved, ref)
-        ctx.dev, ctx.planar, ctx.flags, ctx.keep_out = dev, planar, flags, keep_out
-        ctx.set_materialize_grads(False)
-        if sink is not None:
-            sink.append(buf)
-        return (out, buf[0], buf[1]) if keep_out else (buf[0], buf[1])
-
-    @classmethod
-    def _grad(cls, ctx, grads):
-        img, params, saved, ref = ctx.saved_tensors
-        grad_out, grad_l1, grad_l2 = grads if ctx.keep_out else (None,) + tuple(grads)
-        none = (None,) * 7
-        if grad_out is None and grad_l1 is None and grad_l2 is None:
-            return (None, None) + none
-        grad_img, grad_params = _loss_backward(ctx, cls.MAP, img, params, saved, ref, grad_l1, grad_l2, grad_out)
-        return (grad_img, grad_params if ctx.needs_input_grad[1] else None) + none
-
-
-class DiffEnhanceLossFunction(_ModuleLossFunction):
-    """``vgg_16_UIE.DifferentiableEnhancement`` with the loss fused in (uwie_ref_loss_f32, UWIE_LOSS_VGG): ``img``,
-    ``params`` and ``flags`` as in ``DiffEnhanceFunction``, ``ref`` in ``img``'s layout.  Outputs ``(l1, l2)``, or
-    ``(out, l1, l2)`` with ``keep_out``; gradients reach ``img`` and ``params`` as through ``DiffEnhanceFunction``."""
-
-    MAP = _lib.LOSS_VGG
-
-    @staticmethod
-    def forward(ctx, img, params, ref, flags, planar, keep_out, status, dev, sink=None):
-        return DiffEnhanceLossFunction._run(ctx, img, params, ref, flags, planar, keep_out, status, dev, sink)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        return DiffEnhanceLossFunction._grad(ctx, grads)
-
-
-class GatedDiffEnhanceLossFunction(_ModuleLossFunction):
-    """``deep_learning_parameters.DifferentiableEnhancement`` with the loss fused in (UWIE_LOSS_GATED): as
-    ``GatedDiffEnhanceFunction`` (``flags`` 0), outputs as ``DiffEnhanceLossFunction``.  An image without a valid sorted
-    position makes l1, l2 NaN and sets UWIE_STATUS_DIFF_RANK; this function does not check it."""
-
-    MAP = _lib.LOSS_GATED
-
-    @staticmethod
-    def forward(ctx, img, params, ref, flags, planar, keep_out, status, dev, sink=None):
-        return GatedDiffEnhanceLossFunction._run(ctx, img, params, ref, flags, planar, keep_out, status, dev, sink)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        return GatedDiffEnhanceLossFunction._grad(ctx, grads)
-
-
-def _loss_reference(dev: Device, x, references):
-    """The reference batch of a fused call: float32, x's shape, on x's device (ValueError otherwise)."""
-    if not isinstance(references, torch.Tensor):
-        references = np.asarray(references)
-        if references.dtype != np.float32:
-            raise ValueError(f"expected a float32 reference batch, got {references.dtype}")
-        references = dev.tensor(np.ascontiguousarray(references))
-    if references.dtype != torch.float32:
-        raise ValueError(f"expected a float32 reference batch, got {references.dtype}")
-    if tuple(references.shape) != tuple(x.shape):
-        raise ValueError(f"the reference batch {tuple(references.shape)} does not match the image batch {tuple(x.shape)}")
-    return references.to(dev.torch_device).contiguous()
-
-
-def _module_loss(module, images, params, references, keep_out: bool, status: bool, sink):
-    """The fused step for either module class: (dev, outputs of its loss Function, the image batch)."""
-    if isinstance(module, GatedDifferentiableEnhancement):
-        vals = [params[k] for k in module.KEYS]  # KeyError in the reference's order
-        dev = get_device(module.device)
-        x = module._image(dev, images)
-        try:
-            ref = _loss_reference(dev, x, references)
-        except ValueError:
-            with torch.no_grad():
-                module(x, params)  # the module's own errors (an unindexable position) come first, as in the reference
-            raise
-        B = x.shape[0]
-        grad = module._wants_grad(x, params)
-        cols = []
-        for key, v in zip(module.KEYS, vals):
-            v = (v.to(device=dev.torch_device, dtype=torch.float32) if isinstance(v, torch.Tensor)
-                 else torch.as_tensor(np.asarray(v, dtype=np.float32), device=dev.torch_device))
-            if key in ("L_low", "L_high") or not grad:
-                v = v.detach()
-            cols.append(torch.broadcast_to(v.reshape(-1), (B,)))
-        pt = torch.stack(cols, dim=1).contiguous()
-        res = GatedDiffEnhanceLossFunction.apply(x, pt, ref, 0, True, keep_out, status, dev, sink)
-        return dev, res, x, pt
-    if isinstance(module, DifferentiableEnhancement):
-        dev = get_device(module.device)
-        x = images.to(dev.torch_device) if isinstance(images, torch.Tensor) else dev.tensor(np.ascontiguousarray(images, dtype=np.float32))
-        if x.dtype != torch.float32:
-            raise ValueError(f"expected a float32 image batch, got {x.dtype}")
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError(f"expected a (B, 3, H, W) image batch, got {tuple(x.shape)}")
-        ref = _loss_reference(dev, x, references)
-        B = x.shape[0]
-        cols = []
-        for key, default in (("L_low", None), ("L_high", None), ("omega", 0.0), ("gamma", 1.0)):
-            if key in params:
-                v = params[key]
-                v = (v.to(device=dev.torch_device, dtype=torch.float32) if isinstance(v, torch.Tensor)
-                     else torch.as_tensor(np.asarray(v, dtype=np.float32), device=dev.torch_device))
-                if key in ("L_low", "L_high"):
-                    v = v.detach()
-                cols.append(torch.broadcast_to(v.reshape(-1), (B,)))
-            elif default is None:
-                raise KeyError(key)
-            else:
-                cols.append(torch.full((B,), default, dtype=torch.float32, device=dev.torch_device))
-        flags = (1 if "omega" in params else 0) | (2 if "gamma" in params else 0)
-        pt = torch.stack(cols, dim=1).contiguous()
-        res = DiffEnhanceLossFunction.apply(x, pt, ref, flags, True, keep_out, status, dev, sink)
-        return dev, res, x, pt
-    raise TypeError(f"expected a DifferentiableEnhancement or GatedDifferentiableEnhancement, got {type(module).__name__}")
-
-
-def _read_loss(dev: Device, buf, x=None, pt=None, extra=None):
-    """The one host read of a fused call: buf = {l1, l2, status bits} -> (l1, l2) as Python floats.  A flagged sorted position
-    raises the reference's exception (first), any other status bit UwieError.  ``extra`` (a device float32 [1], e.g. the
-    perceptual loss) comes back in the same copy, as a third value."""
-    host = (buf[:3] if extra is None else torch.cat([buf[:3], extra.reshape(1)])).cpu()
-    bits = int(host[2:3].view(torch.int32).item()) & 0xFFFFFFFF
-    if bits & _lib.STATUS_DIFF_RANK and pt is not None:
-        _raise_rank_error(pt[:, :2].detach().cpu().numpy(), x.shape[2] * x.shape[3])
-        raise _lib.UwieError("diff_gated: the device flagged a sorted position that the host finds valid")
-    if bits:
-        raise _lib.UwieError(f"device status 0x{bits:x}: the results of the calls since the last check are not valid "
-                             "(include/uwie.h UWIE_STATUS_*)")
-    if extra is not None:
-        return float(host[0]), float(host[1]), float(host[3])
-    return float(host[0]), float(host[1])
-
-
-def _with_loss(module, images, params, references):
-    status = isinstance(module, GatedDifferentiableEnhancement)  # the module waits once per call; the vgg module does not
-    sink = []
-    dev, (out, l1, l2), x, pt = _module_loss(module, images, params, references, True, status, sink)
-    if status:
-        _read_loss(dev, sink[0], x, pt)
-    return out, l1, l2
-
-
-class ReferenceLoss(torch.nn.Module):
-    """``deep_learning_parameters.ReferenceLoss`` (:170-196): ``loss, parts = crit(enhanced, reference)`` with
-    ``loss = l1_weight * L1 + l2_weight * MSE`` (0-dim, with ``grad_fn``) and ``parts = {'l1': float, 'l2': float}``.
-
-    float32 ROCm tensors of one shape take the device kernels (uwie_ref_loss_f32, one host read per call for ``parts``); the
-    gradient of ``enhanced`` is torch CPU autograd's, bit for bit.  Other inputs -- different shapes (torch broadcasts them,
-    with its warning), CPU tensors, other dtypes, a reference that requires grad -- go through torch's ``l1_loss`` /
-    ``mse_loss``, as in the reference.
-
-    ``crit.through(module, images, params, references)``: the same ``(loss, parts)`` for ``module(images, params)`` (a
-    ``GatedDifferentiableEnhancement`` or ``DifferentiableEnhancement``) with the loss fused into the module's sweeps: no
-    enhanced tensor is written, and the backward forms dL/d(enhanced) in registers.
-    """
-
-    def __init__(self, l1_weight=0.5, l2_weight=0.5, device: int | None = None):
-        super().__init__()
-        self.l1_weight = l1_weight
-        self.l2_weight = l2_weight
-        self.device = device
-
-    @staticmethod
-    def _takes(enhanced, reference) -> bool:
-        return (isinstance(enhanced, torch.Tensor) and isinstance(reference, torch.Tensor) and enhanced.is_cuda
-                and reference.is_cuda and enhanced.device == reference.device and enhanced.dtype == torch.float32
-                and reference.dtype == torch.float32 and tuple(enhanced.shape) == tuple(reference.shape)
-                and enhanced.numel() > 0 and enhanced.numel() % 3 == 0 and not reference.requires_grad)
-
-    def forward(self, enhanced, reference):
-        if not self._takes(enhanced, reference):
-            l1 = torch.nn.functional.l1_loss(enhanced, reference)
-            l2 = torch.nn.functional.mse_loss(enhanced, reference)
-            return self.l1_weight * l1 + self.l2_weight * l2, {"l1": l1.item(), "l2": l2.item()}
-        dev = get_device(enhanced.device.index)
-        shape = tuple(enhanced.shape)
-        if not (len(shape) == 4 and shape[1] == 3):
-            shape = (1, 3, 1, enhanced.numel() // 3)  # the identity map sums every value: any layout
-        sink = []
-        l1, l2 = RefLossFunction.apply(enhanced.contiguous().view(shape), reference.contiguous().view(shape), dev, sink)
-        host = sink[0][:2].cpu()
-        return self.l1_weight * l1 + self.l2_weight * l2, {"l1": float(host[0]), "l2": float(host[1])}
-
-    def through(self, module, images, params, references):
-        """``crit(module(images, params), references)`` in one fused step: ``(loss, parts)``, one host read per call (the
-        loss values and the device status together).  A gated module's unindexable sorted position raises the module's
-        exception; a reference that is not float32 or not ``images``' shape raises ValueError."""
-        if isinstance(references, torch.Tensor) and references.requires_grad:
-            return self(module(images, params), references)
-        sink = []
-        dev, (l1, l2), x, pt = _module_loss(module, images, params, references, False, True, sink)
-        v1, v2 = _read_loss(dev, sink[0], x, pt if isinstance(module, GatedDifferentiableEnhancement) else None)
-        return self.l1_weight * l1 + self.l2_weight * l2, {"l1": v1, "l2": v2}
 
 
 # ------------------------------------------------------------------ PerceptualLoss / CombinedLoss (vgg_16_UIE.py:257-303, N10)
@@ -889,11 +421,11 @@ class CombinedLoss(torch.nn.Module):
         precision = PerceptualLoss._route(out, ref)
         if precision is None:
             p = self.perceptual_loss(out, ref)
-            v1, v2 = _read_loss(dev, sink[0], x, pt if isinstance(module, GatedDifferentiableEnhancement) else None)
+            v1, v2 = _read_loss(dev, sink[0], x, pt)
             return self._total(l1, l2, p), {"l1": v1, "l2": v2, "perceptual": p.item()}
         psink = []
         p = self.perceptual_loss._device_loss(out, ref, precision, psink)
-        v1, v2, vp = _read_loss(dev, sink[0], x, pt if isinstance(module, GatedDifferentiableEnhancement) else None, psink[0][:1])
+        v1, v2, vp = _read_loss(dev, sink[0], x, pt, psink[0][:1])
         return self._total(l1, l2, p), {"l1": v1, "l2": v2, "perceptual": vp}
 
 

@@ -1072,6 +1072,45 @@ int uwie_select_best_u8(uwie_ctx *ctx, const uint8_t *d_in, int batch, int H, in
     return launch_pick_best(d_scores, n, s, all, d_best, d_best_u8, st);
 }
 
+// The two enhancement modules (k_diffenh.hip): map is UWIE_LOSS_VGG (vgg_16_UIE.DifferentiableEnhancement) or
+// UWIE_LOSS_GATED (deep_learning_parameters.DifferentiableEnhancement, whose flags are reserved: 0).
+// The common start of their forwards: the module's sorted positions, then the selection.  *os = the order statistics.
+static int module_select(uwie_ctx *ctx, int map, const float *d_img, int planar, Shape s, const float *d_params, void *sel_ws,
+                         hipStream_t st, const float **os)
+{
+    SelectPlan plan;
+    if (map == UWIE_LOSS_VGG) UWIE_TRY(select_begin_stretch_ranks(s, d_params, 4, sel_ws, st, &plan));
+    else UWIE_TRY(select_begin_gated_ranks(s, d_params, 4, ctx->d_status, sel_ws, st, &plan));
+    UWIE_TRY(select_run(plan, d_img, planar, s, false, st));
+    *os = (const float *)plan.os;
+    return UWIE_OK;
+}
+
+// a module forward after its entry point's own checks (d_saved: the _save_f32 form)
+static int module_fwd(uwie_ctx *ctx, int map, const float *d_img, float *d_out, int batch, int H, int W, int planar,
+                      const float *d_params, int flags, float *d_saved, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    const Shape s{batch, H, W};
+    UWIE_CHECK_WS(select_ws_bytes(s));
+    hipStream_t st = (hipStream_t)stream;
+    const float *os = nullptr;
+    UWIE_TRY(module_select(ctx, map, d_img, planar ? 1 : 0, s, d_params, d_workspace, st, &os));
+    if (map == UWIE_LOSS_VGG) return launch_diff_enhance(d_img, planar ? 1 : 0, s, d_params, flags, os, d_out, st, d_saved);
+    return launch_diff_gated(d_img, planar ? 1 : 0, s, d_params, os, d_out, st, d_saved);
+}
+
+// a module backward after its entry point's NULL, shape and flags checks: alias is that entry point's message
+static int module_bwd(int map, const float *d_img, const float *d_params, int flags, int planar, int batch, int H, int W,
+                      const float *d_saved, const float *d_grad_out, float *d_grad_img, float *d_grad_params, const char *alias,
+                      void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE((const void *)d_grad_img != (const void *)d_img && (const void *)d_grad_img != (const void *)d_grad_out, alias);
+    const Shape s{batch, H, W};
+    UWIE_CHECK_WS(diff_enhance_bwd_ws_bytes(s));
+    return launch_module_bwd(map, d_img, planar ? 1 : 0, s, d_params, flags, d_saved, nullptr, d_grad_out, nullptr, d_grad_img,
+                             d_grad_params, d_workspace, (hipStream_t)stream);
+}
+
 int uwie_diff_enhance_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, int planar,
                           const float *d_params, int flags, void *d_workspace, size_t workspace_bytes, void *stream)
 {
@@ -1079,13 +1118,8 @@ int uwie_diff_enhance_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int b
     UWIE_SCOPE(ctx);
     UWIE_CHECK_SHAPE(batch, H, W);
     UWIE_REQUIRE((flags & ~3) == 0, "diff_enhance: flags are UWIE_DIFF_OMEGA | UWIE_DIFF_GAMMA");
-    const Shape s{batch, H, W};
-    UWIE_CHECK_WS(select_ws_bytes(s));
-    hipStream_t st = (hipStream_t)stream;
-    SelectPlan plan;
-    UWIE_TRY(select_begin_stretch_ranks(s, d_params, 4, d_workspace, st, &plan));
-    UWIE_TRY(select_run(plan, d_img, planar ? 1 : 0, s, false, st));
-    return launch_diff_enhance(d_img, planar ? 1 : 0, s, d_params, flags, (const float *)plan.os, d_out, st);
+    return module_fwd(ctx, UWIE_LOSS_VGG, d_img, d_out, batch, H, W, planar, d_params, flags, nullptr, d_workspace, workspace_bytes,
+                      stream);
 }
 
 int uwie_diff_enhance_save_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, int planar,
@@ -1096,13 +1130,8 @@ int uwie_diff_enhance_save_f32(uwie_ctx *ctx, const float *d_img, float *d_out, 
     UWIE_SCOPE(ctx);
     UWIE_CHECK_SHAPE(batch, H, W);
     UWIE_REQUIRE((flags & ~3) == 0, "diff_enhance_save: flags are UWIE_DIFF_OMEGA | UWIE_DIFF_GAMMA");
-    const Shape s{batch, H, W};
-    UWIE_CHECK_WS(select_ws_bytes(s));
-    hipStream_t st = (hipStream_t)stream;
-    SelectPlan plan;
-    UWIE_TRY(select_begin_stretch_ranks(s, d_params, 4, d_workspace, st, &plan));
-    UWIE_TRY(select_run(plan, d_img, planar ? 1 : 0, s, false, st));
-    return launch_diff_enhance(d_img, planar ? 1 : 0, s, d_params, flags, (const float *)plan.os, d_out, st, d_saved);
+    return module_fwd(ctx, UWIE_LOSS_VGG, d_img, d_out, batch, H, W, planar, d_params, flags, d_saved, d_workspace, workspace_bytes,
+                      stream);
 }
 
 size_t uwie_diff_enhance_bwd_workspace_bytes(int batch, int H, int W)
@@ -1119,25 +1148,8 @@ int uwie_diff_enhance_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_
     UWIE_SCOPE(ctx);
     UWIE_CHECK_SHAPE(batch, H, W);
     UWIE_REQUIRE((flags & ~3) == 0, "diff_enhance_bwd: flags are UWIE_DIFF_OMEGA | UWIE_DIFF_GAMMA");
-    UWIE_REQUIRE((const void *)d_grad_img != (const void *)d_img && (const void *)d_grad_img != (const void *)d_grad_out,
-                 "diff_enhance_bwd: d_grad_img must not alias d_img or d_grad_out");
-    const Shape s{batch, H, W};
-    UWIE_CHECK_WS(diff_enhance_bwd_ws_bytes(s));
-    return launch_diff_enhance_bwd(d_img, planar ? 1 : 0, s, d_params, flags, d_saved, d_grad_out, d_grad_img, d_grad_params,
-                                   d_workspace, (hipStream_t)stream);
-}
-
-// deep_learning_parameters.DifferentiableEnhancement: flags is reserved (0)
-static int diff_gated_fwd(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, int planar,
-                          const float *d_params, float *d_saved, void *d_workspace, size_t workspace_bytes, void *stream)
-{
-    const Shape s{batch, H, W};
-    UWIE_CHECK_WS(select_ws_bytes(s));
-    hipStream_t st = (hipStream_t)stream;
-    SelectPlan plan;
-    UWIE_TRY(select_begin_gated_ranks(s, d_params, 4, ctx->d_status, d_workspace, st, &plan));
-    UWIE_TRY(select_run(plan, d_img, planar ? 1 : 0, s, false, st));
-    return launch_diff_gated(d_img, planar ? 1 : 0, s, d_params, (const float *)plan.os, d_out, st, d_saved);
+    return module_bwd(UWIE_LOSS_VGG, d_img, d_params, flags, planar, batch, H, W, d_saved, d_grad_out, d_grad_img, d_grad_params,
+                      "diff_enhance_bwd: d_grad_img must not alias d_img or d_grad_out", d_workspace, workspace_bytes, stream);
 }
 
 int uwie_diff_gated_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, int planar,
@@ -1147,7 +1159,8 @@ int uwie_diff_gated_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int bat
     UWIE_SCOPE(ctx);
     UWIE_CHECK_SHAPE(batch, H, W);
     UWIE_REQUIRE(flags == 0, "diff_gated: flags are reserved (0)");
-    return diff_gated_fwd(ctx, d_img, d_out, batch, H, W, planar, d_params, nullptr, d_workspace, workspace_bytes, stream);
+    return module_fwd(ctx, UWIE_LOSS_GATED, d_img, d_out, batch, H, W, planar, d_params, 0, nullptr, d_workspace, workspace_bytes,
+                      stream);
 }
 
 int uwie_diff_gated_save_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, int planar,
@@ -1158,13 +1171,13 @@ int uwie_diff_gated_save_f32(uwie_ctx *ctx, const float *d_img, float *d_out, in
     UWIE_SCOPE(ctx);
     UWIE_CHECK_SHAPE(batch, H, W);
     UWIE_REQUIRE(flags == 0, "diff_gated_save: flags are reserved (0)");
-    return diff_gated_fwd(ctx, d_img, d_out, batch, H, W, planar, d_params, d_saved, d_workspace, workspace_bytes, stream);
+    return module_fwd(ctx, UWIE_LOSS_GATED, d_img, d_out, batch, H, W, planar, d_params, 0, d_saved, d_workspace, workspace_bytes,
+                      stream);
 }
 
 size_t uwie_diff_gated_bwd_workspace_bytes(int batch, int H, int W)
 {
-    if (!shape_ok(batch, H, W)) return 0;
-    return diff_enhance_bwd_ws_bytes(Shape{batch, H, W});
+    return uwie_diff_enhance_bwd_workspace_bytes(batch, H, W);  // the same partials
 }
 
 int uwie_diff_gated_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_params, int flags, int planar, int batch, int H,
@@ -1175,12 +1188,8 @@ int uwie_diff_gated_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_pa
     UWIE_SCOPE(ctx);
     UWIE_CHECK_SHAPE(batch, H, W);
     UWIE_REQUIRE(flags == 0, "diff_gated_bwd: flags are reserved (0)");
-    UWIE_REQUIRE((const void *)d_grad_img != (const void *)d_img && (const void *)d_grad_img != (const void *)d_grad_out,
-                 "diff_gated_bwd: d_grad_img must not alias d_img or d_grad_out");
-    const Shape s{batch, H, W};
-    UWIE_CHECK_WS(diff_enhance_bwd_ws_bytes(s));
-    return launch_diff_gated_bwd(d_img, planar ? 1 : 0, s, d_params, d_saved, d_grad_out, d_grad_img, d_grad_params, d_workspace,
-                                 (hipStream_t)stream);
+    return module_bwd(UWIE_LOSS_GATED, d_img, d_params, 0, planar, batch, H, W, d_saved, d_grad_out, d_grad_img, d_grad_params,
+                      "diff_gated_bwd: d_grad_img must not alias d_img or d_grad_out", d_workspace, workspace_bytes, stream);
 }
 
 // ReferenceLoss: the forward workspace holds the selection and the loss partials; the backward's is the module backward's
@@ -1228,11 +1237,7 @@ int uwie_ref_loss_f32(uwie_ctx *ctx, int map, const float *d_img, const float *d
     void *loss_ws = c.take<char>(refloss_ws_bytes(s));
     const float *os = nullptr;
     if (map != UWIE_LOSS_IDENTITY) {
-        SelectPlan plan;
-        if (map == UWIE_LOSS_VGG) UWIE_TRY(select_begin_stretch_ranks(s, d_params, 4, sel_ws, st, &plan));
-        else UWIE_TRY(select_begin_gated_ranks(s, d_params, 4, ctx->d_status, sel_ws, st, &plan));
-        UWIE_TRY(select_run(plan, d_img, planar ? 1 : 0, s, false, st));
-        os = (const float *)plan.os;
+        UWIE_TRY(module_select(ctx, map, d_img, planar ? 1 : 0, s, d_params, sel_ws, st, &os));
     } else {
         d_out = nullptr;
         d_saved = nullptr;

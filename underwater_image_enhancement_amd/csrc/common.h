@@ -411,16 +411,17 @@ int select_begin_gated_ranks(Shape s, const float *d_params, int stride, uint32_
 // d_saved (optional): [B][3][2] float = {p_lo, p_hi} per plane, what the backward needs from the forward
 int launch_diff_enhance(const float *d_img, int planar, Shape s, const float *d_params, int flags, const float *d_os,
                         float *d_out, hipStream_t st, float *d_saved = nullptr);
-// its gradient (two launches: per-block partials, then a fixed-order finish and the sorted-position scatter)
-size_t diff_enhance_bwd_ws_bytes(Shape s);
-int launch_diff_enhance_bwd(const float *d_img, int planar, Shape s, const float *d_params, int flags, const float *d_saved,
-                            const float *d_grad_out, float *d_grad_img, float *d_grad_params, void *ws, hipStream_t st);
-// k_diffenh.hip: deep_learning_parameters.DifferentiableEnhancement.forward (:32-55), the gated gamma module, and its
-// gradient (params [B][4] = L_low, L_high, use_gamma, gamma; images without a valid sorted position get NaN)
+// k_diffenh.hip: deep_learning_parameters.DifferentiableEnhancement.forward (:32-55), the gated gamma module
+// (params [B][4] = L_low, L_high, use_gamma, gamma; images without a valid sorted position get NaN)
 int launch_diff_gated(const float *d_img, int planar, Shape s, const float *d_params, const float *d_os, float *d_out,
                       hipStream_t st, float *d_saved = nullptr);
-int launch_diff_gated_bwd(const float *d_img, int planar, Shape s, const float *d_params, const float *d_saved,
-                          const float *d_grad_out, float *d_grad_img, float *d_grad_params, void *ws, hipStream_t st);
+// the gradient of either module, map = UWIE_LOSS_VGG / UWIE_LOSS_GATED (two launches: per-block partials, then a fixed-order
+// finish and the sorted-position scatter).  With d_grad_loss the sweep adds ReferenceLoss's gradient against d_ref (below);
+// without (nullptr, d_ref unused) it is the plain module backward of d_grad_out.
+size_t diff_enhance_bwd_ws_bytes(Shape s);
+int launch_module_bwd(int map, const float *d_img, int planar, Shape s, const float *d_params, int flags, const float *d_saved,
+                      const float *d_ref, const float *d_grad_out, const float *d_grad_loss, float *d_grad_img,
+                      float *d_grad_params, void *ws, hipStream_t st);
 // k_diffenh.hip: ReferenceLoss (l1 = mean|o - r|, l2 = mean((o - r)^2)) fused into the module sweeps; map = UWIE_LOSS_*.
 // Forward: after the selection (d_os; not read for the identity map), writes d_loss [2] and optionally d_out / d_saved.
 // Backward: the module's backward with the loss gradient (d_grad_loss [2] on the device) in place of grad_out.

@@ -713,6 +713,25 @@ BwdGeom bwd_geom(Shape s)
     return {cdiv(n, chunk), chunk};
 }
 
+// the backward sweep's per-block partials in the workspace (nullptr: sizing)
+struct BwdPart {
+    double *part;
+    uint32_t *cnt;
+};
+BwdPart carve_bwd(Carver &c, Shape s, BwdGeom g)
+{
+    return {c.take<double>((size_t)s.B * g.gx * kPartD), c.take<uint32_t>((size_t)s.B * g.gx * kPartU)};  // (in this order)
+}
+
+// LAUNCH(K<flags & 3>) for a launch macro LAUNCH(kernel) and a template <int FLAGS> kernel K
+#define UWIE_FOR_FLAGS(LAUNCH, K, flags) \
+    switch ((flags) & 3) {               \
+    case 0: LAUNCH(K<0>); break;         \
+    case 1: LAUNCH(K<1>); break;         \
+    case 2: LAUNCH(K<2>); break;         \
+    default: LAUNCH(K<3>); break;        \
+    }
+
 }  // namespace
 
 int launch_diff_enhance(const float *d_img, int planar, Shape s, const float *d_params, int flags, const float *d_os,
@@ -721,37 +740,6 @@ int launch_diff_enhance(const float *d_img, int planar, Shape s, const float *d_
     const int n = (int)s.npx();
     UWIE_LAUNCH(k_diff_enhance, dim3(grid_for(n, 4096), s.B), dim3(256), 0, st, d_img, planar, n, d_params, flags, d_os,
                 d_out, d_saved);
-    UWIE_LAUNCH_CHECK();
-    return UWIE_OK;
-}
-
-size_t diff_enhance_bwd_ws_bytes(Shape s)
-{
-    const BwdGeom g = bwd_geom(s);
-    Carver c(nullptr);
-    c.take<double>((size_t)s.B * g.gx * kPartD);
-    c.take<uint32_t>((size_t)s.B * g.gx * kPartU);
-    return c.total();
-}
-
-int launch_diff_enhance_bwd(const float *d_img, int planar, Shape s, const float *d_params, int flags, const float *d_saved,
-                            const float *d_grad_out, float *d_grad_img, float *d_grad_params, void *ws, hipStream_t st)
-{
-    const int n = (int)s.npx();
-    const BwdGeom g = bwd_geom(s);
-    Carver c(ws);
-    double *part = c.take<double>((size_t)s.B * g.gx * kPartD);
-    uint32_t *cnt = c.take<uint32_t>((size_t)s.B * g.gx * kPartU);
-    const dim3 grid(g.gx, s.B);
-    switch (flags & 3) {
-    case 0: UWIE_LAUNCH(k_diff_enhance_bwd<0>, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_grad_img, part, cnt); break;
-    case 1: UWIE_LAUNCH(k_diff_enhance_bwd<1>, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_grad_img, part, cnt); break;
-    case 2: UWIE_LAUNCH(k_diff_enhance_bwd<2>, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_grad_img, part, cnt); break;
-    default: UWIE_LAUNCH(k_diff_enhance_bwd<3>, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_grad_img, part, cnt); break;
-    }
-    UWIE_LAUNCH_CHECK();
-    UWIE_LAUNCH(k_diff_enhance_bwd_finish<false>, dim3(3, s.B), dim3(256), 0, st, d_img, planar, n, g.chunk, g.gx, d_params,
-                d_saved, part, cnt, d_grad_img, d_grad_params);
     UWIE_LAUNCH_CHECK();
     return UWIE_OK;
 }
@@ -765,19 +753,48 @@ int launch_diff_gated(const float *d_img, int planar, Shape s, const float *d_pa
     return UWIE_OK;
 }
 
-int launch_diff_gated_bwd(const float *d_img, int planar, Shape s, const float *d_params, const float *d_saved,
-                          const float *d_grad_out, float *d_grad_img, float *d_grad_params, void *ws, hipStream_t st)
+size_t diff_enhance_bwd_ws_bytes(Shape s)
+{
+    Carver c(nullptr);
+    carve_bwd(c, s, bwd_geom(s));
+    return c.total();
+}
+
+static LossGrad loss_grad_args(Shape s, const float *d_grad_loss)
+{
+    const long long N = (long long)s.B * 3 * (long long)s.npx();
+    return LossGrad{d_grad_loss, (float)N, (float)(2.0 / (double)N)};
+}
+
+int launch_module_bwd(int map, const float *d_img, int planar, Shape s, const float *d_params, int flags, const float *d_saved,
+                      const float *d_ref, const float *d_grad_out, const float *d_grad_loss, float *d_grad_img,
+                      float *d_grad_params, void *ws, hipStream_t st)
 {
     const int n = (int)s.npx();
     const BwdGeom g = bwd_geom(s);
     Carver c(ws);
-    double *part = c.take<double>((size_t)s.B * g.gx * kPartD);
-    uint32_t *cnt = c.take<uint32_t>((size_t)s.B * g.gx * kPartU);
-    UWIE_LAUNCH(k_diff_gated_bwd, dim3(g.gx, s.B), dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out,
-                d_grad_img, part, cnt);
+    const BwdPart p = carve_bwd(c, s, g);
+    const dim3 grid(g.gx, s.B);
+#define UWIE_BWD(K) \
+    UWIE_LAUNCH(K, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_grad_img, p.part, p.cnt)
+#define UWIE_LOSS_BWD(K) \
+    UWIE_LAUNCH(K, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_ref, lg, d_grad_img, p.part, p.cnt)
+#define UWIE_BWD_FINISH(K) \
+    UWIE_LAUNCH(K, dim3(3, s.B), dim3(256), 0, st, d_img, planar, n, g.chunk, g.gx, d_params, d_saved, p.part, p.cnt, d_grad_img, d_grad_params)
+    if (d_grad_loss) {
+        const LossGrad lg = loss_grad_args(s, d_grad_loss);
+        if (map == kMapGated) UWIE_LOSS_BWD(k_diff_gated_loss_bwd);
+        else UWIE_FOR_FLAGS(UWIE_LOSS_BWD, k_diff_enhance_loss_bwd, flags);
+    } else {
+        if (map == kMapGated) UWIE_BWD(k_diff_gated_bwd);
+        else UWIE_FOR_FLAGS(UWIE_BWD, k_diff_enhance_bwd, flags);
+    }
     UWIE_LAUNCH_CHECK();
-    UWIE_LAUNCH(k_diff_enhance_bwd_finish<true>, dim3(3, s.B), dim3(256), 0, st, d_img, planar, n, g.chunk, g.gx, d_params,
-                d_saved, part, cnt, d_grad_img, d_grad_params);
+    if (map == kMapGated) UWIE_BWD_FINISH(k_diff_enhance_bwd_finish<true>);
+    else UWIE_BWD_FINISH(k_diff_enhance_bwd_finish<false>);
+#undef UWIE_BWD
+#undef UWIE_LOSS_BWD
+#undef UWIE_BWD_FINISH
     UWIE_LAUNCH_CHECK();
     return UWIE_OK;
 }
@@ -791,12 +808,6 @@ size_t refloss_ws_bytes(Shape s)
     return c.total();
 }
 
-static LossGrad loss_grad_args(Shape s, const float *d_grad_loss)
-{
-    const long long N = (long long)s.B * 3 * (long long)s.npx();
-    return LossGrad{d_grad_loss, (float)N, (float)(2.0 / (double)N)};
-}
-
 int launch_refloss(int map, const float *d_img, int planar, Shape s, const float *d_params, int flags, const float *d_os,
                    const float *d_ref, float *d_out, float *d_saved, float *d_loss, void *ws, hipStream_t st)
 {
@@ -808,12 +819,7 @@ int launch_refloss(int map, const float *d_img, int planar, Shape s, const float
 #define UWIE_REFLOSS_FWD(K) UWIE_LAUNCH(K, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_os, d_ref, d_out, d_saved, part)
     if (map == kMapIdentity) UWIE_REFLOSS_FWD(k_refloss_identity);
     else if (map == kMapGated) UWIE_REFLOSS_FWD(k_refloss_gated);
-    else switch (flags & 3) {
-        case 0: UWIE_REFLOSS_FWD(k_refloss_vgg<0>); break;
-        case 1: UWIE_REFLOSS_FWD(k_refloss_vgg<1>); break;
-        case 2: UWIE_REFLOSS_FWD(k_refloss_vgg<2>); break;
-        default: UWIE_REFLOSS_FWD(k_refloss_vgg<3>); break;
-        }
+    else UWIE_FOR_FLAGS(UWIE_REFLOSS_FWD, k_refloss_vgg, flags);
 #undef UWIE_REFLOSS_FWD
     UWIE_LAUNCH_CHECK();
     const double count = (double)s.B * 3.0 * (double)s.npx();
@@ -826,37 +832,12 @@ int launch_refloss_bwd(int map, const float *d_img, int planar, Shape s, const f
                        const float *d_ref, const float *d_grad_out, const float *d_grad_loss, float *d_grad_img,
                        float *d_grad_params, void *ws, hipStream_t st)
 {
-    const LossGrad lg = loss_grad_args(s, d_grad_loss);
-    if (map == kMapIdentity) {
-        const size_t total = (size_t)s.B * 3 * s.npx();
-        UWIE_LAUNCH(k_refloss_identity_bwd, dim3(grid_for(total)), dim3(256), 0, st, d_img, d_ref, d_grad_out, lg, total, d_grad_img);
-        UWIE_LAUNCH_CHECK();
-        return UWIE_OK;
-    }
-    const int n = (int)s.npx();
-    const BwdGeom g = bwd_geom(s);
-    Carver c(ws);
-    double *part = c.take<double>((size_t)s.B * g.gx * kPartD);
-    uint32_t *cnt = c.take<uint32_t>((size_t)s.B * g.gx * kPartU);
-    const dim3 grid(g.gx, s.B);
-    if (map == kMapGated) {
-        UWIE_LAUNCH(k_diff_gated_loss_bwd, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_ref, lg,
-                    d_grad_img, part, cnt);
-    } else {
-        switch (flags & 3) {
-        case 0: UWIE_LAUNCH(k_diff_enhance_loss_bwd<0>, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_ref, lg, d_grad_img, part, cnt); break;
-        case 1: UWIE_LAUNCH(k_diff_enhance_loss_bwd<1>, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_ref, lg, d_grad_img, part, cnt); break;
-        case 2: UWIE_LAUNCH(k_diff_enhance_loss_bwd<2>, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_ref, lg, d_grad_img, part, cnt); break;
-        default: UWIE_LAUNCH(k_diff_enhance_loss_bwd<3>, grid, dim3(256), 0, st, d_img, planar, n, g.chunk, d_params, d_saved, d_grad_out, d_ref, lg, d_grad_img, part, cnt); break;
-        }
-    }
-    UWIE_LAUNCH_CHECK();
-    if (map == kMapGated)
-        UWIE_LAUNCH(k_diff_enhance_bwd_finish<true>, dim3(3, s.B), dim3(256), 0, st, d_img, planar, n, g.chunk, g.gx, d_params,
-                    d_saved, part, cnt, d_grad_img, d_grad_params);
-    else
-        UWIE_LAUNCH(k_diff_enhance_bwd_finish<false>, dim3(3, s.B), dim3(256), 0, st, d_img, planar, n, g.chunk, g.gx, d_params,
-                    d_saved, part, cnt, d_grad_img, d_grad_params);
+    if (map != kMapIdentity)
+        return launch_module_bwd(map, d_img, planar, s, d_params, flags, d_saved, d_ref, d_grad_out, d_grad_loss, d_grad_img,
+                                 d_grad_params, ws, st);
+    const size_t total = (size_t)s.B * 3 * s.npx();
+    UWIE_LAUNCH(k_refloss_identity_bwd, dim3(grid_for(total)), dim3(256), 0, st, d_img, d_ref, d_grad_out,
+                loss_grad_args(s, d_grad_loss), total, d_grad_img);
     UWIE_LAUNCH_CHECK();
     return UWIE_OK;
 }

@@ -240,92 +240,68 @@ class Device:
                                            ctypes.cast(p6, ctypes.c_void_p), _ptr(ws), ws.numel(), self.stream()))
         return out, kind
 
-    def diff_enhance_f32(self, img, params, planar: bool, has_omega: bool = True, has_gamma: bool = True):
-        """img: float32 cuda tensor [B,3,H,W] (planar) or [B,H,W,3]; params: float32 [B,4] = L_low, L_high, omega, gamma."""
-        assert img.dtype == torch.float32 and params.dtype == torch.float32 and img.dim() == 4
-        B = img.shape[0]
-        H, W = (img.shape[2], img.shape[3]) if planar else (img.shape[1], img.shape[2])
-        assert img.shape[1 if planar else 3] == 3 and tuple(params.shape) == (B, 4)
-        img, params = img.contiguous(), params.contiguous()
+    # ------------------------------------------------------------------ the enhancement modules (uwie_diff_*, DESIGN.md sections 8, 10)
+    @staticmethod
+    def _module_args(img, params, planar: bool, *same):
+        """The common front of the module bindings: img float32 [B,3,H,W] (planar) or [B,H,W,3], params float32 [B,4] (or
+        None), ``same``: float32 tensors of img's shape (or None).  Returns ((B, H, W), the tensors made contiguous)."""
+        assert img.dtype == torch.float32 and img.dim() == 4 and img.shape[1 if planar else 3] == 3
+        B = int(img.shape[0])
+        H, W = (int(v) for v in (img.shape[2:] if planar else img.shape[1:3]))
+        assert params is None or (params.dtype == torch.float32 and tuple(params.shape) == (B, 4))
+        assert all(t is None or (t.dtype == torch.float32 and tuple(t.shape) == tuple(img.shape)) for t in same)
+        return (B, H, W), [t if t is None else t.contiguous() for t in (img, params) + same]
+
+    def _module_fwd(self, fn, img, params, planar: bool, flags: int, save: bool):
+        """A module forward (fn = uwie_diff_*_f32) or, with ``save``, its _save_f32 form, which also fills saved [B,3,2]."""
+        (B, H, W), (img, params) = self._module_args(img, params, planar)
         ws = self.workspace_for(B, H, W)
         out = self.empty(tuple(img.shape), torch.float32)
-        check(self.lib.uwie_diff_enhance_f32(self._ctx, _ptr(img), _ptr(out), B, H, W, int(planar), _ptr(params),
-                                             (1 if has_omega else 0) | (2 if has_gamma else 0), _ptr(ws), ws.numel(),
-                                             self.stream()))
-        return out
+        saved = self.empty((B, 3, 2), torch.float32) if save else None
+        check(fn(self._ctx, _ptr(img), _ptr(out), B, H, W, int(planar), _ptr(params), int(flags),
+                 *((_ptr(saved),) if save else ()), _ptr(ws), ws.numel(), self.stream()))
+        return (out, saved) if save else out
+
+    def _module_bwd(self, fn, ws_bytes, img, params, saved, grad_out, planar: bool, flags: int, want_img: bool):
+        """A module backward (fn = uwie_diff_*_bwd_f32, ws_bytes its workspace function): (grad_img or None, grad_params)."""
+        (B, H, W), (img, params, grad_out) = self._module_args(img, params, planar, grad_out)
+        ws = self.workspace(ws_bytes(B, H, W))
+        grad_img = self.empty(tuple(img.shape), torch.float32) if want_img else None
+        grad_params = self.empty((B, 4), torch.float32)
+        check(fn(self._ctx, _ptr(img), _ptr(params), int(flags), int(planar), B, H, W, _ptr(saved.contiguous()), _ptr(grad_out),
+                 _ptr(grad_img), _ptr(grad_params), _ptr(ws), ws.numel(), self.stream()))
+        return grad_img, grad_params
+
+    def diff_enhance_f32(self, img, params, planar: bool, has_omega: bool = True, has_gamma: bool = True):
+        """img: float32 cuda tensor [B,3,H,W] (planar) or [B,H,W,3]; params: float32 [B,4] = L_low, L_high, omega, gamma."""
+        flags = (1 if has_omega else 0) | (2 if has_gamma else 0)
+        return self._module_fwd(self.lib.uwie_diff_enhance_f32, img, params, planar, flags, False)
 
     def diff_enhance_save_f32(self, img, params, planar: bool, flags: int):
         """diff_enhance_f32 that also returns what the backward needs: (out, saved float32 [B,3,2] = p_lo, p_hi per plane)."""
-        assert img.dtype == torch.float32 and params.dtype == torch.float32 and img.dim() == 4
-        B = img.shape[0]
-        H, W = (img.shape[2], img.shape[3]) if planar else (img.shape[1], img.shape[2])
-        assert img.shape[1 if planar else 3] == 3 and tuple(params.shape) == (B, 4)
-        img, params = img.contiguous(), params.contiguous()
-        ws = self.workspace_for(B, H, W)
-        out = self.empty(tuple(img.shape), torch.float32)
-        saved = self.empty((B, 3, 2), torch.float32)
-        check(self.lib.uwie_diff_enhance_save_f32(self._ctx, _ptr(img), _ptr(out), B, H, W, int(planar), _ptr(params), int(flags),
-                                                  _ptr(saved), _ptr(ws), ws.numel(), self.stream()))
-        return out, saved
+        return self._module_fwd(self.lib.uwie_diff_enhance_save_f32, img, params, planar, flags, True)
 
     def diff_enhance_bwd_f32(self, img, params, saved, grad_out, planar: bool, flags: int, want_img: bool = True):
         """Gradient of diff_enhance: (grad_img in img's layout or None when not wanted, grad_params float32 [B,4] =
         0, 0, d omega, d gamma)."""
-        assert img.dtype == torch.float32 and grad_out.dtype == torch.float32 and tuple(grad_out.shape) == tuple(img.shape)
-        B = img.shape[0]
-        H, W = (img.shape[2], img.shape[3]) if planar else (img.shape[1], img.shape[2])
-        img, params, saved, grad_out = img.contiguous(), params.contiguous(), saved.contiguous(), grad_out.contiguous()
-        ws = self.workspace(self.lib.uwie_diff_enhance_bwd_workspace_bytes(B, H, W))
-        grad_img = self.empty(tuple(img.shape), torch.float32) if want_img else None
-        grad_params = self.empty((B, 4), torch.float32)
-        check(self.lib.uwie_diff_enhance_bwd_f32(self._ctx, _ptr(img), _ptr(params), int(flags), int(planar), B, H, W, _ptr(saved),
-                                                 _ptr(grad_out), _ptr(grad_img), _ptr(grad_params), _ptr(ws), ws.numel(),
-                                                 self.stream()))
-        return grad_img, grad_params
-
-    def _diff_gated_shape(self, img, params, planar: bool):
-        assert img.dtype == torch.float32 and params.dtype == torch.float32 and img.dim() == 4
-        B = img.shape[0]
-        H, W = (img.shape[2], img.shape[3]) if planar else (img.shape[1], img.shape[2])
-        assert img.shape[1 if planar else 3] == 3 and tuple(params.shape) == (B, 4)
-        return B, H, W
+        return self._module_bwd(self.lib.uwie_diff_enhance_bwd_f32, self.lib.uwie_diff_enhance_bwd_workspace_bytes, img, params,
+                                saved, grad_out, planar, flags, want_img)
 
     def diff_gated_f32(self, img, params, planar: bool):
         """deep_learning_parameters.DifferentiableEnhancement's forward (uwie_diff_gated_f32): img float32 cuda [B,3,H,W]
         (planar) or [B,H,W,3]; params float32 [B,4] = L_low, L_high, use_gamma, gamma.  An image without a valid sorted
         position gets NaN and sets UWIE_STATUS_DIFF_RANK (check_status)."""
-        B, H, W = self._diff_gated_shape(img, params, planar)
-        img, params = img.contiguous(), params.contiguous()
-        ws = self.workspace_for(B, H, W)
-        out = self.empty(tuple(img.shape), torch.float32)
-        check(self.lib.uwie_diff_gated_f32(self._ctx, _ptr(img), _ptr(out), B, H, W, int(planar), _ptr(params), 0, _ptr(ws),
-                                           ws.numel(), self.stream()))
-        return out
+        return self._module_fwd(self.lib.uwie_diff_gated_f32, img, params, planar, 0, False)
 
     def diff_gated_save_f32(self, img, params, planar: bool):
         """diff_gated_f32 that also returns what the backward needs: (out, saved float32 [B,3,2] = p_lo, p_hi per plane)."""
-        B, H, W = self._diff_gated_shape(img, params, planar)
-        img, params = img.contiguous(), params.contiguous()
-        ws = self.workspace_for(B, H, W)
-        out = self.empty(tuple(img.shape), torch.float32)
-        saved = self.empty((B, 3, 2), torch.float32)
-        check(self.lib.uwie_diff_gated_save_f32(self._ctx, _ptr(img), _ptr(out), B, H, W, int(planar), _ptr(params), 0,
-                                                _ptr(saved), _ptr(ws), ws.numel(), self.stream()))
-        return out, saved
+        return self._module_fwd(self.lib.uwie_diff_gated_save_f32, img, params, planar, 0, True)
 
     def diff_gated_bwd_f32(self, img, params, saved, grad_out, planar: bool, want_img: bool = True):
         """Gradient of diff_gated: (grad_img in img's layout or None when not wanted, grad_params float32 [B,4] =
         0, 0, d use_gamma, d gamma)."""
-        assert grad_out.dtype == torch.float32 and tuple(grad_out.shape) == tuple(img.shape)
-        B, H, W = self._diff_gated_shape(img, params, planar)
-        img, params, saved, grad_out = img.contiguous(), params.contiguous(), saved.contiguous(), grad_out.contiguous()
-        ws = self.workspace(self.lib.uwie_diff_gated_bwd_workspace_bytes(B, H, W))
-        grad_img = self.empty(tuple(img.shape), torch.float32) if want_img else None
-        grad_params = self.empty((B, 4), torch.float32)
-        check(self.lib.uwie_diff_gated_bwd_f32(self._ctx, _ptr(img), _ptr(params), 0, int(planar), B, H, W, _ptr(saved),
-                                               _ptr(grad_out), _ptr(grad_img), _ptr(grad_params), _ptr(ws), ws.numel(),
-                                               self.stream()))
-        return grad_img, grad_params
+        return self._module_bwd(self.lib.uwie_diff_gated_bwd_f32, self.lib.uwie_diff_gated_bwd_workspace_bytes, img, params,
+                                saved, grad_out, planar, 0, want_img)
 
     # ------------------------------------------------------------------ ReferenceLoss (uwie_ref_loss_*, DESIGN.md section 13)
     def ref_loss_f32(self, map_: int, img, params, ref, planar: bool, flags: int = 0, want_out: bool = False,
@@ -334,20 +310,13 @@ class Device:
         ref.  Returns (out or None, saved float32 [B,3,2] or None (identity), buf float32 [4]): buf[0], buf[1] = l1, l2 and,
         with ``status``, buf[2] = the device status word (uwie_device_status_async, cleared on the device) as uint32 bits, so
         that one copy brings back all three."""
-        assert img.dtype == torch.float32 and ref.dtype == torch.float32 and img.dim() == 4
-        assert tuple(ref.shape) == tuple(img.shape)
-        B = img.shape[0]
-        H, W = (img.shape[2], img.shape[3]) if planar else (img.shape[1], img.shape[2])
-        assert img.shape[1 if planar else 3] == 3
-        img, ref = img.contiguous(), ref.contiguous()
+        identity = map_ == _lib.LOSS_IDENTITY
+        assert identity or params is not None
+        (B, H, W), (img, params, ref) = self._module_args(img, None if identity else params, planar, ref)
         ws = self.workspace(self.lib.uwie_ref_loss_workspace_bytes(B, H, W))
         buf = self.empty((4,), torch.float32)
-        out = saved = None
-        if map_ != _lib.LOSS_IDENTITY:
-            assert params.dtype == torch.float32 and tuple(params.shape) == (B, 4)
-            params = params.contiguous()
-            saved = self.empty((B, 3, 2), torch.float32)
-            out = self.empty(tuple(img.shape), torch.float32) if want_out else None
+        saved = None if identity else self.empty((B, 3, 2), torch.float32)
+        out = self.empty(tuple(img.shape), torch.float32) if want_out and not identity else None
         check(self.lib.uwie_ref_loss_f32(self._ctx, int(map_), _ptr(img), _ptr(params), int(flags), int(planar), B, H, W, _ptr(ref),
                                          _ptr(out), _ptr(saved), _ptr(buf), _ptr(ws), ws.numel(), self.stream()))
         if status:
@@ -358,21 +327,16 @@ class Device:
                          want_img: bool = True):
         """Gradient of ref_loss_f32 given grad_loss float32 [2] = dL/dl1, dL/dl2 on the device (and grad_out = dL/d(out) when
         the output was kept and used): (grad_img or None, grad_params float32 [B,4] or None for the identity map)."""
-        B = img.shape[0]
-        H, W = (img.shape[2], img.shape[3]) if planar else (img.shape[1], img.shape[2])
-        img, ref, grad_loss = img.contiguous(), ref.contiguous(), grad_loss.contiguous()
-        assert grad_loss.dtype == torch.float32 and grad_loss.numel() == 2
-        if grad_out is not None:
-            assert grad_out.dtype == torch.float32 and tuple(grad_out.shape) == tuple(img.shape)
-            grad_out = grad_out.contiguous()
         identity = map_ == _lib.LOSS_IDENTITY
+        (B, H, W), (img, params, ref, grad_out) = self._module_args(img, None if identity else params, planar, ref, grad_out)
+        grad_loss = grad_loss.contiguous()
+        assert grad_loss.dtype == torch.float32 and grad_loss.numel() == 2
         ws = self.workspace(self.lib.uwie_ref_loss_workspace_bytes(B, H, W))
         grad_img = self.empty(tuple(img.shape), torch.float32) if want_img or identity else None
         grad_params = None if identity else self.empty((B, 4), torch.float32)
-        check(self.lib.uwie_ref_loss_bwd_f32(self._ctx, int(map_), _ptr(img), _ptr(None if identity else params.contiguous()),
-                                             int(flags), int(planar), B, H, W, _ptr(saved), _ptr(ref), _ptr(grad_out),
-                                             _ptr(grad_loss), _ptr(grad_img), _ptr(grad_params), _ptr(ws), ws.numel(),
-                                             self.stream()))
+        check(self.lib.uwie_ref_loss_bwd_f32(self._ctx, int(map_), _ptr(img), _ptr(params), int(flags), int(planar), B, H, W,
+                                             _ptr(saved), _ptr(ref), _ptr(grad_out), _ptr(grad_loss), _ptr(grad_img),
+                                             _ptr(grad_params), _ptr(ws), ws.numel(), self.stream()))
         return grad_img, grad_params
 
     # ------------------------------------------------------------------ PerceptualLoss (uwie_perceptual_*, DESIGN.md section 14)
