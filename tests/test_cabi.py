@@ -73,6 +73,37 @@ def test_workspace_sizes(lib):
     assert lib.uwie_workspace_bytes(1, 480, 640, ctypes.byref(p)) <= small
 
 
+WS_SHAPES = ((1, 1, 1), (2, 48, 64), (3, 131, 203), (16, 1080, 1920))
+# uwie_workspace_bytes per (surface, strategy) at WS_SHAPES, recorded before the selection's workspace carve became one function
+# (the selection's share is in every one of them); None: p = NULL, what Device.percentiles_f32 sizes its workspace from
+WS_BYTES = {
+    (_lib.SURFACE_SIX, 1): (12783360, 25645056, 39066624, 912388096),
+    (_lib.SURFACE_SIX, 2): (12783104, 25620480, 39066624, 912388096),
+    (_lib.SURFACE_SIX, 3): (12783360, 25694208, 40024320, 1310519296),
+    (_lib.SURFACE_SIX, 4): (12782592, 25565184, 38347776, 204500992),
+    (_lib.SURFACE_SIX, 5): (12782592, 25565184, 38347776, 204500992),
+    (_lib.SURFACE_SIX, 6): (12782592, 25565184, 38347776, 204500992),
+    (_lib.SURFACE_DICT, 0): (12783616, 25768448, 40982784, 1696167936),
+    (_lib.SURFACE_DICT, 1): (12783872, 25793024, 40982784, 1696167936),
+    (_lib.SURFACE_DICT, 2): (12783616, 25768448, 40982784, 1696167936),
+    (_lib.SURFACE_DICT, 3): (12782592, 25565184, 38347776, 204500992),
+    (_lib.SURFACE_DICT, 4): (12782592, 25565184, 38347776, 204500992),
+    None: (12783616, 25718784, 40343808, 2421968896),
+}
+
+
+def test_workspace_bytes_are_unchanged(lib):
+    assert sorted(_lib.DICT_STRATEGIES.values()) == [0, 1, 2, 3, 4]
+    for key, want in WS_BYTES.items():
+        ref = None
+        if key is not None:
+            p = uw.UwieParams()
+            assert lib.uwie_params_init(ctypes.byref(p), *key) == 0
+            ref = ctypes.byref(p)
+        got = tuple(lib.uwie_workspace_bytes(B, H, W, ref) for B, H, W in WS_SHAPES)
+        assert got == want, f"{key}: {got}"
+
+
 def test_null_arguments_are_rejected_without_a_gpu(lib):
     assert lib.uwie_enhance_u8(None, None, None, None, 1, 8, 8, None, None, 0, None) == -1
     assert lib.uwie_params_init(None, 0, 1) == -1

@@ -386,3 +386,75 @@ def test_diff_gated_ranks(dev, planar):
         want = gated(t(x), t(params[:, :1]), t(params[:, 1:2]), t(params[:, 2:3]), t(params[:, 3:4]), planar=bool(planar)).numpy()
         sr.assert_same(out, want, f"gated forward {H}x{W} planar={planar}")
     assert dev.check_status() == 0
+
+
+# ------------------------------------------------------------------ D. the host path: tiny planes, launches per route
+def test_routes_tiny_planes(dev, orc):
+    """Planes of 1 .. 24 pixels through every route key and tuning cell: fewer than four pixels is where no sample is drawn
+    (ngroups == 0) and where the rank route's npx >= 4 guard sits; 1 x 5 and 3 x 8 have a ragged and a whole last group of
+    four.  One batch of two frames as well."""
+    rng = np.random.default_rng(9)
+    for H, W in ((1, 1), (1, 3), (2, 2), (1, 5), (3, 8)):
+        frame = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+        check_routes(dev, orc, frame[None], f"tiny {H}x{W}", alone=False)
+    check_routes(dev, orc, rng.integers(0, 256, (2, 3, 8, 3), dtype=np.uint8), "tiny 2 x 3x8", alone=False)
+
+
+ROW_PREFIXES = ("k_sel_", "k_lin_", "k_rank_", "k_restore_", "k_recover64_", "k_pct_")
+ROW_CELLS = (("default", {}), ("rank_sweep2", dict(rank_sweep=2)), ("restore_store", dict(restore_store=1)),
+             ("select_generic", dict(select_generic=1)), ("no_predict", dict(lin_no_predict=1)), ("lin_cap16", dict(lin_cap=16)))
+ROW_ROUTES = ((2, False), (3, False), ("medium_dehazing", False), ("medium_dehazing", True))
+
+
+def selection_rows(dev, frames):
+    """{(cell, strategy, f64 entry): {profiler row name: launches}} of the selection's and its producers' kernels (a launch
+    of a kernel with two template arguments is reported in parentheses: "(k_lin_collect_src<float, 4>)")."""
+    out = {}
+    for cell, tuning in ROW_CELLS:
+        with dev.tuning(**tuning):
+            for k, f64 in ROW_ROUTES:
+                dev.profile(True)
+                try:
+                    route_pct(dev, frames, k, f64)
+                    rows = dev.profile_rows()
+                finally:
+                    dev.profile(False)
+                out[cell, k, f64] = {name: calls for name, (_, calls) in sorted(rows.items()) if name.lstrip("(").startswith(ROW_PREFIXES)}
+    return out
+
+
+# Recorded by running selection_rows at the commit before the float32 and float64 host paths were merged (never from the
+# merged code): bench.py and profiles/f32t_stats.py match rows by these names.  Which kernels are launched and how often is
+# decided on the host (shape, tuning, strategy), never by the data.  Every row is one launch, but the key-digit passes': one
+# per digit (three float32, six float64), which return at once for planes that are not flagged.
+def _rows(passes, *names):
+    return {**{name: 1 for name in names}, "k_sel_pass<Src>": passes}
+
+
+LIN32 = ("k_lin_predict", "k_lin_scan<float>", "k_lin_finish<float>", "k_restore_hist_collect", "k_pct_finish<V>")
+LIN32_S3 = ("k_lin_predict", "k_lin_scan<float>", "k_lin_finish<float>", "k_restore_hist_collect4", "k_lin_collect<float>",
+            "k_pct_finish_chain")  # strategy 3: no sample, four windows, stored planes, the chained finish
+LIN64 = ("k_lin_predict", "k_lin_scan<double>", "k_lin_finish<double>", "k_recover64_hist_collect", "k_pct_finish<V>")
+RANK32 = ("k_lin_predict", "k_lin_sample<float>", "k_restore_rank", "k_rank_scan", "k_lin_finish<float>", "k_pct_finish<V>")
+SRC32, SRC64 = "(k_lin_collect_src<float, 4>)", "k_lin_collect_src64"
+ROWS_BY_CELL = {  # cell: strategy 2, strategy 3, medium_dehazing (the same through both entry points)
+    "default": (_rows(3, *LIN32, "k_lin_sample<float>", SRC32), _rows(3, *LIN32_S3), _rows(6, *LIN64, "k_lin_sample<double>", SRC64)),
+    "rank_sweep2": (_rows(3, *RANK32), _rows(3, *LIN32_S3), _rows(6, *LIN64, "k_lin_sample<double>", SRC64)),
+    "restore_store": (_rows(3, *LIN32, "k_lin_sample<float>", "k_lin_collect<float>"), _rows(3, *LIN32_S3),
+                      _rows(6, *LIN64, "k_lin_sample<double>", "k_lin_collect<double>")),
+    "select_generic": (_rows(3, "k_sel_init<K>", "k_restore_hist_key", "k_pct_finish<V>"),
+                       _rows(3, "k_sel_init<K>", "k_restore_hist_key", "k_pct_finish_chain"),
+                       _rows(6, "k_sel_init<K>", "k_recover64_hist_key", "k_pct_finish<V>")),
+    "no_predict": (_rows(3, *LIN32, SRC32), _rows(3, *LIN32_S3), _rows(6, *LIN64, SRC64)),
+    "lin_cap16": (_rows(3, *LIN32, "k_lin_sample<float>", SRC32), _rows(3, *LIN32_S3), _rows(6, *LIN64, "k_lin_sample<double>", SRC64)),
+}
+ROWS = {(cell, k, f64): by[min(i, 2)] for cell, by in ROWS_BY_CELL.items() for i, (k, f64) in enumerate(ROW_ROUTES)}
+
+
+def test_profiler_rows_per_route(dev):
+    frames = np.random.default_rng(10).integers(0, 256, (2, 48, 64, 3), dtype=np.uint8)
+    got = selection_rows(dev, frames)
+    assert sorted(got, key=str) == sorted(ROWS, key=str)
+    for key in ROWS:
+        assert got[key] == ROWS[key], f"{key}: {got[key]}"
+    assert dev.check_status() == 0

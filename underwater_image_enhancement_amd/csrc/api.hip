@@ -230,11 +230,13 @@ int stage_guided(const Pipe &P, Shape s, const uwie_params *p, const FuseT0Args 
     return UWIE_OK;
 }
 
-int stage_stretch(const Pipe &P, Shape s, double lo, double hi, float eps, hipStream_t st)
+// enhance_contrast / white_balance (S6:191-199 / :211-219) of a float32 HWC image: two percentiles into pct [B][3][2], then
+// the stretch to `out` (which may be img)
+int stretch_f32(const float *img, float *out, Shape s, double lo, double hi, float eps, float *pct, void *ws, hipStream_t st)
 {
     const double q[2] = {lo, hi};
-    UWIE_TRY(launch_percentiles_f32(P.F, 0, s, q, 2, P.pct, P.scratch, st));
-    return launch_stretch_apply_f32(P.F, P.pct, 2, 0, 1, eps, P.F, s, st);
+    UWIE_TRY(launch_percentiles(img, 0, s, q, 2, pct, ws, st));
+    return launch_stretch_apply_f32(img, pct, 2, 0, 1, eps, out, s, st);
 }
 
 // Cast detection (or the forced kind): what every six_stadigy strategy starts from.
@@ -283,7 +285,7 @@ int six_dehaze_tail(uwie_ctx *ctx, const uint8_t *d_in, const int32_t *kind, Sha
     const RestoreSrc src{d_in, kind, P.A, P.t, t_is_f32};
     bool recompute = false;
     if (tune().select_generic) {
-        UWIE_TRY(select_begin(s, q, k == 3 ? 4 : 2, P.scratch, st, &plan));
+        UWIE_TRY(select_begin<float>(s, q, k == 3 ? 4 : 2, P.scratch, st, &plan));
         UWIE_TRY(launch_restore_planar_hist(d_in, kind, P.A, P.t, s, P.F, plan.ghist, st, false, nullptr, t_is_f32));
         UWIE_TRY(select_run(plan, P.F, 1, s, true, st));
     } else {
@@ -298,7 +300,7 @@ int six_dehaze_tail(uwie_ctx *ctx, const uint8_t *d_in, const int32_t *kind, Sha
         // four windows made the restore sweep 2.9 ms at 4K x 16 against 0.65 + 0.35 for sweep + collection.
         // Tuning lin_predict3 brings the windows back.
         const bool predict = k != 3 || tune().lin_predict3;
-        UWIE_TRY(select_lin_begin(s, q, k == 3 ? 4 : 2, P.scratch, st, &plan, predict ? &src : nullptr));
+        UWIE_TRY(select_lin_begin<float>(s, q, k == 3 ? 4 : 2, P.scratch, st, &plan, predict ? &src : nullptr));
         // (small jobs keep the histogram sweep: at 1080p x 1 the rank-counting kernels' fixed costs -- wavefront-private queues,
         // a window-wide list for the finish -- make them 54 + 20 us against 34 + 14; tuning rank_sweep = 2 forces them anyway)
         const bool big = (size_t)s.B * s.npx() >= ((size_t)1 << 24) || tune().rank_sweep >= 2;
@@ -347,24 +349,24 @@ int run_dict_dehaze(uwie_ctx *ctx, const uint8_t *d_in, Shape s, const uwie_para
     UWIE_TRY(stage_guided(P, s, p, FuseT0Args{d_in, nullptr, P.A, (float)p->omega, 1e-10f, 0}, st));  // ES:221-232
     SelectPlan plan;
     const double q[2] = {p->L_low, p->L_high};
-    // the recovered image is clipped to [0, 1]: linear first digit, one collecting sweep (select_lin_*64);
+    // the recovered image is clipped to [0, 1]: linear first digit, one collecting sweep (select_lin_*<double>);
     // tuning select_generic keeps the six-digit key sweeps
     const RestoreSrc src{d_in, nullptr, P.A, P.t};
     bool recompute = false;
     if (tune().select_generic) {
-        UWIE_TRY(select_begin64(s, q, 2, P.scratch, st, &plan));
+        UWIE_TRY(select_begin<double>(s, q, 2, P.scratch, st, &plan));
         UWIE_TRY(launch_recover64_planar_hist(d_in, P.A, P.t, s, P.F64, plan.ghist, st));
-        UWIE_TRY(select_run64(plan, P.F64, 1, s, true, st));
+        UWIE_TRY(select_run(plan, P.F64, 1, s, true, st));
     } else {
         // the float64 image (24 B/px) is not stored either: histogram sweep, collecting sweep and stretch recompute it
         // from the frame and t (11 B/px each), and so do the key-digit passes of flagged planes.  Tuning restore_store keeps
         // the stored planes.
         recompute = !tune().restore_store;
-        UWIE_TRY(select_lin_begin64(s, q, 2, P.scratch, st, &plan, &src));
+        UWIE_TRY(select_lin_begin<double>(s, q, 2, P.scratch, st, &plan, &src));
         UWIE_TRY(launch_recover64_planar_hist(d_in, P.A, P.t, s, recompute ? nullptr : P.F64, plan.ghist, st, true, &plan));
-        UWIE_TRY(select_lin_run64(plan, P.F64, s, st, recompute ? &src : nullptr));
+        UWIE_TRY(select_lin_run(plan, P.F64, s, st, recompute ? &src : nullptr));
     }
-    UWIE_TRY(select_lerp64(plan, s, P.pct64, st));
+    UWIE_TRY(select_lerp(plan, s, P.pct64, st));
     return launch_tail_plain64(P.F64, P.pct64, s, p->apply_gamma, p->gamma, d_out_u8, d_out_f32, st, recompute ? &src : nullptr,
                                d_out_f64);
 }
@@ -446,9 +448,7 @@ FloatPipe<T> carve_float(Carver &c, Shape s, const uwie_params *p)
 // percentile stretch of a float32 HWC image in place (S6:191-199 / :211-219)
 static int float_stretch(const FloatPipe<float> &P, float *img, Shape s, double lo, double hi, hipStream_t st)
 {
-    const double q[2] = {lo, hi};
-    UWIE_TRY(launch_percentiles_f32(img, 0, s, q, 2, P.pct, P.scratch, st));
-    return launch_stretch_apply_f32(img, P.pct, 2, 0, 1, 1e-6f, img, s, st);
+    return stretch_f32(img, img, s, lo, hi, 1e-6f, P.pct, P.scratch, st);
 }
 
 // six_stadigy.py strategies 1-6 on a float32 image (S6:230-285); the result image goes to out_f32 and/or out_u8
@@ -519,9 +519,9 @@ static int run_float_dict(uwie_ctx *ctx, const T *d_img, Shape s, const uwie_par
     UWIE_TRY((launch_float_restore<T, double>(d_img, P.A, P.t, s, P.F64, 1, st)));
     SelectPlan plan;
     const double q[2] = {p->L_low, p->L_high};
-    UWIE_TRY(select_begin64(s, q, 2, P.scratch, st, &plan));
-    UWIE_TRY(select_run64(plan, P.F64, 1, s, false, st));
-    UWIE_TRY(select_lerp64(plan, s, P.pct64, st));
+    UWIE_TRY(select_begin<double>(s, q, 2, P.scratch, st, &plan));
+    UWIE_TRY(select_run(plan, P.F64, 1, s, false, st));
+    UWIE_TRY(select_lerp(plan, s, P.pct64, st));
     return launch_tail_plain64(P.F64, P.pct64, s, p->apply_gamma, p->gamma, out_u8, out_f32, st, nullptr, out_f64);
 }
 
@@ -1713,7 +1713,7 @@ int uwie_percentiles_f32(uwie_ctx *ctx, const float *d_img, int batch, int H, in
     UWIE_CHECK_SHAPE(batch, H, W);
     const Shape s{batch, H, W};
     UWIE_CHECK_WS(select_ws_bytes(s));
-    return launch_percentiles_f32(d_img, 0, s, q_percent, nq, d_out, d_workspace, (hipStream_t)stream);
+    return launch_percentiles(d_img, 0, s, q_percent, nq, d_out, d_workspace, (hipStream_t)stream);
 }
 
 int uwie_percentiles_f64(uwie_ctx *ctx, const double *d_img, int batch, int H, int W, const double *q_percent, int nq,
@@ -1724,7 +1724,7 @@ int uwie_percentiles_f64(uwie_ctx *ctx, const double *d_img, int batch, int H, i
     UWIE_CHECK_SHAPE(batch, H, W);
     const Shape s{batch, H, W};
     UWIE_CHECK_WS(select_ws_bytes(s));
-    return launch_percentiles_f64(d_img, s, q_percent, nq, d_out, d_workspace, (hipStream_t)stream);
+    return launch_percentiles(d_img, 0, s, q_percent, nq, d_out, d_workspace, (hipStream_t)stream);
 }
 
 int uwie_enhance_percentiles(uwie_ctx *ctx, const void *d_workspace, size_t workspace_bytes, int batch, int H, int W,
@@ -1761,10 +1761,7 @@ int uwie_stretch_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch,
     float *pct = c.take<float>((size_t)batch * 3 * 2);
     void *ws = c.take<char>(select_ws_bytes(s));
     UWIE_CHECK_WS(c.total());
-    const double q[2] = {lo_percent, hi_percent};
-    hipStream_t st = (hipStream_t)stream;
-    UWIE_TRY(launch_percentiles_f32(d_img, 0, s, q, 2, pct, ws, st));
-    return launch_stretch_apply_f32(d_img, pct, 2, 0, 1, 1e-6f, d_out, s, st);
+    return stretch_f32(d_img, d_out, s, lo_percent, hi_percent, 1e-6f, pct, ws, (hipStream_t)stream);
 }
 
 int uwie_gamma_f32(uwie_ctx *ctx, const float *d_img, float *d_out, size_t n, double g, int mode, void *stream)

@@ -74,12 +74,14 @@ private:
 #define UWIE_PROF_CAT2(a, b) a##b
 #define UWIE_PROF_CAT(a, b) UWIE_PROF_CAT2(a, b)
 #define UWIE_PROF(name, st) ::uwie::ProfScope UWIE_PROF_CAT(_uwie_prof_, __LINE__)(name, st)
-// every kernel launch goes through this: named timing scope + launch
-#define UWIE_LAUNCH(kernel, grid, block, lds, st, ...)                      \
+// every kernel launch goes through this: named timing scope + launch.  The profiler row is the kernel as written at the
+// launch; UWIE_LAUNCH_AS names the row itself (a launch inside a template would report its parameter, not the type)
+#define UWIE_LAUNCH_AS(row, kernel, grid, block, lds, st, ...)              \
     do {                                                                    \
-        UWIE_PROF(#kernel, st);                                             \
+        UWIE_PROF(row, st);                                                 \
         hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__);      \
     } while (0)
+#define UWIE_LAUNCH(kernel, ...) UWIE_LAUNCH_AS(#kernel, kernel, __VA_ARGS__)
 
 }  // namespace uwie
 
@@ -319,18 +321,19 @@ int launch_guided_fast(const uint8_t *d_gray, const float *d_t0, Shape s, int k,
 // k_select.hip
 constexpr int kMaxPct = 4;  // percentiles per call
 size_t select_ws_bytes(Shape s);
-// d_vals: float32 image, HWC ([B][H][W][3], planar = 0) or planar ([B][3][H][W], planar = 1); d_out [B][3][nq]
-int launch_percentiles_f32(const float *d_vals, int planar, Shape s, const double *q_percent, int nq, float *d_out,
-                           void *ws, hipStream_t st);
-// the same on a float64 image ([B][H][W][3]); d_out [B][3][nq]
-int launch_percentiles_f64(const double *d_vals, Shape s, const double *q_percent, int nq, double *d_out, void *ws, hipStream_t st);
+// The selection's host entry points are templates on the value type V = float (S6 surface) or double (ES surface), defined
+// and instantiated for both in k_select.hip.
+// d_vals: image of V, HWC ([B][H][W][3], planar = 0) or planar ([B][3][H][W], planar = 1); d_out [B][3][nq]
+template <typename V>
+int launch_percentiles(const V *d_vals, int planar, Shape s, const double *q_percent, int nq, V *d_out, void *ws, hipStream_t st);
 // d_out[i] = (double)d_in[i], i < n
 int launch_widen_f32(const float *d_in, double *d_out, size_t n, hipStream_t st);
 
-// selection in pieces, for producers that fuse the first histogram sweep (digit = f32_key(v) >> 21, 2048 bins,
-// accumulated into plan.ghist[(b*3 + c) * kSelGroupStride + digit])
+// selection in pieces, for producers that fuse the first histogram sweep (digit = f32_key(v) >> 21 resp. f64_key(v) >> 53,
+// 2048 bins, accumulated into plan.ghist[(b*3 + c) * kSelGroupStride + digit])
 constexpr int kSelGroupStride = 2 * kMaxPct * 2048;
 constexpr int kSelOsStride = 2 * kMaxPct;  // order statistics per (image, channel) in SelectPlan::os
+struct LinState;
 struct SelectPlan {
     void *state;
     uint32_t *ghist;
@@ -339,12 +342,14 @@ struct SelectPlan {
     int nq;
     bool is64;
     // linear-digit path (select_lin_*): per (image, channel) state, candidate lists and fallback flags
-    void *lin;
-    float *lists;          // [B*3][kLinLists][cap]
+    LinState *lin;
+    void *lists;           // [B*3][kLinLists][cap] values of the data's dtype: read through lists_as
     uint32_t *flags;       // [B*3] 1 = a candidate list overflowed, use the key-digit passes
     uint32_t cap;
     bool predicted;        // the producer files the predicted windows: the collecting sweep is the rare fallback
     uint32_t ranks[2 * kMaxPct];
+    template <typename V>
+    V *lists_as() const { return static_cast<V *>(lists); }
 };
 // Selection on clipped [0, 1] float32 planes with ONE sweep after the producer's histogram: the first digit is a linear
 // 2050-way split of [0, 1] (exact 0 and exact 1 get their own bins), which a whole frame spreads over thousands of bins,
@@ -365,7 +370,7 @@ __host__ __device__ inline uint32_t lin_digit(double x)  // the same split for t
     const uint32_t d = (uint32_t)(x * 2048.0);
     return 1 + (d > 2047u ? 2047u : d);
 }
-// Per (image, channel) state of the linear-digit selection.  With a prediction (select_lin_begin(..., predict)) the
+// Per (image, channel) state of the linear-digit selection.  With a prediction (select_lin_begin<V>(..., predict)) the
 // producer already files the elements of two windows of bins, each around the predicted position of a percentile's
 // ranks, into one list per window during its own sweep; the scan then checks the prediction against the exact
 // histogram, and only planes it missed need the collecting sweep (whose groups reuse the lists).
@@ -389,17 +394,18 @@ constexpr int kRankCapMul = 4;
 constexpr uint32_t kLinAnyBin = 0xfffffffeu;  // LinState::qbin: the query's list is its whole window, rr its rank inside it
 struct RestoreSrc;
 // predict != nullptr: the target bins are predicted from a subsample of the restored image (k_lin_sample)
+template <typename V>
 int select_lin_begin(Shape s, const double *q_percent, int nq, void *ws, hipStream_t st, SelectPlan *plan,
                      const RestoreSrc *predict = nullptr);
 // src != nullptr: the values are recomputed from *src (d_planar is not read); flagged planes take the key-digit passes
-int select_lin_run(const SelectPlan &plan, const float *d_planar, Shape s, hipStream_t st, const RestoreSrc *src = nullptr);
-// float64 planes (ES surface): linear first digit by the producer, one collecting sweep, finish on the lists
-int select_lin_begin64(Shape s, const double *q_percent, int nq, void *ws, hipStream_t st, SelectPlan *plan,
-                       const RestoreSrc *predict = nullptr);
-int select_lin_run64(const SelectPlan &plan, const double *d_planar, Shape s, hipStream_t st, const RestoreSrc *src = nullptr);
+template <typename V>
+int select_lin_run(const SelectPlan &plan, const V *d_planar, Shape s, hipStream_t st, const RestoreSrc *src = nullptr);
+template <typename V>
 int select_begin(Shape s, const double *q_percent, int nq, void *ws, hipStream_t st, SelectPlan *plan);
-int select_run(const SelectPlan &plan, const float *d_vals, int planar, Shape s, bool pass1_done, hipStream_t st);
-int select_lerp(const SelectPlan &plan, Shape s, float *d_out, hipStream_t st);                     // [B][3][nq]
+template <typename V>
+int select_run(const SelectPlan &plan, const V *d_vals, int planar, Shape s, bool pass1_done, hipStream_t st);
+template <typename V>
+int select_lerp(const SelectPlan &plan, Shape s, V *d_out, hipStream_t st);                         // [B][3][nq]
 int select_lerp_chain(const SelectPlan &plan, Shape s, float eps, float *d_pct4, hipStream_t st);   // [B][3][4]
 // explicit sorted positions per image (vgg_16_UIE.py:78-82): os[bc*8 + 0/1] = sorted[int(L_low/100*n)], sorted[int(L_high/100*n)]
 int select_begin_stretch_ranks(Shape s, const float *d_params, int stride, void *ws, hipStream_t st, SelectPlan *plan);
@@ -469,10 +475,6 @@ size_t param_net_ws_bytes(Shape s);
 int launch_param_net(const ParamNet &net, const float *img, const float *feat, Shape s, float *out, float *pooled, void *ws,
                      hipStream_t st);
 int launch_u8_to_f32(const uint8_t *d_in, size_t n, float *d_out, hipStream_t st);
-// float64 data (ES surface): first digit = f64_key(v) >> 53
-int select_begin64(Shape s, const double *q_percent, int nq, void *ws, hipStream_t st, SelectPlan *plan);
-int select_run64(const SelectPlan &plan, const double *d_vals, int planar, Shape s, bool pass1_done, hipStream_t st);
-int select_lerp64(const SelectPlan &plan, Shape s, double *d_out, hipStream_t st);
 
 // k_fused.hip: the fused tail of the dehazing strategies
 // what the restored image (six_stadigy.py:183-188) is made of; consumers may recompute it from here (restore.h)

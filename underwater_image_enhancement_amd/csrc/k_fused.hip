@@ -1379,41 +1379,58 @@ ClaheGeom make_geom(Shape s, double clip, int tx, int ty)
 
 float gamma_exponent(int mode, double g) { return mode == 1 ? (float)g : mode == 2 ? (float)(1.0 / g) : 1.0f; }
 
+// Blocks per frame of a producer sweep of about `total` blocks per call: 16 .. 384 per frame (a block clears and flushes its LDS
+// counters: small batches get fewer, longer blocks; 4K x 16: 768 per frame 0.62 ms, 192: 0.53), one per 1024 pixels at most.
+int producer_blocks(int total, Shape s)
+{
+    const int nblk = std::min(std::max(cdiv(total, s.B), 16), 384);
+    return std::min(nblk, cdiv((long long)s.npx(), 1024));
+}
+
+// profiler rows and the plan check's message of the histogram producer per value type (names as the profiler reports them)
+template <typename V>
+struct HistRows;
+template <>
+struct HistRows<float> {
+    static constexpr const char *collect = "k_restore_hist_collect", *collect4 = "k_restore_hist_collect4", *lin = "k_restore_hist_lin",
+                                *key = "k_restore_hist_key", *plan_msg = "restore: a selection plan goes with its own linear histogram";
+};
+template <>
+struct HistRows<double> {
+    static constexpr const char *collect = "k_recover64_hist_collect", *collect4 = collect, *lin = "k_recover64_hist_lin",
+                                *key = "k_recover64_hist_key", *plan_msg = "recover: a selection plan goes with its own linear histogram";
+};
+
+// k_restore_planar_hist<.., V>: with a plan the collecting variant, else the linear or the key first digit alone
+template <typename V>
+int launch_planar_hist(const RestoreSrc &S, Shape s, V *d_planar, uint32_t *d_ghist, hipStream_t st, bool linear, const SelectPlan *plan)
+{
+    using Rows = HistRows<V>;
+    constexpr bool f64 = sizeof(V) == 8;
+    constexpr int NW4 = f64 ? 2 : 4;  // four windows (strategy 3, tuning lin_predict3) exist in float32 only
+    if (plan) UWIE_REQUIRE(linear && d_ghist == plan->ghist && (!f64 || plan->nq <= 2), Rows::plan_msg);
+    // 24.6 KB of LDS per block: six blocks per CU, 1536 resident on the chip.  Enough blocks for several full rounds
+    // (2048 blocks were 1.33 rounds: a third of the chip idle for half the kernel).
+    // 4K x 64: 32 per frame 2.79 ms, 96: 2.52, 192: 2.43, 384: 2.47 (round 1)
+    const dim3 grid(producer_blocks(12288, s), s.B);
+    const auto launch = [&](const char *row, auto kernel) {
+        UWIE_LAUNCH_AS(row, kernel, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist, plan ? plan->lin : nullptr,
+                       plan ? plan->lists_as<V>() : nullptr, plan ? plan->cap : 0u);
+    };
+    if (plan && plan->nq <= 2) launch(Rows::collect, k_restore_planar_hist<true, true, 2, V>);
+    else if (plan) launch(Rows::collect4, k_restore_planar_hist<true, true, NW4, V>);
+    else if (linear) launch(Rows::lin, k_restore_planar_hist<true, false, 2, V>);
+    else launch(Rows::key, k_restore_planar_hist<false, false, 2, V>);
+    UWIE_LAUNCH_CHECK();
+    return UWIE_OK;
+}
+
 }  // namespace
 
 int launch_restore_planar_hist(const uint8_t *d_in, const int32_t *d_kind, const float *d_A, const double *d_t, Shape s,
                                float *d_planar, uint32_t *d_ghist, hipStream_t st, bool linear, const SelectPlan *plan, int t32)
 {
-    // 24.6 KB of LDS per block: six blocks per CU, 1536 resident on the chip.  Enough blocks for several full rounds
-    // (2048 blocks were 1.33 rounds: a third of the chip idle for half the kernel).
-    int nblk = cdiv(12288, s.B);  // 4K x 64: 32 per frame 2.79 ms, 96: 2.52, 192: 2.43, 384: 2.47 (round 1)
-    // (a block clears and flushes 6 K counters: small batches get fewer, longer blocks; 4K x 16: 768 per frame 0.62 ms, 192: 0.53)
-    nblk = nblk < 16 ? 16 : nblk > 384 ? 384 : nblk;
-    const int need = cdiv((long long)s.npx(), 1024);
-    if (nblk > need) nblk = need;
-    const RestoreSrc S{d_in, d_kind, d_A, d_t, t32};
-    const dim3 grid(nblk, s.B);
-    const auto k_restore_hist_collect = k_restore_planar_hist<true, true, 2>;  // (names as the profiler reports them)
-    const auto k_restore_hist_collect4 = k_restore_planar_hist<true, true, 4>;
-    const auto k_restore_hist_lin = k_restore_planar_hist<true, false>;
-    const auto k_restore_hist_key = k_restore_planar_hist<false, false>;
-    if (plan) {
-        UWIE_REQUIRE(linear && d_ghist == plan->ghist, "restore: a selection plan goes with its own linear histogram");
-        if (plan->nq <= 2)
-            UWIE_LAUNCH(k_restore_hist_collect, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist,
-                        (LinState *)plan->lin, plan->lists, plan->cap);
-        else
-            UWIE_LAUNCH(k_restore_hist_collect4, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist,
-                        (LinState *)plan->lin, plan->lists, plan->cap);
-    } else if (linear) {
-        UWIE_LAUNCH(k_restore_hist_lin, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist,
-                    (LinState *)nullptr, (float *)nullptr, 0u);
-    } else {
-        UWIE_LAUNCH(k_restore_hist_key, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist,
-                    (LinState *)nullptr, (float *)nullptr, 0u);
-    }
-    UWIE_LAUNCH_CHECK();
-    return UWIE_OK;
+    return launch_planar_hist<float>(RestoreSrc{d_in, d_kind, d_A, d_t, t32}, s, d_planar, d_ghist, st, linear, plan);
 }
 
 int launch_restore_rank(const RestoreSrc &src, Shape s, const SelectPlan &plan, hipStream_t st)
@@ -1421,11 +1438,7 @@ int launch_restore_rank(const RestoreSrc &src, Shape s, const SelectPlan &plan, 
     UWIE_REQUIRE(!src.t32 && plan.nq <= 2 && plan.predicted && s.npx() >= 4, "restore_rank: float64 transmission, two predicted percentiles");
     // 28.8 KB of LDS per block: five blocks per CU, 1280 on the chip.  Four whole rounds of them per call (the histogram
     // sweep's 12288 blocks were 9.6 rounds, the last one 60 % full: 1.43 -> 1.37 ms at 4K x 64, A/B/C with 2560 / 3840 / 5120).
-    int nblk = cdiv(5120, s.B);
-    nblk = nblk < 16 ? 16 : nblk > 384 ? 384 : nblk;
-    const int need = cdiv((long long)s.npx(), 1024);
-    if (nblk > need) nblk = need;
-    UWIE_LAUNCH(k_restore_rank, dim3(nblk, s.B), dim3(256), 0, st, src, (int)s.npx(), (LinState *)plan.lin, plan.lists,
+    UWIE_LAUNCH(k_restore_rank, dim3(producer_blocks(5120, s), s.B), dim3(256), 0, st, src, (int)s.npx(), plan.lin, plan.lists_as<float>(),
                 (uint32_t)kRankCapMul * plan.cap);
     UWIE_LAUNCH_CHECK();
     return UWIE_OK;
@@ -1434,28 +1447,7 @@ int launch_restore_rank(const RestoreSrc &src, Shape s, const SelectPlan &plan, 
 int launch_recover64_planar_hist(const uint8_t *d_in, const float *d_A, const double *d_t, Shape s, double *d_planar,
                                  uint32_t *d_ghist, hipStream_t st, bool linear, const SelectPlan *plan)
 {
-    int nblk = cdiv(12288, s.B);
-    nblk = nblk < 16 ? 16 : nblk > 384 ? 384 : nblk;
-    const int need = cdiv((long long)s.npx(), 1024);
-    if (nblk > need) nblk = need;
-    const RestoreSrc S{d_in, nullptr, d_A, d_t};
-    const dim3 grid(nblk, s.B);
-    const auto k_recover64_hist_collect = k_restore_planar_hist<true, true, 2, double>;  // (names as the profiler reports them)
-    const auto k_recover64_hist_lin = k_restore_planar_hist<true, false, 2, double>;
-    const auto k_recover64_hist_key = k_restore_planar_hist<false, false, 2, double>;
-    if (plan) {
-        UWIE_REQUIRE(linear && d_ghist == plan->ghist && plan->nq <= 2, "recover: a selection plan goes with its own linear histogram");
-        UWIE_LAUNCH(k_recover64_hist_collect, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist,
-                    (LinState *)plan->lin, reinterpret_cast<double *>(plan->lists), plan->cap);
-    } else if (linear) {
-        UWIE_LAUNCH(k_recover64_hist_lin, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist, (LinState *)nullptr,
-                    (double *)nullptr, 0u);
-    } else {
-        UWIE_LAUNCH(k_recover64_hist_key, grid, dim3(256), 0, st, S, (int)s.npx(), d_planar, d_ghist, (LinState *)nullptr,
-                    (double *)nullptr, 0u);
-    }
-    UWIE_LAUNCH_CHECK();
-    return UWIE_OK;
+    return launch_planar_hist<double>(RestoreSrc{d_in, nullptr, d_A, d_t}, s, d_planar, d_ghist, st, linear, plan);
 }
 
 int launch_tail_plain64(const double *d_planar, const double *d_pct, Shape s, int apply_gamma, double gamma,

@@ -60,7 +60,7 @@ struct SelState {                 // one per (image, channel)
     uint32_t ngroups;
     uint32_t ticket;              // blocks of the running pass that have added their counts (k_sel_pass)
 };
-// (select_ws_bytes carves the states at this stride for both key widths)
+// (carve_select takes the states at this stride for both key widths)
 static_assert(sizeof(SelState<uint64_t>) == 200 && sizeof(SelState<uint32_t>) <= 200, "selection state layout");
 
 struct RankList {
@@ -438,27 +438,56 @@ void percentile_indices(long long n, double q_percent, uint32_t *prev, uint32_t 
     *t = (double)(vi - p);
 }
 
-template <typename V>
-int begin_t(Shape s, const double *q_percent, int nq, void *ws, hipStream_t st, SelectPlan *plan)
+// list capacity per (image, channel, group); UWIE_LIN_CAP overrides it (tests force the overflow / fallback path)
+uint32_t lin_cap(Shape s)
 {
-    using K = typename Traits<V>::K;
+    const uint32_t dflt = (uint32_t)std::max<size_t>(65536, s.npx() / 64);
+    const long v = tune().lin_cap;  // (0 outside an entry point: the workspace is sized for the default)
+    return v > 0 && v < (long)dflt ? (uint32_t)v : dflt;
+}
+
+// The selection's workspace, the one place that lays it out: every begin carves its plan here and select_ws_bytes is this
+// carve on a null base.  lin: the buffers of the linear-digit and rank routes behind the three every route uses.
+void carve_select(Carver &c, Shape s, bool lin, SelectPlan *plan)
+{
+    const size_t nbc = (size_t)s.B * 3;
+    plan->state = c.take<SelState<uint64_t>>(nbc);  // sized for the wider key
+    plan->ghist = c.take<uint32_t>(nbc * kMaxRanks * kBins);
+    plan->os = c.take<double>(nbc * kMaxRanks);
+    if (!lin) return;
+    plan->lin = c.take<LinState>(nbc);
+    plan->flags = c.take<uint32_t>(nbc);
+    plan->cap = lin_cap(s);
+    plan->lists = c.take<double>(nbc * kLinLists * plan->cap);  // (sized for the float64 surface)
+}
+
+int zero_ghist(const SelectPlan &plan, Shape s, hipStream_t st)
+{
+    UWIE_HIP_CHECK(hipMemsetAsync(plan.ghist, 0, sizeof(uint32_t) * (size_t)s.B * 3 * kMaxRanks * kBins, st));
+    return UWIE_OK;
+}
+
+RankList rank_list(const SelectPlan &plan)
+{
+    RankList ranks;
+    ranks.n = 2 * plan.nq;
+    for (int j = 0; j < ranks.n; ++j) ranks.r[j] = plan.ranks[j];
+    return ranks;
+}
+
+// What the percentile begins share: the checks, the carve, and np.percentile's ranks and weights in the data's dtype V.
+template <typename V>
+int plan_percentiles(Shape s, const double *q_percent, int nq, void *ws, bool lin, SelectPlan *plan)
+{
     UWIE_REQUIRE(nq >= 1 && nq <= kMaxPct, "percentiles: 1..4 percentiles per call");
     const long long n = (long long)s.npx();
     UWIE_REQUIRE(n >= 1 && n < (1ll << 31), "percentiles: plane size out of range");
     Carver c(ws);
-    const int nbc = s.B * 3;
-    plan->state = c.take<SelState<uint64_t>>(nbc);  // sized for the wider key
-    plan->ghist = c.take<uint32_t>((size_t)nbc * kMaxRanks * kBins);
-    plan->os = c.take<double>((size_t)nbc * kMaxRanks);
+    carve_select(c, s, lin, plan);
     plan->nq = nq;
     plan->is64 = sizeof(V) == 8;
-    RankList ranks;
-    ranks.n = 2 * nq;
     for (int j = 0; j < nq; ++j)
-        percentile_indices<V>(n, q_percent[j], &ranks.r[2 * j], &ranks.r[2 * j + 1], &plan->t[j]);
-    UWIE_LAUNCH(k_sel_init<K>, dim3(cdiv(nbc, 64)), dim3(64), 0, st, (SelState<K> *)plan->state, nbc, ranks);
-    UWIE_LAUNCH_CHECK();
-    UWIE_HIP_CHECK(hipMemsetAsync(plan->ghist, 0, sizeof(uint32_t) * (size_t)nbc * kMaxRanks * kBins, st));
+        percentile_indices<V>(n, q_percent[j], &plan->ranks[2 * j], &plan->ranks[2 * j + 1], &plan->t[j]);
     return UWIE_OK;
 }
 
@@ -502,24 +531,21 @@ __global__ void k_sel_init_gated_ranks(SelState<uint32_t> *st, int nbc, const fl
     st[i] = sel_state<uint32_t>(ranks);
 }
 
-template <typename V>
-int run_t(const SelectPlan &plan, const V *d_vals, int planar, Shape s, bool pass1_done, hipStream_t st)
+// The rank begins of the two DifferentiableEnhancement modules: init(state, nbc, n) launches the kernel that writes every
+// plane's two ranks.
+template <class Init>
+int begin_ranks(Shape s, const char *range_msg, void *ws, hipStream_t st, SelectPlan *plan, Init &&init)
 {
-    const int n = (int)s.npx(), nbc = s.B * 3;
-    const StoredVals<V> src{d_vals, (size_t)n * 3, planar ? (size_t)n : (size_t)1, planar ? 1 : 3};
-    return sel_passes(plan, src, n, nbc, pass_blocks(n, nbc, false), pass1_done, nullptr, st);
-}
-
-template <typename V>
-int lerp_t(const SelectPlan &plan, Shape s, V *d_out, hipStream_t st)
-{
-    FracList<V> fr;
-    fr.n = plan.nq;
-    for (int j = 0; j < plan.nq; ++j) fr.t[j] = (V)plan.t[j];
-    const int nbc = s.B * 3;
-    UWIE_LAUNCH(k_pct_finish<V>, dim3(cdiv(nbc * plan.nq, 64)), dim3(64), 0, st, (const V *)plan.os, nbc, fr, d_out);
+    const long long n = (long long)s.npx();
+    UWIE_REQUIRE(n >= 1 && n < (1ll << 31), range_msg);
+    Carver c(ws);
+    carve_select(c, s, false, plan);
+    plan->nq = 1;  // two ranks
+    plan->is64 = false;
+    plan->t[0] = 0.0;
+    init((SelState<uint32_t> *)plan->state, s.B * 3, (int)n);
     UWIE_LAUNCH_CHECK();
-    return UWIE_OK;
+    return zero_ghist(*plan, s, st);
 }
 
 }  // namespace
@@ -528,16 +554,6 @@ int lerp_t(const SelectPlan &plan, Shape s, V *d_out, hipStream_t st)
 namespace {
 
 constexpr uint32_t kLinDone = 0xffffffffu;
-constexpr int kLinStage = 512;  // candidates a block stages in LDS per group before it reserves list space
-
-// list capacity per (image, channel, group); UWIE_LIN_CAP overrides it (tests force the overflow / fallback path)
-uint32_t lin_cap(Shape s)
-{
-    const uint32_t dflt = (uint32_t)std::max<size_t>(65536, s.npx() / 64);
-    const long v = tune().lin_cap;  // (0 outside an entry point: the workspace is sized for the default)
-    return v > 0 && v < (long)dflt ? (uint32_t)v : dflt;
-}
-
 constexpr int kLinSampleOff = 4096;  // the sample histogram of a plane lives behind the producer's in its ghist group
 
 // grid (blocks, B): linear-digit histogram of the restored image on every stride-th group of four pixels (ngs groups;
@@ -1146,86 +1162,79 @@ __global__ void __launch_bounds__(1024) k_lin_finish(const LinState *__restrict_
     if (tid == 0) os[bc * kMaxRanks + q1] = Traits<V>::value((K)(s_nloc > r_mine + 1u ? prefix : s_kmin));
 }
 
-struct LinBufs {
-    LinState *lin;
-    float *lists;
-    uint32_t *flags;
+// profiler rows of the launches below that name V (the rows are matched by name: bench.py, profiles/f32t_stats.py)
+template <typename V>
+struct LinRows;
+template <>
+struct LinRows<float> {
+    static constexpr const char *sample = "k_lin_sample<float>", *scan = "k_lin_scan<float>", *collect = "k_lin_collect<float>",
+                                *collect_src = "(k_lin_collect_src<float, 4>)", *finish = "k_lin_finish<float>";
 };
-LinBufs carve_lin(Carver &c, Shape s)
-{
-    LinBufs b;
-    const size_t nbc = (size_t)s.B * 3;
-    b.lin = c.take<LinState>(nbc);
-    b.flags = c.take<uint32_t>(nbc);
-    b.lists = reinterpret_cast<float *>(c.take<double>(nbc * kLinLists * lin_cap(s)));  // (sized for the float64 surface)
-    return b;
-}
+template <>
+struct LinRows<double> {
+    static constexpr const char *sample = "k_lin_sample<double>", *scan = "k_lin_scan<double>", *collect = "k_lin_collect<double>",
+                                *collect_src = "k_lin_collect_src64", *finish = "k_lin_finish<double>";
+};
 
 }  // namespace
 
-int select_lin_begin(Shape s, const double *q_percent, int nq, void *ws, hipStream_t st, SelectPlan *plan,
-                     const RestoreSrc *predict)
+size_t select_ws_bytes(Shape s)
 {
-    UWIE_REQUIRE(nq >= 1 && nq <= kMaxPct, "percentiles: 1..4 percentiles per call");
-    const long long n = (long long)s.npx();
-    UWIE_REQUIRE(n >= 1 && n < (1ll << 31), "percentiles: plane size out of range");
-    Carver c(ws);
-    const int nbc = s.B * 3;
-    plan->state = c.take<SelState<uint64_t>>(nbc);
-    plan->ghist = c.take<uint32_t>((size_t)nbc * kMaxRanks * kBins);
-    plan->os = c.take<double>((size_t)nbc * kMaxRanks);
-    const LinBufs lb = carve_lin(c, s);
-    plan->lin = lb.lin;
-    plan->lists = lb.lists;
-    plan->flags = lb.flags;
-    plan->cap = lin_cap(s);
-    plan->nq = nq;
-    plan->is64 = false;
-    for (int j = 0; j < nq; ++j)
-        percentile_indices<float>(n, q_percent[j], &plan->ranks[2 * j], &plan->ranks[2 * j + 1], &plan->t[j]);
+    Carver c(nullptr);
+    SelectPlan plan;
+    carve_select(c, s, true, &plan);
+    return c.total();
+}
+
+// Before the producer: the plan, zeroed counters and (predict) the windows of bins predicted from a sample of *predict.
+template <typename V>
+int select_lin_begin(Shape s, const double *q_percent, int nq, void *ws, hipStream_t st, SelectPlan *plan, const RestoreSrc *predict)
+{
+    constexpr bool f64 = sizeof(V) == 8;
+    int rc = plan_percentiles<V>(s, q_percent, nq, ws, true, plan);
     // only the first kLinBins counters of every (image, channel) are used by the producer (and kLinBins more by the sample)
-    UWIE_HIP_CHECK(hipMemsetAsync(plan->ghist, 0, sizeof(uint32_t) * (size_t)nbc * kMaxRanks * kBins, st));
-    RankList ranks;
-    ranks.n = 2 * nq;
-    for (int j = 0; j < ranks.n; ++j) ranks.r[j] = plan->ranks[j];
-    uint32_t ns = 0;
+    if (rc == UWIE_OK) rc = zero_ghist(*plan, s, st);
+    if (rc != UWIE_OK) return rc;
+    const int n = (int)s.npx(), nbc = s.B * 3;
+    // ~128 K sample pixels per frame in evenly spaced groups of four (odd stride: no column is favoured): the
+    // sampling error of a 1 % rank is ~0.03 % of the frame, half a bin where the 2048 bins are equally full
+    const int ngroups = n / 4;
     // tuning (tests): lin_no_predict switches the prediction off, lin_predict_shift = k moves the predicted windows k bins
-    // up (a large shift makes every prediction miss: collecting-sweep fallback)
-    const int shift = tune().lin_predict_shift;
-    plan->predicted = false;
-    if (predict && !tune().lin_no_predict) {
-        plan->predicted = true;
-        // ~128 K sample pixels per frame in evenly spaced groups of four (odd stride: no column is favoured): the
-        // sampling error of a 1 % rank is ~0.03 % of the frame, half a bin where the 2048 bins are equally full
-        const int ngroups = (int)(n / 4);
-        if (ngroups > 0) {
-            int stride = std::max(1, ngroups / 32768);
-            if (stride > 1) stride |= 1;
-            const int ngs = ngroups / stride;
-            ns = 4u * (uint32_t)ngs;
-            UWIE_LAUNCH(k_lin_sample<float>, dim3(std::max(1, std::min(8, cdiv(ngs, 512))), s.B), dim3(256), 0, st, *predict, (int)n,
-                        stride, ngs, plan->ghist);
-            UWIE_LAUNCH_CHECK();
-        }
+    // up (a large shift makes every prediction miss: collecting-sweep fallback).
+    // The float64 terms.  nq <= 2 has to be there: the float64 producer files two windows at most (launch_recover64_planar_hist
+    // refuses a larger plan) where the float32 one has a four-window variant.  ngroups > 0 need not differ: a plane of fewer
+    // than four pixels gets no sample and so no window on either surface, every query takes the collecting sweep, and
+    // `predicted` then only picks that sweep's grid (select_lin_run) and, in float32, opens the rank route, which asks for
+    // four pixels itself.  Float32 has always said true there and float64 false; both are kept as they were.
+    plan->predicted = predict && !tune().lin_no_predict && (!f64 || (nq <= 2 && ngroups > 0));
+    uint32_t ns = 0;
+    if (plan->predicted && ngroups > 0) {
+        int stride = std::max(1, ngroups / 32768);
+        if (stride > 1) stride |= 1;
+        const int ngs = ngroups / stride;
+        ns = 4u * (uint32_t)ngs;
+        UWIE_LAUNCH_AS(LinRows<V>::sample, k_lin_sample<V>, dim3(std::max(1, std::min(8, cdiv(ngs, 512))), s.B), dim3(256), 0, st,
+                       *predict, n, stride, ngs, plan->ghist);
+        UWIE_LAUNCH_CHECK();
     }
-    UWIE_LAUNCH(k_lin_predict, dim3(nbc), dim3(256), 0, st, (LinState *)plan->lin, plan->ghist, ranks, (uint32_t)n, ns,
-                shift);
+    UWIE_LAUNCH(k_lin_predict, dim3(nbc), dim3(256), 0, st, plan->lin, plan->ghist, rank_list(*plan), (uint32_t)n, ns,
+                tune().lin_predict_shift);
     UWIE_LAUNCH_CHECK();
     return UWIE_OK;
 }
 
 // After the producer has filled the linear-digit histogram: scan -> one collecting sweep -> finish on the lists;
 // planes whose list overflowed (a heavy bin, e.g. a constant image) take the key-digit passes.
-int select_lin_run(const SelectPlan &plan, const float *d_planar, Shape s, hipStream_t st, const RestoreSrc *src)
+template <typename V>
+int select_lin_run(const SelectPlan &plan, const V *d_planar, Shape s, hipStream_t st, const RestoreSrc *src)
 {
+    using Rows = LinRows<V>;
     const int n = (int)s.npx(), nbc = s.B * 3;
-    RankList ranks;
-    ranks.n = 2 * plan.nq;
-    for (int j = 0; j < ranks.n; ++j) ranks.r[j] = plan.ranks[j];
+    const RankList ranks = rank_list(plan);
     UWIE_REQUIRE(!src || ranks.n <= 4, "select_lin_run: the recomputing sweep handles at most two percentiles");
-    LinState *lin = (LinState *)plan.lin;
-    UWIE_LAUNCH(k_lin_scan<float>, dim3(nbc), dim3(256), 0, st, lin, plan.ghist, ranks, (float *)plan.os, plan.flags, plan.cap,
-                (SelState<uint32_t> *)plan.state);
+    V *lists = plan.lists_as<V>(), *os = (V *)plan.os;
+    UWIE_LAUNCH_AS(Rows::scan, k_lin_scan<V>, dim3(nbc), dim3(256), 0, st, plan.lin, plan.ghist, ranks, os, plan.flags, plan.cap,
+                   (SelState<typename Traits<V>::K> *)plan.state);
     UWIE_LAUNCH_CHECK();
     int blocks = (int)(((long long)n + 131071) / 131072);
     if (blocks * nbc < 1024) blocks = cdiv(1024, nbc);
@@ -1236,185 +1245,53 @@ int select_lin_run(const SelectPlan &plan, const float *d_planar, Shape s, hipSt
     if (plan.predicted) blocks = std::max(1, std::min(2 * blocks, cdiv(24576, nbc)));
     if (src) {
         const int per_image = std::min(3 * blocks, std::max(1, cdiv(n, 2048)));
-        UWIE_LAUNCH((k_lin_collect_src<float, 4>), dim3(per_image, s.B), dim3(256), 0, st, *src, n, lin, plan.lists, plan.cap);
+        UWIE_LAUNCH_AS(Rows::collect_src, (k_lin_collect_src<V, 4>), dim3(per_image, s.B), dim3(256), 0, st, *src, n, plan.lin, lists,
+                       plan.cap);
     } else {
-        UWIE_LAUNCH(k_lin_collect<float>, dim3(blocks, nbc), dim3(256), 0, st, (const float *)d_planar, n, lin, plan.lists, plan.cap);
+        UWIE_LAUNCH_AS(Rows::collect, k_lin_collect<V>, dim3(blocks, nbc), dim3(256), 0, st, d_planar, n, plan.lin, lists, plan.cap);
     }
     UWIE_LAUNCH_CHECK();
-    UWIE_LAUNCH(k_lin_finish<float>, dim3(nbc, ranks.n), dim3(1024), 0, st, lin, (const float *)plan.lists, plan.cap, (float *)plan.os,
-                plan.flags, 0, kLinLists);
+    UWIE_LAUNCH_AS(Rows::finish, k_lin_finish<V>, dim3(nbc, ranks.n), dim3(1024), 0, st, plan.lin, lists, plan.cap, os,
+                   plan.flags, 0, kLinLists);
     UWIE_LAUNCH_CHECK();
     // the flagged planes: the key-digit passes over their recomputed or stored values (they return at once for the others)
-    if (src) return sel_passes(plan, RestoredVals<float>{*src, n}, n, nbc, pass_blocks(n, nbc, true), false, plan.flags, st);
-    const StoredVals<float> vals{d_planar, (size_t)n * 3, (size_t)n, 1};
+    if (src) return sel_passes(plan, RestoredVals<V>{*src, n}, n, nbc, pass_blocks(n, nbc, true), false, plan.flags, st);
+    const StoredVals<V> vals{d_planar, (size_t)n * 3, (size_t)n, 1};
     return sel_passes(plan, vals, n, nbc, pass_blocks(n, nbc, false), false, plan.flags, st);
 }
+
+template int select_lin_begin<float>(Shape, const double *, int, void *, hipStream_t, SelectPlan *, const RestoreSrc *);
+template int select_lin_run<float>(const SelectPlan &, const float *, Shape, hipStream_t, const RestoreSrc *);
+template int select_lin_begin<double>(Shape, const double *, int, void *, hipStream_t, SelectPlan *, const RestoreSrc *);
+template int select_lin_run<double>(const SelectPlan &, const double *, Shape, hipStream_t, const RestoreSrc *);
 
 // After launch_restore_rank: scan -> finish on the window lists; flagged planes take the key-digit passes.
 int select_rank_run(const SelectPlan &plan, Shape s, hipStream_t st, const RestoreSrc &src)
 {
     const int n = (int)s.npx(), nbc = s.B * 3;
-    RankList ranks;
-    ranks.n = 2 * plan.nq;
-    for (int j = 0; j < ranks.n; ++j) ranks.r[j] = plan.ranks[j];
-    LinState *lin = (LinState *)plan.lin;
-    UWIE_LAUNCH(k_rank_scan, dim3(cdiv(nbc, 64)), dim3(64), 0, st, lin, ranks, (float *)plan.os, plan.flags, kRankCapMul * plan.cap, nbc,
-                (SelState<uint32_t> *)plan.state);
+    const RankList ranks = rank_list(plan);
+    UWIE_LAUNCH(k_rank_scan, dim3(cdiv(nbc, 64)), dim3(64), 0, st, plan.lin, ranks, (float *)plan.os, plan.flags, kRankCapMul * plan.cap,
+                nbc, (SelState<uint32_t> *)plan.state);
     UWIE_LAUNCH_CHECK();
-    UWIE_LAUNCH(k_lin_finish<float>, dim3(nbc, ranks.n), dim3(1024), 0, st, lin, (const float *)plan.lists, kRankCapMul * plan.cap,
-                (float *)plan.os, plan.flags, 1, kLinLists / kRankCapMul);
+    UWIE_LAUNCH(k_lin_finish<float>, dim3(nbc, ranks.n), dim3(1024), 0, st, plan.lin, plan.lists_as<float>(),
+                kRankCapMul * plan.cap, (float *)plan.os, plan.flags, 1, kLinLists / kRankCapMul);
     UWIE_LAUNCH_CHECK();
     return sel_passes(plan, RestoredVals<float>{src, n}, n, nbc, pass_blocks(n, nbc, true), false, plan.flags, st);
 }
 
-// float64 planes (ES surface): the same selection without the prediction; the lists hold doubles
-int select_lin_begin64(Shape s, const double *q_percent, int nq, void *ws, hipStream_t st, SelectPlan *plan,
-                       const RestoreSrc *predict)
-{
-    UWIE_REQUIRE(nq >= 1 && nq <= kMaxPct, "percentiles: 1..4 percentiles per call");
-    const long long n = (long long)s.npx();
-    UWIE_REQUIRE(n >= 1 && n < (1ll << 31), "percentiles: plane size out of range");
-    Carver c(ws);
-    const int nbc = s.B * 3;
-    plan->state = c.take<SelState<uint64_t>>(nbc);
-    plan->ghist = c.take<uint32_t>((size_t)nbc * kMaxRanks * kBins);
-    plan->os = c.take<double>((size_t)nbc * kMaxRanks);
-    const LinBufs lb = carve_lin(c, s);
-    plan->lin = lb.lin;
-    plan->lists = lb.lists;
-    plan->flags = lb.flags;
-    plan->cap = lin_cap(s);
-    plan->nq = nq;
-    plan->is64 = true;
-    for (int j = 0; j < nq; ++j)
-        percentile_indices<double>(n, q_percent[j], &plan->ranks[2 * j], &plan->ranks[2 * j + 1], &plan->t[j]);
-    UWIE_HIP_CHECK(hipMemsetAsync(plan->ghist, 0, sizeof(uint32_t) * (size_t)nbc * kMaxRanks * kBins, st));
-    RankList ranks;
-    ranks.n = 2 * nq;
-    for (int j = 0; j < ranks.n; ++j) ranks.r[j] = plan->ranks[j];
-    // prediction as in select_lin_begin (same tuning selectors)
-    uint32_t ns = 0;
-    const int shift = tune().lin_predict_shift;
-    plan->predicted = false;
-    const int ngroups = (int)(n / 4);
-    if (predict && nq <= 2 && ngroups > 0 && !tune().lin_no_predict) {
-        plan->predicted = true;
-        int stride = std::max(1, ngroups / 32768);
-        if (stride > 1) stride |= 1;
-        const int ngs = ngroups / stride;
-        ns = 4u * (uint32_t)ngs;
-        UWIE_LAUNCH(k_lin_sample<double>, dim3(std::max(1, std::min(8, cdiv(ngs, 512))), s.B), dim3(256), 0, st, *predict, (int)n,
-                    stride, ngs, plan->ghist);
-        UWIE_LAUNCH_CHECK();
-    }
-    UWIE_LAUNCH(k_lin_predict, dim3(nbc), dim3(256), 0, st, (LinState *)plan->lin, plan->ghist, ranks, (uint32_t)n, ns, shift);
-    UWIE_LAUNCH_CHECK();
-    return UWIE_OK;
-}
-
-int select_lin_run64(const SelectPlan &plan, const double *d_planar, Shape s, hipStream_t st, const RestoreSrc *src)
-{
-    const int n = (int)s.npx(), nbc = s.B * 3;
-    RankList ranks;
-    ranks.n = 2 * plan.nq;
-    for (int j = 0; j < ranks.n; ++j) ranks.r[j] = plan.ranks[j];
-    UWIE_REQUIRE(!src || ranks.n <= 4, "select_lin_run64: the recomputing sweep handles at most two percentiles");
-    LinState *lin = (LinState *)plan.lin;
-    double *lists = reinterpret_cast<double *>(plan.lists);
-    UWIE_LAUNCH(k_lin_scan<double>, dim3(nbc), dim3(256), 0, st, lin, plan.ghist, ranks, (double *)plan.os, plan.flags, plan.cap,
-                (SelState<uint64_t> *)plan.state);
-    UWIE_LAUNCH_CHECK();
-    int blocks = (int)(((long long)n + 131071) / 131072);
-    if (blocks * nbc < 1024) blocks = cdiv(1024, nbc);
-    blocks = blocks < 1 ? 1 : blocks > 256 ? 256 : blocks;
-    if (plan.predicted) blocks = std::max(1, std::min(2 * blocks, cdiv(24576, nbc)));  // (see select_lin_run)
-    if (src) {
-        const int per_image = std::min(3 * blocks, std::max(1, cdiv(n, 2048)));
-        const auto k_lin_collect_src64 = k_lin_collect_src<double, 4>;
-        UWIE_LAUNCH(k_lin_collect_src64, dim3(per_image, s.B), dim3(256), 0, st, *src, n, lin, lists, plan.cap);
-    } else {
-        UWIE_LAUNCH(k_lin_collect<double>, dim3(blocks, nbc), dim3(256), 0, st, (const double *)d_planar, n, lin, lists, plan.cap);
-    }
-    UWIE_LAUNCH_CHECK();
-    UWIE_LAUNCH(k_lin_finish<double>, dim3(nbc, ranks.n), dim3(1024), 0, st, lin, (const double *)lists, plan.cap, (double *)plan.os,
-                plan.flags, 0, kLinLists);
-    UWIE_LAUNCH_CHECK();
-    // the flagged planes: the key-digit passes over their recomputed or stored values (they return at once for the others)
-    if (src) return sel_passes(plan, RestoredVals<double>{*src, n}, n, nbc, pass_blocks(n, nbc, true), false, plan.flags, st);
-    const StoredVals<double> vals{d_planar, (size_t)n * 3, (size_t)n, 1};
-    return sel_passes(plan, vals, n, nbc, pass_blocks(n, nbc, false), false, plan.flags, st);
-}
-
-size_t select_ws_bytes(Shape s)
-{
-    Carver c(nullptr);
-    const size_t nbc = (size_t)s.B * 3;
-    c.take<SelState<uint64_t>>(nbc);
-    c.take<uint32_t>(nbc * kMaxRanks * kBins);
-    c.take<double>(nbc * kMaxRanks);
-    carve_lin(c, s);
-    return c.total();
-}
-
 int select_begin_stretch_ranks(Shape s, const float *d_params, int stride, void *ws, hipStream_t st, SelectPlan *plan)
 {
-    const long long n = (long long)s.npx();
-    UWIE_REQUIRE(n >= 1 && n < (1ll << 31), "stretch ranks: plane size out of range");
-    Carver c(ws);
-    const int nbc = s.B * 3;
-    plan->state = c.take<SelState<uint64_t>>(nbc);
-    plan->ghist = c.take<uint32_t>((size_t)nbc * kMaxRanks * kBins);
-    plan->os = c.take<double>((size_t)nbc * kMaxRanks);
-    plan->nq = 1;  // two ranks
-    plan->is64 = false;
-    plan->t[0] = 0.0;
-    UWIE_LAUNCH(k_sel_init_stretch_ranks, dim3(cdiv(nbc, 64)), dim3(64), 0, st, (SelState<uint32_t> *)plan->state, nbc,
-                d_params, stride, (int)n);
-    UWIE_LAUNCH_CHECK();
-    UWIE_HIP_CHECK(hipMemsetAsync(plan->ghist, 0, sizeof(uint32_t) * (size_t)nbc * kMaxRanks * kBins, st));
-    return UWIE_OK;
+    return begin_ranks(s, "stretch ranks: plane size out of range", ws, st, plan, [&](SelState<uint32_t> *state, int nbc, int n) {
+        UWIE_LAUNCH(k_sel_init_stretch_ranks, dim3(cdiv(nbc, 64)), dim3(64), 0, st, state, nbc, d_params, stride, n);
+    });
 }
 
 int select_begin_gated_ranks(Shape s, const float *d_params, int stride, uint32_t *d_status, void *ws, hipStream_t st,
                              SelectPlan *plan)
 {
-    const long long n = (long long)s.npx();
-    UWIE_REQUIRE(n >= 1 && n < (1ll << 31), "gated ranks: plane size out of range");
-    Carver c(ws);
-    const int nbc = s.B * 3;
-    plan->state = c.take<SelState<uint64_t>>(nbc);
-    plan->ghist = c.take<uint32_t>((size_t)nbc * kMaxRanks * kBins);
-    plan->os = c.take<double>((size_t)nbc * kMaxRanks);
-    plan->nq = 1;  // two ranks
-    plan->is64 = false;
-    plan->t[0] = 0.0;
-    UWIE_LAUNCH(k_sel_init_gated_ranks, dim3(cdiv(nbc, 64)), dim3(64), 0, st, (SelState<uint32_t> *)plan->state, nbc,
-                d_params, stride, (int)n, d_status);
-    UWIE_LAUNCH_CHECK();
-    UWIE_HIP_CHECK(hipMemsetAsync(plan->ghist, 0, sizeof(uint32_t) * (size_t)nbc * kMaxRanks * kBins, st));
-    return UWIE_OK;
-}
-
-int select_begin(Shape s, const double *q, int nq, void *ws, hipStream_t st, SelectPlan *plan)
-{
-    return begin_t<float>(s, q, nq, ws, st, plan);
-}
-int select_begin64(Shape s, const double *q, int nq, void *ws, hipStream_t st, SelectPlan *plan)
-{
-    return begin_t<double>(s, q, nq, ws, st, plan);
-}
-int select_run(const SelectPlan &plan, const float *d_vals, int planar, Shape s, bool pass1_done, hipStream_t st)
-{
-    return run_t<float>(plan, d_vals, planar, s, pass1_done, st);
-}
-int select_run64(const SelectPlan &plan, const double *d_vals, int planar, Shape s, bool pass1_done, hipStream_t st)
-{
-    return run_t<double>(plan, d_vals, planar, s, pass1_done, st);
-}
-int select_lerp(const SelectPlan &plan, Shape s, float *d_out, hipStream_t st) { return lerp_t<float>(plan, s, d_out, st); }
-int select_lerp64(const SelectPlan &plan, Shape s, double *d_out, hipStream_t st)
-{
-    return lerp_t<double>(plan, s, d_out, st);
+    return begin_ranks(s, "gated ranks: plane size out of range", ws, st, plan, [&](SelState<uint32_t> *state, int nbc, int n) {
+        UWIE_LAUNCH(k_sel_init_gated_ranks, dim3(cdiv(nbc, 64)), dim3(64), 0, st, state, nbc, d_params, stride, n, d_status);
+    });
 }
 
 int select_lerp_chain(const SelectPlan &plan, Shape s, float eps, float *d_pct4, hipStream_t st)
@@ -1429,26 +1306,58 @@ int select_lerp_chain(const SelectPlan &plan, Shape s, float eps, float *d_pct4,
     return UWIE_OK;
 }
 
-int launch_percentiles_f32(const float *d_vals, int planar, Shape s, const double *q_percent, int nq, float *d_out,
-                           void *ws, hipStream_t st)
+// ===================================================================================== the key-digit route on stored values
+template <typename V>
+int select_begin(Shape s, const double *q_percent, int nq, void *ws, hipStream_t st, SelectPlan *plan)
+{
+    using K = typename Traits<V>::K;
+    const int rc = plan_percentiles<V>(s, q_percent, nq, ws, false, plan);
+    if (rc != UWIE_OK) return rc;
+    const int nbc = s.B * 3;
+    UWIE_LAUNCH(k_sel_init<K>, dim3(cdiv(nbc, 64)), dim3(64), 0, st, (SelState<K> *)plan->state, nbc, rank_list(*plan));
+    UWIE_LAUNCH_CHECK();
+    return zero_ghist(*plan, s, st);
+}
+
+template <typename V>
+int select_run(const SelectPlan &plan, const V *d_vals, int planar, Shape s, bool pass1_done, hipStream_t st)
+{
+    const int n = (int)s.npx(), nbc = s.B * 3;
+    const StoredVals<V> src{d_vals, (size_t)n * 3, planar ? (size_t)n : (size_t)1, planar ? 1 : 3};
+    return sel_passes(plan, src, n, nbc, pass_blocks(n, nbc, false), pass1_done, nullptr, st);
+}
+
+template <typename V>
+int select_lerp(const SelectPlan &plan, Shape s, V *d_out, hipStream_t st)
+{
+    FracList<V> fr;
+    fr.n = plan.nq;
+    for (int j = 0; j < plan.nq; ++j) fr.t[j] = (V)plan.t[j];
+    const int nbc = s.B * 3;
+    UWIE_LAUNCH(k_pct_finish<V>, dim3(cdiv(nbc * plan.nq, 64)), dim3(64), 0, st, (const V *)plan.os, nbc, fr, d_out);
+    UWIE_LAUNCH_CHECK();
+    return UWIE_OK;
+}
+
+template <typename V>
+int launch_percentiles(const V *d_vals, int planar, Shape s, const double *q_percent, int nq, V *d_out, void *ws, hipStream_t st)
 {
     SelectPlan plan;
-    int rc = select_begin(s, q_percent, nq, ws, st, &plan);
+    int rc = select_begin<V>(s, q_percent, nq, ws, st, &plan);
     if (rc != UWIE_OK) return rc;
     rc = select_run(plan, d_vals, planar, s, false, st);
     if (rc != UWIE_OK) return rc;
     return select_lerp(plan, s, d_out, st);
 }
 
-int launch_percentiles_f64(const double *d_vals, Shape s, const double *q_percent, int nq, double *d_out, void *ws, hipStream_t st)
-{
-    SelectPlan plan;
-    int rc = select_begin64(s, q_percent, nq, ws, st, &plan);
-    if (rc != UWIE_OK) return rc;
-    rc = select_run64(plan, d_vals, 0, s, false, st);
-    if (rc != UWIE_OK) return rc;
-    return select_lerp64(plan, s, d_out, st);
-}
+template int select_begin<float>(Shape, const double *, int, void *, hipStream_t, SelectPlan *);
+template int select_begin<double>(Shape, const double *, int, void *, hipStream_t, SelectPlan *);
+template int select_run<float>(const SelectPlan &, const float *, int, Shape, bool, hipStream_t);
+template int select_run<double>(const SelectPlan &, const double *, int, Shape, bool, hipStream_t);
+template int select_lerp<float>(const SelectPlan &, Shape, float *, hipStream_t);
+template int select_lerp<double>(const SelectPlan &, Shape, double *, hipStream_t);
+template int launch_percentiles<float>(const float *, int, Shape, const double *, int, float *, void *, hipStream_t);
+template int launch_percentiles<double>(const double *, int, Shape, const double *, int, double *, void *, hipStream_t);
 
 namespace {
 __global__ void k_widen_f32(const float *__restrict__ in, double *__restrict__ out, size_t n)
