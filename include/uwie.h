@@ -287,6 +287,27 @@ int uwie_diff_enhance_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_
                               float *d_grad_params, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * The same module for u8 frames, in the byte domain (k_diffenh_u8.hip): what
+ * EnhancementPredictor.process_single_image does from a decoded frame to a u8 frame (use_trained_model.py:113-164).
+ * d_in: [batch][H][W][3] uint8, the frame whose float image is u8 / 255.  x = (float)v / 255.0f is strictly increasing in
+ * the byte v, so the two sorted positions are two bins of the channel's 256-bin histogram and the stretch takes at most
+ * 256 values per channel: two passes over the frame's bytes (count, apply), no float image anywhere.
+ *   d_out_u8  [batch][H][W][3] uint8   = (uint8)(v * 255.0f) of the module's clamped output v (it holds no NaN: the final
+ *             clamp turns NaN into 0), the bytes of (np.clip(enhanced, 0, 1) * 255).astype(np.uint8)
+ *   d_out_f32 [batch][H][W][3] float32 = v, the bits uwie_diff_enhance_f32 gives for uwie_u8_to_f32 of the frame
+ *   Either may be NULL, not both (UWIE_E_INVALID).  d_saved (optional): as uwie_diff_enhance_save_f32 leaves it.
+ * d_in must be 4-byte aligned (UWIE_E_INVALID otherwise: the count pass reads dwords); the outputs need no alignment beyond
+ * their element types.  Every check runs before the first launch.
+ * Workspace: uwie_workspace_bytes_diff_u8(batch, H, W) = the histograms and the order statistics, about 3 KB per image
+ * whatever H x W is (0: batch/H/W out of range).
+ */
+size_t uwie_workspace_bytes_diff_u8(int batch, int H, int W);
+int uwie_diff_enhance_u8(uwie_ctx *ctx, const uint8_t *d_in, uint8_t *d_out_u8, float *d_out_f32, int batch, int H, int W,
+                         const float *d_params /* [batch][4] L_low, L_high, omega, gamma */,
+                         int flags /* UWIE_DIFF_OMEGA | UWIE_DIFF_GAMMA */, float *d_saved /* optional */, void *d_workspace,
+                         size_t workspace_bytes, void *stream);
+
+/*
  * deep_learning_parameters.DifferentiableEnhancement (deep_learning_parameters.py:24-90), the module EndToEndTrainer trains
  * through (the contract: DESIGN.md section 10).  Per plane: stretch between the sorted positions k = int(L_low / 100.0 * n)
  * and int(L_high / 100.0 * n) with Python's indexing rules (no clamp: a negative k counts from the end; an image whose k is

@@ -108,6 +108,8 @@ SIGNATURES = {
     "uwie_diff_enhance_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _SZ, _VP],
     "uwie_diff_enhance_save_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _SZ, _VP],
     "uwie_diff_enhance_bwd_workspace_bytes": [_I, _I, _I],
+    "uwie_workspace_bytes_diff_u8": [_I, _I, _I],
+    "uwie_diff_enhance_u8": [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _SZ, _VP],
     "uwie_diff_enhance_bwd_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP],
     "uwie_diff_gated_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _SZ, _VP],
     "uwie_diff_gated_save_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _SZ, _VP],
@@ -169,6 +171,7 @@ _RESTYPES = {
     "uwie_workspace_bytes_float": ctypes.c_size_t,
     "uwie_workspace_bytes_select": ctypes.c_size_t,
     "uwie_diff_enhance_bwd_workspace_bytes": ctypes.c_size_t,
+    "uwie_workspace_bytes_diff_u8": ctypes.c_size_t,
     "uwie_diff_gated_bwd_workspace_bytes": ctypes.c_size_t,
     "uwie_ref_loss_workspace_bytes": ctypes.c_size_t,
     "uwie_workspace_bytes_feature_extractor": ctypes.c_size_t,

@@ -643,7 +643,9 @@ class EnhancementPredictor:
     Python floats (clamped as :70-79); for a ``[B,H,W,3]`` batch, one float64 array per key.  ``enhance_image(img, params)``
     returns float32 HxWx3, clipped to [0, 1] with NaN and infinities replaced as :101-111.  ``enhance_batch(frames)`` runs
     the whole chain for a batch as one device pipeline (no host read between the stages) and returns ``[B,H,W,3]`` float32
-    on the device, equal to B ``enhance_image`` calls bit for bit."""
+    on the device, equal to B ``enhance_image`` calls bit for bit.  ``enhance_batch_u8(frames)`` goes on to the uint8
+    frame ``process_single_image`` writes, in the byte domain; ``process_frames(list)`` is ``process_folder``'s loop for
+    decoded frames of mixed sizes."""
 
     def __init__(self, weights, input_size: int = 224, device: int | None = None):
         self.input_size = int(input_size)
@@ -686,13 +688,17 @@ class EnhancementPredictor:
         feats = dev.extract_features_u8(u8)
         return self.model._device_forward(dev, x, feats)[0]
 
-    def _clamped(self, dev: Device, u8):
-        """float32 [B,4] (omega, gamma, L_low, L_high) on the device = float32(np.clip(float(v), lo, hi)) of the network's
-        outputs: the reference's float64 clip (:74-77), then the float32 tensor of enhance_image (:96-103).  NaN stays NaN."""
-        raw = self._raw(dev, u8).double()
+    @staticmethod
+    def _clip(dev: Device, raw):
+        """float32(np.clip(float(v), lo, hi)) of the network's float32 [B,4] on the device: the reference's float64 clip
+        (:74-77), then the float32 tensor of enhance_image (:96-103).  NaN stays NaN."""
         lo = torch.tensor([PREDICTOR_CLIP[k][0] for k in PARAM_KEYS], dtype=torch.float64, device=dev.torch_device)
         hi = torch.tensor([PREDICTOR_CLIP[k][1] for k in PARAM_KEYS], dtype=torch.float64, device=dev.torch_device)
-        return torch.minimum(torch.maximum(raw, lo), hi).float()
+        return torch.minimum(torch.maximum(raw.double(), lo), hi).float()
+
+    def _clamped(self, dev: Device, u8):
+        """float32 [B,4] (omega, gamma, L_low, L_high) on the device: the network's outputs, clipped (_clip)."""
+        return self._clip(dev, self._raw(dev, u8))
 
     @staticmethod
     def _enhance(dev: Device, u8, cols):
@@ -731,6 +737,77 @@ class EnhancementPredictor:
         clipped = self._clamped(dev, u8)
         out = self._enhance(dev, u8, clipped[:, [2, 3, 0, 1]].contiguous()).clamp_(0.0, 1.0)
         return torch.nan_to_num_(out, nan=0.0, posinf=1.0, neginf=0.0).clamp_(0.0, 1.0)
+
+    def _batch_u8(self, dev: Device, u8):
+        """(out_u8, clamped float32 [B,4], the network's raw float32 [B,4]) for uint8 frames on the device: the network, the
+        clip and the module in the byte domain (uwie_diff_enhance_u8), no host read in between."""
+        raw = self._raw(dev, u8)
+        clipped = self._clip(dev, raw)
+        out, _ = dev.diff_enhance_u8(u8, clipped[:, [2, 3, 0, 1]].contiguous(), 3, want_u8=True, want_f32=False)
+        return out, clipped, raw
+
+    def enhance_batch_u8(self, frames):
+        """``process_single_image``'s u8 result (use_trained_model.py:118-127) for a batch, as one device pipeline:
+        ``(out_u8 [B,H,W,3] uint8 on the device, params float32 [B,4] = omega, gamma, L_low, L_high, clamped)``.  ``frames`` as
+        for ``enhance_batch``; ``out_u8`` equals ``(enhance_batch(frames) * 255).to(uint8)``.  The enhancement runs on the
+        frames' bytes: no float image is made."""
+        dev = get_device(self.device)
+        u8, _ = self._frames(frames, dev)
+        out, clipped, _ = self._batch_u8(dev, u8)
+        return out, clipped
+
+    @staticmethod
+    def _param_dicts(raw):
+        """predict_parameters' dicts (six Python floats each) from the network's raw outputs, float32 [B,4] on the host."""
+        raw = np.asarray(raw, dtype=np.float64)
+        dicts = []
+        for row in raw:
+            d = {k: float(np.clip(row[i], *PREDICTOR_CLIP[k])) for i, k in enumerate(PARAM_KEYS)}
+            d["guided_radius"] = 15.0
+            d["use_gamma"] = 1.0
+            dicts.append(d)
+        return dicts
+
+    def process_frames(self, frames, filenames=None):
+        """``process_folder``'s loop (use_trained_model.py:145-164) without the file I/O, for decoded frames whose sizes may
+        differ: ``frames`` is a sequence of HxWx3 frames (uint8, or float images equal to u8 / 255), ``filenames`` optional
+        names for the messages.  Frames of equal shape go through one ``enhance_batch_u8`` call per shape.  Returns
+        ``(outputs, params)`` in input order: ``outputs[i]`` the enhanced uint8 HxWx3 NumPy frame, ``params[i]`` the dict
+        ``predict_parameters`` gives for it.  A frame that raises does not stop the others (:163-164): its output is ``None``
+        and its ``params`` entry is the exception's message (prefixed with its file name when names are given).  Input
+        errors are found per frame before any launch; an error of a group's device run fails that group's frames."""
+        frames = list(frames)
+        if filenames is not None and len(filenames) != len(frames):
+            raise ValueError(f"{len(filenames)} file names for {len(frames)} frames")
+        dev = get_device(self.device)
+        outputs, params = [None] * len(frames), [None] * len(frames)
+
+        def fail(i, e):
+            outputs[i] = None
+            params[i] = f"{filenames[i]}: {e}" if filenames is not None else str(e)
+
+        groups = {}
+        for i, f in enumerate(frames):
+            try:
+                u8, single = self._frames(f, dev)
+                if not single:
+                    raise ValueError(f"process_frames takes HxWx3 frames, got {tuple(u8.shape)}")
+                groups.setdefault(tuple(u8.shape), []).append((i, u8))
+            except Exception as e:  # noqa: BLE001 - the reference's loop catches everything (:163)
+                fail(i, e)
+
+        for members in groups.values():
+            try:
+                out, _, raw = self._batch_u8(dev, torch.cat([u8 for _, u8 in members]))
+                out, raw = out.cpu().numpy(), raw.cpu().numpy()
+                dev.check_status()
+            except Exception as e:  # noqa: BLE001 - a device error: the whole group fails, nothing is launched again for it
+                for i, _ in members:
+                    fail(i, e)
+                continue
+            for (i, _), o, d in zip(members, out, self._param_dicts(raw)):
+                outputs[i], params[i] = o, d
+        return outputs, params
 
 
 QUALITY_KEYS = ("contrast", "sharpness", "entropy", "saturation", "brightness", "edge_density", "colorfulness", "naturalness")

@@ -1152,6 +1152,26 @@ int uwie_diff_enhance_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_
                       "diff_enhance_bwd: d_grad_img must not alias d_img or d_grad_out", d_workspace, workspace_bytes, stream);
 }
 
+size_t uwie_workspace_bytes_diff_u8(int batch, int H, int W)
+{
+    if (!shape_ok(batch, H, W)) return 0;
+    return diff_u8_ws_bytes(Shape{batch, H, W});
+}
+
+int uwie_diff_enhance_u8(uwie_ctx *ctx, const uint8_t *d_in, uint8_t *d_out_u8, float *d_out_f32, int batch, int H, int W,
+                         const float *d_params, int flags, float *d_saved, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE(ctx && d_in && d_params, "diff_enhance_u8: NULL pointer");
+    UWIE_REQUIRE(d_out_u8 || d_out_f32, "diff_enhance_u8: at least one of d_out_u8, d_out_f32");
+    UWIE_REQUIRE(((uintptr_t)d_in & 3) == 0, "diff_enhance_u8: d_in must be 4-byte aligned");  // k_frame_hist reads dwords
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_REQUIRE((flags & ~3) == 0, "diff_enhance_u8: flags are UWIE_DIFF_OMEGA | UWIE_DIFF_GAMMA");
+    const Shape s{batch, H, W};
+    UWIE_CHECK_WS(diff_u8_ws_bytes(s));
+    UWIE_SCOPE(ctx);  // every argument check above needs no device
+    return launch_diff_enhance_u8(d_in, s, d_params, flags, d_out_u8, d_out_f32, d_saved, d_workspace, (hipStream_t)stream);
+}
+
 int uwie_diff_gated_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, int planar,
                         const float *d_params, int flags, void *d_workspace, size_t workspace_bytes, void *stream)
 {

@@ -167,6 +167,38 @@ __device__ __forceinline__ float pow_f32_fast(float x, float g)
     return (float)v;
 }
 
+// vgg_16_UIE.DifferentiableEnhancement.forward per pixel (k_diffenh.hip's vgg_px), in two halves so that the float32
+// kernels and the byte-domain ones (k_diffenh_u8.hip, which tabulates the first half per byte value) share one source:
+//   vgg_stretch        clamp((x - p_low) / (p_high - p_low + 1e-8), 0, 1) of one channel value
+//   vgg_after_stretch  [UWIE_DIFF_OMEGA] dehaze with A = 0.6 -> [UWIE_DIFF_GAMMA] pow(v + 1e-8, gamma) -> clamp(0, 1), in place.
+//                      fmaxf(NaN, 0) = 0: the final clamp leaves no NaN behind
+__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
+__device__ __forceinline__ float vgg_stretch(float x, float lo, float rng) { return clamp01((x - lo) / rng); }
+__device__ __forceinline__ void vgg_after_stretch(float (&v)[3], float omega, float gamma, int flags)
+{
+    if (flags & 1) {
+        const float dark = fminf(fminf(v[0], v[1]), v[2]);
+        const float t = fminf(fmaxf(1.0f - omega * dark, 0.1f), 1.0f);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = clamp01((v[c] - 0.6f) / t + 0.6f);
+    }
+    if (flags & 2) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = pow_f32_fast(v[c] + 1e-8f, gamma);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = clamp01(v[c]);
+}
+
+// torch.sort position int((L / 100.0) * n) clamped to [0, n - 1] (vgg_16_UIE.py:78-82; k_sel_init_stretch_ranks)
+__device__ __forceinline__ long long stretch_rank(float L, int n)
+{
+    const double pos = ((double)L / 100.0) * (double)n;
+    if (!(pos > 0.0)) return 0;
+    if (pos >= (double)(n - 1)) return n - 1;
+    return (long long)pos;
+}
+
 // which channel color_correction attenuates for a cast kind (UWIE_CAST_*): greenish -> G, bluish -> B
 __device__ __forceinline__ bool px_atten(int kind, int c) { return kind != 0 && c == kind; }
 // (img * 255).astype(np.uint8): float32 product, truncation toward zero

@@ -26,28 +26,16 @@ namespace uwie {
 
 namespace {
 
-__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
-
 // The per-pixel forwards, shared by the inference kernels and the loss sweep (k_refloss_*): the clamp masks of the loss
 // backward recompute these values, so both must see the same bits.
-// vgg: v = clamp(stretch -> [dehaze] -> [gamma]) of one pixel's three channels (flags: UWIE_DIFF_OMEGA | UWIE_DIFF_GAMMA)
+// vgg: v = clamp(stretch -> [dehaze] -> [gamma]) of one pixel's three channels (flags: UWIE_DIFF_OMEGA | UWIE_DIFF_GAMMA);
+// the two halves are in devutil.h, where the byte-domain kernels (k_diffenh_u8.hip) take them from too
 __device__ __forceinline__ void vgg_px(const float (&x)[3], const float (&lo)[3], const float (&rng)[3], float omega, float gamma,
                                        int flags, float (&v)[3])
 {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = clamp01((x[c] - lo[c]) / rng[c]);
-    if (flags & 1) {
-        const float dark = fminf(fminf(v[0], v[1]), v[2]);
-        const float t = fminf(fmaxf(1.0f - omega * dark, 0.1f), 1.0f);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = clamp01((v[c] - 0.6f) / t + 0.6f);
-    }
-    if (flags & 2) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = pow_f32_fast(v[c] + 1e-8f, gamma);
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = clamp01(v[c]);
+    for (int c = 0; c < 3; ++c) v[c] = vgg_stretch(x[c], lo[c], rng[c]);
+    vgg_after_stretch(v, omega, gamma, flags);
 }
 
 // gated: one channel value; ok = false (no valid sorted position) gives NaN
@@ -122,15 +110,6 @@ __global__ void __launch_bounds__(256) k_diff_gated(const float *__restrict__ im
             out[i] = gated_px(img[i], lo[c], rng[c], u, e, om, ok);
         }
     }
-}
-
-// torch.sort position int((L / 100.0) * n) clamped to [0, n - 1] (vgg_16_UIE.py:78-82; k_sel_init_stretch_ranks)
-__device__ __forceinline__ long long stretch_rank(float L, int n)
-{
-    const double pos = ((double)L / 100.0) * (double)n;
-    if (!(pos > 0.0)) return 0;
-    if (pos >= (double)(n - 1)) return n - 1;
-    return (long long)pos;
 }
 
 // dL/d(out) of w1 * mean|out - ref| + w2 * mean((out - ref)^2) in torch's autograd order, given

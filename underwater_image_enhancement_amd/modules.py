@@ -318,6 +318,32 @@ class DifferentiableEnhancement(_EnhancementModule):
         out = dev.diff_enhance_f32(dev.tensor(x[None]), pt, planar=False)[0].cpu().numpy()
         return np.clip(out, 0.0, 1.0)
 
+    def enhance_u8(self, frames_u8, params, out: str = "u8"):
+        """The forward for uint8 frames in the byte domain (uwie_diff_enhance_u8): inference only, no
+        autograd.  ``frames_u8``: ``[H,W,3]`` / ``[B,H,W,3]`` uint8, NumPy (the result comes back as NumPy) or a torch tensor
+        (it stays on the device); the image is ``u8 / 255``.  ``params``: the module's dict, as for ``forward``.
+        ``out="float32"``: the module's output in the frames' layout, the bits ``forward`` gives for ``u8 / 255``;
+        ``out="u8"``: ``(np.clip(that, 0, 1) * 255).astype(np.uint8)``, use_trained_model.py:131."""
+        if out not in ("u8", "float32"):
+            raise ValueError(f"out is 'u8' or 'float32', got {out!r}")
+        dev = get_device(self.device)
+        was_numpy = not isinstance(frames_u8, torch.Tensor)
+        t = torch.from_numpy(np.ascontiguousarray(frames_u8)) if was_numpy else frames_u8
+        if t.dtype != torch.uint8:
+            raise TypeError(f"expected uint8 frames, got {t.dtype}")
+        single = t.dim() == 3
+        if single:
+            t = t.unsqueeze(0)
+        if t.dim() != 4 or t.shape[-1] != 3 or t.numel() == 0:
+            raise ValueError(f"expected non-empty [H,W,3] or [B,H,W,3] frames, got {tuple(frames_u8.shape)}")
+        t = t.to(dev.torch_device).contiguous()
+        pt, flags = _param_columns(dev, params, self._SPEC, t.shape[0], False)
+        o8, o32 = dev.diff_enhance_u8(t, pt, flags, want_u8=out == "u8", want_f32=out == "float32")
+        res = o8 if out == "u8" else o32
+        if single:
+            res = res[0]
+        return res.cpu().numpy() if was_numpy else res
+
 
 class GatedDifferentiableEnhancement(_EnhancementModule):
     """``deep_learning_parameters.DifferentiableEnhancement`` (deep_learning_parameters.py:24-90) on the device, forward and

@@ -287,6 +287,27 @@ class Device:
         return self._module_bwd(self.lib.uwie_diff_enhance_bwd_f32, self.lib.uwie_diff_enhance_bwd_workspace_bytes, img, params,
                                 saved, grad_out, planar, flags, want_img)
 
+    def diff_enhance_u8(self, u8, cols, flags: int = 3, want_u8: bool = True, want_f32: bool = False, saved: bool = False):
+        """The module in the byte domain (uwie_diff_enhance_u8).  u8: uint8 cuda tensor [B,H,W,3], the
+        frame whose float image is u8 / 255; cols: float32 [B,4] = L_low, L_high, omega, gamma.  Returns (out_u8 or None =
+        (uint8)(v * 255) of the module's output v, out_f32 or None = v, the bits diff_enhance_f32 gives for u8_to_f32(u8)),
+        and with ``saved`` a third item, float32 [B,3,2] as diff_enhance_save_f32 returns it."""
+        assert u8.dtype == torch.uint8
+        u8 = u8.contiguous()
+        B, H, W = self._bhw(u8)
+        assert cols.dtype == torch.float32 and tuple(cols.shape) == (B, 4)
+        cols = cols.contiguous()
+        n = self.lib.uwie_workspace_bytes_diff_u8(B, H, W)
+        if n == 0:
+            raise _lib.UwieError("batch/H/W out of range")
+        ws = self.workspace(n)
+        out_u8 = self.empty((B, H, W, 3), torch.uint8) if want_u8 else None
+        out_f32 = self.empty((B, H, W, 3), torch.float32) if want_f32 else None
+        sv = self.empty((B, 3, 2), torch.float32) if saved else None
+        check(self.lib.uwie_diff_enhance_u8(self._ctx, _ptr(u8), _ptr(out_u8), _ptr(out_f32), B, H, W, _ptr(cols), int(flags),
+                                            _ptr(sv), _ptr(ws), ws.numel(), self.stream()))
+        return (out_u8, out_f32, sv) if saved else (out_u8, out_f32)
+
     def diff_gated_f32(self, img, params, planar: bool):
         """deep_learning_parameters.DifferentiableEnhancement's forward (uwie_diff_gated_f32): img float32 cuda [B,3,H,W]
         (planar) or [B,H,W,3]; params float32 [B,4] = L_low, L_high, use_gamma, gamma.  An image without a valid sorted
