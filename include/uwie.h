@@ -330,6 +330,27 @@ int uwie_diff_gated_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_pa
                             void *d_workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * The gated module for u8 frames, in the byte domain (k_diffgated_u8.hip): the inference route of
+ * EndToEndTrainer's stack from a decoded frame to a u8 frame.  d_in: [batch][H][W][3] uint8, the frame whose float image is
+ * u8 / 255.  Nothing after the stretch mixes channels, so per image and channel the module is a function of the byte alone:
+ * count (256 bins per channel), one block per image that finds the two sorted positions (Python's indexing rules, as above)
+ * and tabulates the module for the 3 x 256 byte values, then a pure lookup over the frame's bytes.
+ *   d_out_u8  [batch][H][W][3] uint8   = (uint8)(v * 255.0f) of the module's output v
+ *   d_out_f32 [batch][H][W][3] float32 = v, the bits uwie_diff_gated_f32 gives for uwie_u8_to_f32 of the frame
+ *   Either may be NULL, not both (UWIE_E_INVALID).  d_saved (optional): as uwie_diff_gated_save_f32 leaves it.
+ * An image without a valid sorted position sets UWIE_STATUS_DIFF_RANK; its floats are NaN and its bytes 0, the other images
+ * of the batch are not affected.  d_params: [batch][4] float32 = {L_low, L_high, use_gamma, gamma}; flags: reserved, 0.
+ * d_in must be 4-byte aligned (UWIE_E_INVALID otherwise); the outputs need no alignment beyond their element types.  Every
+ * argument check runs before the context is touched.
+ * Workspace: uwie_workspace_bytes_diff_gated_u8(batch) = the histograms and the tables, 7 KB per image whatever H x W is
+ * (0: batch < 1).
+ */
+size_t uwie_workspace_bytes_diff_gated_u8(int batch);
+int uwie_diff_gated_u8(uwie_ctx *ctx, const uint8_t *d_in, uint8_t *d_out_u8, float *d_out_f32, int batch, int H, int W,
+                       const float *d_params /* [batch][4] L_low, L_high, use_gamma, gamma */, int flags /* 0 */,
+                       float *d_saved /* optional */, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
  * ReferenceLoss (deep_learning_parameters.py:170-196) and the L1 / MSE terms of CombinedLoss (vgg_16_UIE.py:272-303) on a
  * module's output o and a reference r (the contract: DESIGN.md section 13): d_loss [2] float32 = {l1, l2} =
  * {mean|o - r|, mean((o - r)^2)} over all N = batch * 3 * H * W values (torch's 'mean' reduction).  The float32 terms are
@@ -416,6 +437,28 @@ void uwie_param_net_destroy(uwie_param_net *net);
 size_t uwie_param_net_workspace_bytes(int batch, int H, int W);
 int uwie_param_net_f32(uwie_ctx *ctx, const uwie_param_net *net, const float *d_img, const float *d_features, int batch, int H, int W,
                        float *d_out, float *d_pooled, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * deep_learning_parameters.ParameterPredictor.forward in eval mode (deep_learning_parameters.py:97-163; DESIGN.md section
+ * 17), float32, no autograd: Linear(feature_dim, hidden) + ReLU -> num_blocks residual blocks relu(W2 relu(W1 x + b1) + b2 + x)
+ * -> Linear(hidden, hidden / 2) + ReLU -> four heads Linear(hidden / 2, 1) + sigmoid with the ranges of :158-161 (Dropout is
+ * the identity).  d_params: the state dict's tensors, float32 on the device, flat in state_dict() order:
+ *   input_proj.0.weight [hidden][feature_dim], .bias; res_blocks.N.block.0.weight [hidden][hidden], .bias, .block.3.weight,
+ *   .bias for N = 0 .. num_blocks - 1; output_proj.0.weight [hidden / 2][hidden], .bias; param_heads.K.weight [1][hidden / 2],
+ *   .bias for K = gamma, L_low, L_high, use_gamma.  d_params is not kept.
+ * hidden_dim even, 2 .. 1152; feature_dim 1 .. 1152; num_blocks 0 .. 64 (UWIE_E_INVALID otherwise).
+ * uwie_mlp_forward: d_features [batch][feature_dim], float64 (features_are_f64, what uwie_feature_extractor_u8 writes; each
+ * value is rounded to float32 as it is loaded, torch's .float()) or float32; d_out [batch][4] float32 = L_low, L_high,
+ * use_gamma, gamma: the gated module's d_params.  batch 1 .. 2^20.  Deterministic: one wave per neuron sums in a fixed order,
+ * so a row's result does not depend on the batch it is in.  Workspace: uwie_mlp_workspace_bytes(batch, hidden_dim) (0: out
+ * of range).
+ */
+typedef struct uwie_mlp uwie_mlp;
+int uwie_mlp_create(uwie_ctx *ctx, const float *d_params, int feature_dim, int hidden_dim, int num_blocks, uwie_mlp **out_net);
+void uwie_mlp_destroy(uwie_mlp *net);
+size_t uwie_mlp_workspace_bytes(int batch, int hidden_dim);
+int uwie_mlp_forward(uwie_ctx *ctx, const uwie_mlp *net, const void *d_features, int features_are_f64, int batch, float *d_out,
+                     void *d_workspace, size_t workspace_bytes, void *stream);
 
 /*
  * u8.astype(float32) / 255.0 of n bytes in any layout (each value (float)v / 255.0f, IEEE division): the float image of

@@ -114,6 +114,8 @@ SIGNATURES = {
     "uwie_diff_gated_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _SZ, _VP],
     "uwie_diff_gated_save_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _SZ, _VP],
     "uwie_diff_gated_bwd_workspace_bytes": [_I, _I, _I],
+    "uwie_workspace_bytes_diff_gated_u8": [_I],
+    "uwie_diff_gated_u8": [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _SZ, _VP],
     "uwie_diff_gated_bwd_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP],
     "uwie_ref_loss_workspace_bytes": [_I, _I, _I],
     "uwie_ref_loss_f32": [_VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP],
@@ -128,6 +130,10 @@ SIGNATURES = {
     "uwie_param_net_destroy": [_VP],
     "uwie_param_net_workspace_bytes": [_I, _I, _I],
     "uwie_param_net_f32": [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _SZ, _VP],
+    "uwie_mlp_create": [_VP, _VP, _I, _I, _I, ctypes.POINTER(_VP)],
+    "uwie_mlp_destroy": [_VP],
+    "uwie_mlp_workspace_bytes": [_I, _I],
+    "uwie_mlp_forward": [_VP, _VP, _VP, _I, _I, _VP, _VP, _SZ, _VP],
     "uwie_u8_to_f32": [_VP, _VP, _VP, _SZ, _VP],
     "uwie_extract_features_u8": [_VP, _VP, _VP, _I, _I, _I, _VP, _SZ, _VP],
     "uwie_feature_extractor_count": [_I, _I],
@@ -181,6 +187,9 @@ _RESTYPES = {
     "uwie_vgg_destroy": None,
     "uwie_param_net_workspace_bytes": ctypes.c_size_t,
     "uwie_param_net_destroy": None,
+    "uwie_workspace_bytes_diff_gated_u8": ctypes.c_size_t,
+    "uwie_mlp_workspace_bytes": ctypes.c_size_t,
+    "uwie_mlp_destroy": None,
 }
 
 _lib = None

@@ -776,38 +776,245 @@ class EnhancementPredictor:
         ``predict_parameters`` gives for it.  A frame that raises does not stop the others (:163-164): its output is ``None``
         and its ``params`` entry is the exception's message (prefixed with its file name when names are given).  Input
         errors are found per frame before any launch; an error of a group's device run fails that group's frames."""
-        frames = list(frames)
-        if filenames is not None and len(filenames) != len(frames):
-            raise ValueError(f"{len(filenames)} file names for {len(frames)} frames")
-        dev = get_device(self.device)
-        outputs, params = [None] * len(frames), [None] * len(frames)
+        return _process_frames(self, frames, filenames)
 
-        def fail(i, e):
-            outputs[i] = None
-            params[i] = f"{filenames[i]}: {e}" if filenames is not None else str(e)
 
-        groups = {}
-        for i, f in enumerate(frames):
-            try:
-                u8, single = self._frames(f, dev)
-                if not single:
-                    raise ValueError(f"process_frames takes HxWx3 frames, got {tuple(u8.shape)}")
-                groups.setdefault(tuple(u8.shape), []).append((i, u8))
-            except Exception as e:  # noqa: BLE001 - the reference's loop catches everything (:163)
+def _process_frames(predictor, frames, filenames):
+    """``process_frames`` of ``EnhancementPredictor`` and ``GatedEnhancementPredictor``: grouping by shape and keep-going.
+    ``predictor`` has ``device``, ``_frames(frame, dev)``, ``_batch_u8(dev, u8) -> (out_u8, params, raw)`` and
+    ``_param_dicts(raw on the host)``."""
+    frames = list(frames)
+    if filenames is not None and len(filenames) != len(frames):
+        raise ValueError(f"{len(filenames)} file names for {len(frames)} frames")
+    dev = get_device(predictor.device)
+    outputs, params = [None] * len(frames), [None] * len(frames)
+
+    def fail(i, e):
+        outputs[i] = None
+        params[i] = f"{filenames[i]}: {e}" if filenames is not None else str(e)
+
+    groups = {}
+    for i, f in enumerate(frames):
+        try:
+            u8, single = predictor._frames(f, dev)
+            if not single:
+                raise ValueError(f"process_frames takes HxWx3 frames, got {tuple(u8.shape)}")
+            groups.setdefault(tuple(u8.shape), []).append((i, u8))
+        except Exception as e:  # noqa: BLE001 - the reference's loop catches everything (:163)
+            fail(i, e)
+
+    for members in groups.values():
+        try:
+            out, _, raw = predictor._batch_u8(dev, torch.cat([u8 for _, u8 in members]))
+            out, raw = out.cpu().numpy(), raw.cpu().numpy()
+            dev.check_status()
+        except Exception as e:  # noqa: BLE001 - a device error: the whole group fails, nothing is launched again for it
+            for i, _ in members:
                 fail(i, e)
+            continue
+        for (i, _), o, d in zip(members, out, predictor._param_dicts(raw)):
+            outputs[i], params[i] = o, d
+    return outputs, params
 
-        for members in groups.values():
-            try:
-                out, _, raw = self._batch_u8(dev, torch.cat([u8 for _, u8 in members]))
-                out, raw = out.cpu().numpy(), raw.cpu().numpy()
-                dev.check_status()
-            except Exception as e:  # noqa: BLE001 - a device error: the whole group fails, nothing is launched again for it
-                for i, _ in members:
-                    fail(i, e)
-                continue
-            for (i, _), o, d in zip(members, out, self._param_dicts(raw)):
-                outputs[i], params[i] = o, d
-        return outputs, params
+
+# ------------------------------------------------------------------ ParameterPredictor / GatedEnhancementPredictor (N13)
+GATED_PARAM_KEYS = ("gamma", "L_low", "L_high", "use_gamma")  # param_heads order (deep_learning_parameters.py:142-147)
+
+
+def _predictor_state(state):
+    """(validated float32 CPU tensors in state_dict() order, feature_dim, hidden_dim, num_blocks) of a
+    ``deep_learning_parameters.ParameterPredictor``: ``state`` is its state dict, the module itself, a checkpoint dict with
+    the ``'param_predictor'`` key (``EndToEndTrainer.save_model``) or a path to either.  The sizes come from the tensors'
+    shapes; a missing key or a shape that does not fit raises ValueError naming the key."""
+    if isinstance(state, (str, os.PathLike)):
+        state = torch.load(state, map_location="cpu", weights_only=True)
+    if isinstance(state, torch.nn.Module):
+        state = state.state_dict()
+    if "param_predictor" in state:
+        state = state["param_predictor"]
+    name = "ParameterPredictor state"
+    first = "input_proj.0.weight"
+    if first not in state:
+        raise ValueError(f"{name}: missing key '{first}'")
+    w = torch.as_tensor(state[first])
+    if w.dim() != 2:
+        raise ValueError(f"{name}: '{first}' has shape {tuple(w.shape)}, expected (hidden_dim, feature_dim)")
+    h, f = int(w.shape[0]), int(w.shape[1])
+    if h % 2 or not (2 <= h <= 1152 and 1 <= f <= 1152):
+        raise ValueError(f"{name}: '{first}' has shape {tuple(w.shape)}: hidden_dim must be even and, like feature_dim, "
+                         "at most 1152")
+    nb = 0
+    while f"res_blocks.{nb}.block.0.weight" in state:
+        nb += 1
+    layout = [(first, (h, f)), ("input_proj.0.bias", (h,))]
+    for i in range(nb):
+        layout += [(f"res_blocks.{i}.block.0.weight", (h, h)), (f"res_blocks.{i}.block.0.bias", (h,)),
+                   (f"res_blocks.{i}.block.3.weight", (h, h)), (f"res_blocks.{i}.block.3.bias", (h,))]
+    layout += [("output_proj.0.weight", (h // 2, h)), ("output_proj.0.bias", (h // 2,))]
+    for k in GATED_PARAM_KEYS:
+        layout += [(f"param_heads.{k}.weight", (1, h // 2)), (f"param_heads.{k}.bias", (1,))]
+    out = {}
+    for key, shape in layout:
+        if key not in state:
+            raise ValueError(f"{name}: missing key '{key}'")
+        t = torch.as_tensor(state[key])
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: '{key}' has shape {tuple(t.shape)}, expected {shape}")
+        out[key] = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
+    return out, f, h, nb
+
+
+class ParameterPredictor:
+    """``deep_learning_parameters.ParameterPredictor`` (:114-163) in eval mode on the device (k_param_net.hip, DESIGN.md
+    section 17).  ``state``: a state dict, the ``nn.Module``, or a checkpoint dict / path with the ``'param_predictor'`` key
+    that ``EndToEndTrainer.save_model`` writes; ``feature_dim``, ``hidden_dim`` and ``num_blocks`` come from the tensors'
+    shapes (ValueError naming the key when they do not fit).  ``predictor(rows)``: ``rows`` ``[B, feature_dim]`` float32 or
+    float64 (NumPy or torch; float64 is rounded to float32, as ``torch.from_numpy(features).float()``), returns the
+    reference's dict of four ``(B, 1)`` float32 tensors on the device (``gamma``, ``L_low``, ``L_high``, ``use_gamma``).
+    Inference only.  The weights are a frozen copy, packed once per GPU; ``close()`` frees them."""
+
+    def __init__(self, state, device: int | None = None):
+        self._state, self.feature_dim, self.hidden_dim, self.num_blocks = _predictor_state(state)
+        self.device = device
+        self._handles = {}
+        if device is not None:
+            self._handle(get_device(device))
+
+    def close(self):
+        for index, h in list(self._handles.items()):
+            get_device(index).mlp_destroy(h)
+        self._handles.clear()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    def state_dict(self):
+        return dict(self._state)
+
+    def _handle(self, dev: Device):
+        if dev.index not in self._handles:
+            flat = torch.cat([t.reshape(-1) for t in self._state.values()])
+            self._handles[dev.index] = dev.mlp_create(flat, self.feature_dim, self.hidden_dim, self.num_blocks)
+        return self._handles[dev.index]
+
+    def columns(self, rows, dev: Device | None = None):
+        """float32 ``[B,4]`` on the device in the gated module's order (``GatedDifferentiableEnhancement.KEYS``)."""
+        dev = dev or get_device(self.device)
+        if not isinstance(rows, torch.Tensor):
+            rows = torch.from_numpy(np.ascontiguousarray(rows))
+        if rows.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"expected float32 or float64 feature rows, got {rows.dtype}")
+        if rows.dim() == 1:
+            rows = rows[None]
+        if rows.dim() != 2 or rows.shape[1] != self.feature_dim or rows.shape[0] == 0:
+            raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({'x'.join(str(v) for v in rows.shape)} and "
+                               f"{self.feature_dim}x{self.hidden_dim})")
+        return dev.mlp_forward(self._handle(dev), rows.detach().to(dev.torch_device), self.hidden_dim)
+
+    def forward(self, rows):
+        cols = self.columns(rows)
+        at = {k: i for i, k in enumerate(GatedDifferentiableEnhancement.KEYS)}
+        return {k: cols[:, at[k]:at[k] + 1] for k in GATED_PARAM_KEYS}
+
+    __call__ = forward
+
+
+class GatedEnhancementPredictor:
+    """The inference route of ``EndToEndTrainer``'s stack (deep_learning_parameters.py) on the device, the counterpart of
+    ``EnhancementPredictor``: ``FeatureExtractor`` rows -> ``ParameterPredictor`` -> the gated ``DifferentiableEnhancement``.
+    ``state`` as for ``ParameterPredictor`` (``feature_dim`` 79).  Frames are uint8 RGB, or float images equal to
+    ``u8 / 255`` (as ``EnhancementPredictor``); H and W even or 1 (an odd side has no DCT block: 74 features).
+
+    ``predict_parameters(frames)``: the network's dict of Python floats for one frame, of float64 arrays for a batch.
+    ``enhance_batch_u8(frames)``: ``(out_u8, params float32 [B,4] = L_low, L_high, use_gamma, gamma)`` on the device:
+    features, MLP and the byte-domain module (uwie_diff_gated_u8) with no host read between the stages.
+    ``enhance_batch(frames)``: the float32 route, ``u8_to_f32`` then ``GatedDifferentiableEnhancement.forward``, ``[B,H,W,3]``.
+    ``process_frames`` as ``EnhancementPredictor.process_frames``.  ``validate_batch`` is ``EndToEndTrainer.validate``'s
+    loop body."""
+
+    def __init__(self, state, device: int | None = None):
+        self.device = device
+        self.model = ParameterPredictor(state, device=device)
+        if self.model.feature_dim != 79:
+            raise ValueError(f"ParameterPredictor state: 'input_proj.0.weight' takes {self.model.feature_dim} features, "
+                             "FeatureExtractor gives 79")
+        self.enhancer = GatedDifferentiableEnhancement()
+        self.enhancer.device = device
+        self.criterion = ReferenceLoss(0.5, 0.5, device=device)
+
+    @staticmethod
+    def _frames(img, dev: Device):
+        return EnhancementPredictor._frames(img, dev)
+
+    def _cols(self, dev: Device, u8):
+        """The network's float32 [B,4] (gated order) for uint8 frames on the device."""
+        rows = dev.feature_extractor(u8)
+        if rows.shape[1] != 79:
+            raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({rows.shape[0]}x{rows.shape[1]} and "
+                               f"79x{self.model.hidden_dim}): a frame with an odd side has no DCT features")
+        return self.model.columns(rows, dev)
+
+    @staticmethod
+    def _dict(cols):
+        return {k: cols[:, i:i + 1] for i, k in enumerate(GatedDifferentiableEnhancement.KEYS)}
+
+    def predict_parameters(self, frames):
+        dev = get_device(self.device)
+        u8, single = self._frames(frames, dev)
+        raw = self._cols(dev, u8).double().cpu().numpy()
+        dev.check_status()
+        at = {k: i for i, k in enumerate(GatedDifferentiableEnhancement.KEYS)}
+        params = {k: raw[:, at[k]] for k in GATED_PARAM_KEYS}
+        return {k: float(v[0]) for k, v in params.items()} if single else params
+
+    def enhance_batch(self, frames):
+        dev = get_device(self.device)
+        u8, _ = self._frames(frames, dev)
+        cols = self._cols(dev, u8)
+        with torch.no_grad():
+            out = self.enhancer(dev.u8_to_f32(u8).permute(0, 3, 1, 2).contiguous(), self._dict(cols))
+        return out.permute(0, 2, 3, 1).contiguous()
+
+    def _batch_u8(self, dev: Device, u8):
+        cols = self._cols(dev, u8)
+        out, _ = dev.diff_gated_u8(u8, cols, want_u8=True, want_f32=False)
+        return out, cols, cols
+
+    def enhance_batch_u8(self, frames):
+        """``(out_u8 [B,H,W,3] uint8 on the device, params float32 [B,4] = L_low, L_high, use_gamma, gamma)``; ``out_u8``
+        equals ``(enhance_batch(frames) * 255).to(uint8)``.  No host read: ``Device.check_status`` reports an unindexable
+        sorted position (the network's ranges leave none)."""
+        dev = get_device(self.device)
+        u8, _ = self._frames(frames, dev)
+        out, cols, _ = self._batch_u8(dev, u8)
+        return out, cols
+
+    @staticmethod
+    def _param_dicts(raw):
+        at = {k: i for i, k in enumerate(GatedDifferentiableEnhancement.KEYS)}
+        return [{k: float(row[at[k]]) for k in GATED_PARAM_KEYS} for row in np.asarray(raw, dtype=np.float64)]
+
+    def process_frames(self, frames, filenames=None):
+        """``EnhancementPredictor.process_frames`` for this stack: ``(outputs, params)`` in input order, frames of equal
+        shape in one ``enhance_batch_u8`` call per shape, a failing frame does not stop the others."""
+        return _process_frames(self, frames, filenames)
+
+    def validate_batch(self, images, references, features=None):
+        """``EndToEndTrainer.validate``'s loop body (:316-329) for one batch: ``images`` / ``references`` float32
+        ``(B,3,H,W)``, ``features`` ``(B,79)`` (None: ``FeatureExtractor``'s rows of the images).  Returns
+        ``(loss, {'l1', 'l2'})`` from ``ReferenceLoss(0.5, 0.5).through(GatedDifferentiableEnhancement(), ...)`` under
+        ``no_grad``, with one host read."""
+        dev = get_device(self.device)
+        x = images.to(dev.torch_device) if isinstance(images, torch.Tensor) else dev.tensor(np.asarray(images))
+        with torch.no_grad():
+            if features is None:
+                nhwc = x.permute(0, 2, 3, 1).contiguous()
+                features = dev.feature_extractor((nhwc * 255).to(torch.uint8), nhwc)
+            cols = self.model.columns(features, dev)
+            return self.criterion.through(self.enhancer, x, self._dict(cols), references)
 
 
 QUALITY_KEYS = ("contrast", "sharpness", "entropy", "saturation", "brightness", "edge_density", "colorfulness", "naturalness")

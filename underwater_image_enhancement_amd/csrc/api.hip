@@ -1172,6 +1172,27 @@ int uwie_diff_enhance_u8(uwie_ctx *ctx, const uint8_t *d_in, uint8_t *d_out_u8, 
     return launch_diff_enhance_u8(d_in, s, d_params, flags, d_out_u8, d_out_f32, d_saved, d_workspace, (hipStream_t)stream);
 }
 
+size_t uwie_workspace_bytes_diff_gated_u8(int batch)
+{
+    if (batch < 1) return 0;
+    return diff_gated_u8_ws_bytes(batch);
+}
+
+int uwie_diff_gated_u8(uwie_ctx *ctx, const uint8_t *d_in, uint8_t *d_out_u8, float *d_out_f32, int batch, int H, int W,
+                       const float *d_params, int flags, float *d_saved, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE(ctx && d_in && d_params, "diff_gated_u8: NULL pointer");
+    UWIE_REQUIRE(d_out_u8 || d_out_f32, "diff_gated_u8: at least one of d_out_u8, d_out_f32");
+    UWIE_REQUIRE(((uintptr_t)d_in & 3) == 0, "diff_gated_u8: d_in must be 4-byte aligned");  // k_frame_hist reads dwords
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_REQUIRE(batch <= 65535, "diff_gated_u8: batch is at most 65535");  // one grid row per image
+    UWIE_REQUIRE(flags == 0, "diff_gated_u8: flags are reserved (0)");
+    UWIE_CHECK_WS(diff_gated_u8_ws_bytes(batch));
+    UWIE_SCOPE(ctx);  // every argument check above needs no device
+    return launch_diff_gated_u8(d_in, Shape{batch, H, W}, d_params, ctx->d_status, d_out_u8, d_out_f32, d_saved, d_workspace,
+                                (hipStream_t)stream);
+}
+
 int uwie_diff_gated_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, int planar,
                         const float *d_params, int flags, void *d_workspace, size_t workspace_bytes, void *stream)
 {
@@ -1445,6 +1466,68 @@ int uwie_param_net_f32(uwie_ctx *ctx, const uwie_param_net *net, const float *d_
     UWIE_CHECK_WS(param_net_ws_bytes(s));
     UWIE_SCOPE(ctx);
     return launch_param_net(net->net, d_img, d_features, s, d_out, d_pooled, d_workspace, (hipStream_t)stream);
+}
+
+// ParameterPredictor (k_param_net.hip)
+struct uwie_mlp {
+    int device;
+    Mlp net;  // device pointers into blob
+    void *blob;
+};
+
+static bool mlp_dims_ok(int F, int Hd, int nb)
+{
+    return F >= 1 && F <= 1152 && Hd >= 2 && Hd <= 1152 && Hd % 2 == 0 && nb >= 0 && nb <= 64;
+}
+
+int uwie_mlp_create(uwie_ctx *ctx, const float *d_params, int feature_dim, int hidden_dim, int num_blocks, uwie_mlp **out_net)
+{
+    UWIE_REQUIRE(ctx && d_params && out_net, "mlp_create: NULL pointer");
+    *out_net = nullptr;
+    UWIE_REQUIRE(mlp_dims_ok(feature_dim, hidden_dim, num_blocks),
+                 "mlp_create: feature_dim 1 .. 1152, hidden_dim even 2 .. 1152, num_blocks 0 .. 64");
+    UWIE_SCOPE(ctx);
+    void *blob = nullptr;
+    UWIE_HIP_CHECK(hipMalloc(&blob, mlp_count(feature_dim, hidden_dim, num_blocks) * sizeof(float)));
+    Mlp net{};
+    const int rc = mlp_pack(d_params, feature_dim, hidden_dim, num_blocks, static_cast<float *>(blob), &net, nullptr);
+    const hipError_t e = rc == UWIE_OK ? hipStreamSynchronize(nullptr) : hipSuccess;
+    if (rc != UWIE_OK || e != hipSuccess) {
+        (void)hipFree(blob);
+        if (e != hipSuccess) set_error("mlp_create: packing failed: %s", hipGetErrorString(e));
+        return rc != UWIE_OK ? rc : UWIE_E_HIP;
+    }
+    *out_net = new uwie_mlp{ctx->device, net, blob};
+    return UWIE_OK;
+}
+
+void uwie_mlp_destroy(uwie_mlp *net)
+{
+    if (!net) return;
+    int prev = -1;
+    const bool switch_dev = hipGetDevice(&prev) == hipSuccess && prev != net->device && hipSetDevice(net->device) == hipSuccess;
+    (void)hipFree(net->blob);
+    if (switch_dev) (void)hipSetDevice(prev);
+    delete net;
+}
+
+size_t uwie_mlp_workspace_bytes(int batch, int hidden_dim)
+{
+    if (batch < 1 || batch > (1 << 20) || !mlp_dims_ok(1, hidden_dim, 0)) return 0;
+    return mlp_ws_bytes(batch, hidden_dim);
+}
+
+int uwie_mlp_forward(uwie_ctx *ctx, const uwie_mlp *net, const void *d_features, int features_are_f64, int batch, float *d_out,
+                     void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE(ctx && net && d_features && d_out, "mlp_forward: NULL pointer");
+    UWIE_REQUIRE(net->device == ctx->device, "mlp_forward: the network lives on another device");
+    UWIE_REQUIRE(batch >= 1 && batch <= (1 << 20), "mlp_forward: batch out of range (1 .. 2^20)");
+    UWIE_REQUIRE(((uintptr_t)d_features & (features_are_f64 ? 7 : 3)) == 0 && ((uintptr_t)d_out & 3) == 0,
+                 "mlp_forward: d_features and d_out must be aligned for their element types");
+    UWIE_CHECK_WS(mlp_ws_bytes(batch, net->net.H));
+    UWIE_SCOPE(ctx);
+    return launch_mlp(net->net, d_features, features_are_f64 != 0, batch, d_out, d_workspace, (hipStream_t)stream);
 }
 
 int uwie_u8_to_f32(uwie_ctx *ctx, const uint8_t *d_in, float *d_out, size_t n, void *stream)

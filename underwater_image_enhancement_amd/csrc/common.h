@@ -422,6 +422,11 @@ int launch_diff_enhance(const float *d_img, int planar, Shape s, const float *d_
 size_t diff_u8_ws_bytes(Shape s);
 int launch_diff_enhance_u8(const uint8_t *d_in, Shape s, const float *d_params, int flags, uint8_t *d_out_u8, float *d_out_f32,
                            float *d_saved, void *ws, hipStream_t st);
+// k_diffgated_u8.hip: the gated module for u8 frames in the byte domain: per image a 3 x 256 table.
+// d_out_u8 / d_out_f32 / d_saved optional (at least one output), ws: diff_gated_u8_ws_bytes (independent of H x W)
+size_t diff_gated_u8_ws_bytes(int B);
+int launch_diff_gated_u8(const uint8_t *d_in, Shape s, const float *d_params, uint32_t *d_status, uint8_t *d_out_u8,
+                         float *d_out_f32, float *d_saved, void *ws, hipStream_t st);
 // k_diffenh.hip: deep_learning_parameters.DifferentiableEnhancement.forward (:32-55), the gated gamma module
 // (params [B][4] = L_low, L_high, use_gamma, gamma; images without a valid sorted position get NaN)
 int launch_diff_gated(const float *d_img, int planar, Shape s, const float *d_params, const float *d_os, float *d_out,
@@ -480,6 +485,17 @@ size_t param_net_ws_bytes(Shape s);
 int launch_param_net(const ParamNet &net, const float *img, const float *feat, Shape s, float *out, float *pooled, void *ws,
                      hipStream_t st);
 int launch_u8_to_f32(const uint8_t *d_in, size_t n, float *d_out, hipStream_t st);
+// k_param_net.hip: deep_learning_parameters.ParameterPredictor in eval mode
+struct Mlp {
+    int F, H, nb;            // feature_dim, hidden_dim, num_blocks
+    const float *base;       // input_proj.0 ... output_proj.0 in state_dict() order
+    const float *hw, *hb;    // the four heads as one layer, [4][H / 2] and [4], in the gated order
+};
+size_t mlp_count(int F, int H, int nb);
+int mlp_pack(const float *d_params, int F, int H, int nb, float *blob, Mlp *net, hipStream_t st);
+size_t mlp_ws_bytes(int B, int hidden);
+// feat: [B][F] float32, or float64 (f64) rounded to float32 on load; out: [B][4] = L_low, L_high, use_gamma, gamma
+int launch_mlp(const Mlp &net, const void *feat, bool f64, int B, float *out, void *ws, hipStream_t st);
 
 // k_fused.hip: the fused tail of the dehazing strategies
 // what the restored image (six_stadigy.py:183-188) is made of; consumers may recompute it from here (restore.h)

@@ -190,6 +190,17 @@ __device__ __forceinline__ void vgg_after_stretch(float (&v)[3], float omega, fl
     for (int c = 0; c < 3; ++c) v[c] = clamp01(v[c]);
 }
 
+// deep_learning_parameters.DifferentiableEnhancement.forward (:44-54) for one channel value, the source of k_diff_gated, the
+// fused loss sweeps (k_diffenh.hip) and the byte-domain table (k_diffgated_u8.hip): s = clamp((x - p_low) / rng, 0, 1) with
+// rng = p_high - p_low + 1e-8, z = pow(s + 1e-8, e) with e = 1.0f / gamma, clamp(u * z + om * s, 0, 1) with om = 1 - u.
+// ok = false (no valid sorted position) gives NaN.
+__device__ __forceinline__ float gated_px(float x, float lo, float rng, float u, float e, float om, bool ok)
+{
+    const float sv = clamp01((x - lo) / rng);
+    const float z = pow_f32_fast(sv + 1e-8f, e);
+    return ok ? clamp01(u * z + om * sv) : __builtin_nanf("");
+}
+
 // torch.sort position int((L / 100.0) * n) clamped to [0, n - 1] (vgg_16_UIE.py:78-82; k_sel_init_stretch_ranks)
 __device__ __forceinline__ long long stretch_rank(float L, int n)
 {

@@ -38,13 +38,7 @@ __device__ __forceinline__ void vgg_px(const float (&x)[3], const float (&lo)[3]
     vgg_after_stretch(v, omega, gamma, flags);
 }
 
-// gated: one channel value; ok = false (no valid sorted position) gives NaN
-__device__ __forceinline__ float gated_px(float x, float lo, float rng, float u, float e, float om, bool ok)
-{
-    const float sv = clamp01((x - lo) / rng);
-    const float z = pow_f32_fast(sv + 1e-8f, e);
-    return ok ? clamp01(u * z + om * sv) : __builtin_nanf("");
-}
+// gated: gated_px (devutil.h), one channel value; the byte-domain table (k_diffgated_u8.hip) compiles the same source
 
 // planar: img/out [B][3][n];  interleaved: [B][n][3].  os: [B*3][kSelOsStride] floats, entries 0/1 = p_low, p_high.
 __global__ void __launch_bounds__(256) k_diff_enhance(const float *__restrict__ img, int planar, int n,

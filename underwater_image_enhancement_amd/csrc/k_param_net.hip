@@ -13,7 +13,13 @@
 //                                   LIN_RELU     ReLU
 //                                   LIN_ATTN     fused * sigmoid(x): the attention product
 //                                   LIN_RANGE    sigmoid(x) * (max - min) + min with the head's param_ranges
+//                                   LIN_RES_RELU   relu(x + aux): a residual block's second layer (ParameterPredictor)
+//                                   LIN_GATED_RANGE  sigmoid(x) * scale + min with ParameterPredictor's ranges, gated order
+//                                   X64: the input rows are float64 and are rounded to float32 as they are staged
 //   k_pn_u8_to_f32                  EnhancementPredictor's float image u8 / 255, in the frames' own layout
+//
+// deep_learning_parameters.ParameterPredictor.forward in eval mode (:97-163) is five kinds of launch of
+// the same kernel (launch_mlp): input_proj, per residual block two layers, output_proj, and the four heads as one N = 4 layer.
 #include "common.h"
 
 namespace uwie {
@@ -22,19 +28,23 @@ namespace {
 
 constexpr int kKR = 18;  // weight registers per lane: K <= 64 * 18 = 1152
 constexpr int kFeat = 79, kHalf = 512, kPooled = 1024, kHid = 256, kHead = 128;
-enum { LIN_BN_RELU = 0, LIN_RELU = 1, LIN_ATTN = 2, LIN_RANGE = 3 };
+enum { LIN_BN_RELU = 0, LIN_RELU = 1, LIN_ATTN = 2, LIN_RANGE = 3, LIN_RES_RELU = 4, LIN_GATED_RANGE = 5 };
 
 // param_ranges (vgg_16_UIE.py:193-198) in ModuleDict order: omega, gamma, L_low, L_high.  torch multiplies the float32
 // sigmoid by the Python float (max - min) and adds min, each operand rounded to float32 first.
 __constant__ float kRangeScale[4] = {(float)(0.9 - 0.3), (float)(1.5 - 1.0), (float)(15.0 - 2.0), (float)(95.0 - 60.0)};
 __constant__ float kRangeMin[4] = {0.3f, 1.0f, 2.0f, 60.0f};
+// ParameterPredictor's ranges (deep_learning_parameters.py:158-161) in the gated module's column order: L_low, L_high,
+// use_gamma, gamma.  sigmoid * 15 + 5, sigmoid * 13 + 85, sigmoid, sigmoid * 0.5 + 1.0: the Python numbers as float32.
+__constant__ float kGatedScale[4] = {15.0f, 13.0f, 1.0f, 0.5f};
+__constant__ float kGatedMin[4] = {5.0f, 85.0f, 0.0f, 1.0f};
 
 struct LinArgs {
-    const float *x;    // [B][ldx]
+    const float *x;    // [B][ldx] (X64: float64 values)
     const float *w;    // [N][K]
     const float *b;    // [N]
     const float *bn;   // LIN_BN_RELU: [4][N] = weight, bias, running_mean, running_var
-    const float *aux;  // LIN_ATTN: the fused vector [B][N]
+    const float *aux;  // LIN_ATTN: the fused vector [B][N]; LIN_RES_RELU: the block's input [B][N]
     float *y;          // [B][N]
     int B, K, N, ldx;
     int xstep;         // input offset per output neuron (the heads' last layers read their own 128 hidden values)
@@ -46,7 +56,7 @@ __device__ __forceinline__ float sigmoid_f(float v) { return 1.0f / (1.0f + expf
 
 constexpr int kLdsRows = 8192;  // floats of batch rows staged in LDS per pass (32 KB)
 
-template <int EPI>
+template <int EPI, bool X64 = false>
 __global__ void __launch_bounds__(256) k_pn_linear(LinArgs a)
 {
     __shared__ float xs[kLdsRows];
@@ -70,7 +80,9 @@ __global__ void __launch_bounds__(256) k_pn_linear(LinArgs a)
         __syncthreads();  // the previous pass's rows are consumed
         for (int i = threadIdx.x; i < nr * span; i += 256) {
             const int r = i / span;
-            xs[i] = xg[(size_t)(b0 + r) * a.ldx + (i - r * span)];
+            const size_t at = (size_t)(b0 + r) * a.ldx + (i - r * span);
+            if constexpr (X64) xs[i] = (float)(reinterpret_cast<const double *>(a.x) + (size_t)n0 * a.xstep)[at];
+            else xs[i] = xg[at];
         }
         __syncthreads();
         if (!live) continue;
@@ -94,6 +106,11 @@ __global__ void __launch_bounds__(256) k_pn_linear(LinArgs a)
                 v = relu_f(v);
             } else if constexpr (EPI == LIN_ATTN) {
                 v = a.aux[(size_t)b * a.N + n] * sigmoid_f(v);
+            } else if constexpr (EPI == LIN_RES_RELU) {
+                v = relu_f(v + a.aux[(size_t)b * a.N + n]);
+            } else if constexpr (EPI == LIN_GATED_RANGE) {
+                v = sigmoid_f(v);
+                if (n != 2) v = v * kGatedScale[n] + kGatedMin[n];  // use_gamma is the sigmoid itself
             } else {
                 v = sigmoid_f(v) * kRangeScale[n] + kRangeMin[n];
             }
@@ -166,7 +183,7 @@ PnBufs carve_pn(Shape s, void *ws, size_t *total = nullptr)
     return A;
 }
 
-template <int EPI>
+template <int EPI, bool X64 = false>
 int linear(const char *name, const float *x, int ldx, int xstep, const float *w, const float *b, const float *bn, const float *aux,
            float *y, int B, int K, int N, hipStream_t st)
 {
@@ -176,7 +193,7 @@ int linear(const char *name, const float *x, int ldx, int xstep, const float *w,
     }
     LinArgs a{x, w, b, bn, aux, y, B, K, N, ldx, xstep};
     UWIE_PROF(name, st);
-    hipLaunchKernelGGL(k_pn_linear<EPI>, dim3(cdiv(N, 4)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((k_pn_linear<EPI, X64>), dim3(cdiv(N, 4)), dim3(256), 0, st, a);
     UWIE_LAUNCH_CHECK();
     return UWIE_OK;
 }
@@ -309,6 +326,79 @@ int launch_param_net(const ParamNet &net, const float *img, const float *feat, S
     PN_TRY(linear<LIN_ATTN>("pn attention.2", A.a1, kHid / 4, 0, net.lw[3], net.lb[3], nullptr, A.h2, A.fused, B, kHid / 4, kHid, st));
     PN_TRY(linear<LIN_RELU>("pn heads.0", A.fused, kHid, 0, net.lw[4], net.lb[4], nullptr, nullptr, A.hh, B, kHid, 4 * kHead, st));
     PN_TRY(linear<LIN_RANGE>("pn heads.3", A.hh, 4 * kHead, kHead, net.lw[5], net.lb[5], nullptr, nullptr, out, B, kHead, 4, st));
+    return UWIE_OK;
+}
+
+// ---------------------------------------------------------------- ParameterPredictor
+namespace {
+
+struct MlpBufs {
+    float *X, *T, *Y, *half;
+};
+MlpBufs carve_mlp(int B, int hidden, void *ws, size_t *total = nullptr)
+{
+    Carver c(ws);
+    MlpBufs A;
+    A.X = c.take<float>((size_t)B * hidden);
+    A.T = c.take<float>((size_t)B * hidden);
+    A.Y = c.take<float>((size_t)B * hidden);
+    A.half = c.take<float>((size_t)B * (hidden / 2));
+    if (total) *total = c.total();
+    return A;
+}
+
+}  // namespace
+
+size_t mlp_count(int F, int Hd, int nb)
+{
+    const size_t h = (size_t)Hd, half = h / 2;
+    return (size_t)F * h + h + (size_t)nb * 2 * (h * h + h) + half * h + half + 4 * (half + 1);
+}
+
+// blob = d_params as it is (state_dict() order) up to output_proj; the four heads (state order gamma, L_low, L_high,
+// use_gamma, each a weight row and a bias) gathered as one [4][hidden / 2] layer in the gated order
+int mlp_pack(const float *d_params, int F, int Hd, int nb, float *blob, Mlp *net, hipStream_t st)
+{
+    const size_t h = (size_t)Hd, half = h / 2, body = mlp_count(F, Hd, nb) - 4 * (half + 1);
+    UWIE_HIP_CHECK(hipMemcpyAsync(blob, d_params, body * sizeof(float), hipMemcpyDeviceToDevice, st));
+    float *hw = blob + body, *hb = hw + 4 * half;
+    const int from_state[4] = {1, 2, 3, 0};  // L_low, L_high, use_gamma, gamma
+    for (int j = 0; j < 4; ++j) {
+        const float *src = d_params + body + (size_t)from_state[j] * (half + 1);
+        UWIE_HIP_CHECK(hipMemcpyAsync(hw + (size_t)j * half, src, half * sizeof(float), hipMemcpyDeviceToDevice, st));
+        UWIE_HIP_CHECK(hipMemcpyAsync(hb + j, src + half, sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    net->F = F, net->H = Hd, net->nb = nb;
+    net->base = blob;
+    net->hw = hw, net->hb = hb;
+    return UWIE_OK;
+}
+
+size_t mlp_ws_bytes(int B, int hidden)
+{
+    size_t n = 0;
+    (void)carve_mlp(B, hidden, nullptr, &n);
+    return n;
+}
+
+int launch_mlp(const Mlp &net, const void *feat, bool f64, int B, float *out, void *ws, hipStream_t st)
+{
+    MlpBufs A = carve_mlp(B, net.H, ws);
+    const int F = net.F, Hd = net.H, half = Hd / 2;
+    const float *p = net.base;
+    const float *w = p, *b = p + (size_t)Hd * F;
+    p = b + Hd;
+    if (f64) PN_TRY((linear<LIN_RELU, true>("mlp input_proj", static_cast<const float *>(feat), F, 0, w, b, nullptr, nullptr, A.X, B, F, Hd, st)));
+    else PN_TRY(linear<LIN_RELU>("mlp input_proj", static_cast<const float *>(feat), F, 0, w, b, nullptr, nullptr, A.X, B, F, Hd, st));
+    for (int k = 0; k < net.nb; ++k) {
+        const float *w1 = p, *b1 = w1 + (size_t)Hd * Hd, *w2 = b1 + Hd, *b2 = w2 + (size_t)Hd * Hd;
+        p = b2 + Hd;
+        PN_TRY(linear<LIN_RELU>("mlp block.0", A.X, Hd, 0, w1, b1, nullptr, nullptr, A.T, B, Hd, Hd, st));
+        PN_TRY(linear<LIN_RES_RELU>("mlp block.3", A.T, Hd, 0, w2, b2, nullptr, A.X, A.Y, B, Hd, Hd, st));
+        std::swap(A.X, A.Y);
+    }
+    PN_TRY(linear<LIN_RELU>("mlp output_proj", A.X, Hd, 0, p, p + (size_t)half * Hd, nullptr, nullptr, A.half, B, Hd, half, st));
+    PN_TRY(linear<LIN_GATED_RANGE>("mlp heads", A.half, half, 0, net.hw, net.hb, nullptr, nullptr, out, B, half, 4, st));
     return UWIE_OK;
 }
 

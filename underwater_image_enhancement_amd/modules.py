@@ -236,6 +236,29 @@ class GatedDiffEnhanceLossFunction(_ModuleLossFunction):
         return GatedDiffEnhanceLossFunction._grad(ctx, grads)
 
 
+def _frames_u8(module, frames_u8, out: str):
+    """The common front of the modules' ``enhance_u8``: (dev, uint8 [B,H,W,3] on it, was_numpy, single)."""
+    if out not in ("u8", "float32"):
+        raise ValueError(f"out is 'u8' or 'float32', got {out!r}")
+    dev = get_device(module.device)
+    was_numpy = not isinstance(frames_u8, torch.Tensor)
+    t = torch.from_numpy(np.ascontiguousarray(frames_u8)) if was_numpy else frames_u8
+    if t.dtype != torch.uint8:
+        raise TypeError(f"expected uint8 frames, got {t.dtype}")
+    single = t.dim() == 3
+    if single:
+        t = t.unsqueeze(0)
+    if t.dim() != 4 or t.shape[-1] != 3 or t.numel() == 0:
+        raise ValueError(f"expected non-empty [H,W,3] or [B,H,W,3] frames, got {tuple(frames_u8.shape)}")
+    return dev, t.to(dev.torch_device).contiguous(), was_numpy, single
+
+
+def _finish_u8(res, was_numpy, single):
+    if single:
+        res = res[0]
+    return res.cpu().numpy() if was_numpy else res
+
+
 # ------------------------------------------------------------------ the two modules
 class _EnhancementModule:
     """What the two modules share.  A subclass states ``_SPEC`` (its keys in the device's column order, each with its
@@ -324,25 +347,10 @@ class DifferentiableEnhancement(_EnhancementModule):
         (it stays on the device); the image is ``u8 / 255``.  ``params``: the module's dict, as for ``forward``.
         ``out="float32"``: the module's output in the frames' layout, the bits ``forward`` gives for ``u8 / 255``;
         ``out="u8"``: ``(np.clip(that, 0, 1) * 255).astype(np.uint8)``, use_trained_model.py:131."""
-        if out not in ("u8", "float32"):
-            raise ValueError(f"out is 'u8' or 'float32', got {out!r}")
-        dev = get_device(self.device)
-        was_numpy = not isinstance(frames_u8, torch.Tensor)
-        t = torch.from_numpy(np.ascontiguousarray(frames_u8)) if was_numpy else frames_u8
-        if t.dtype != torch.uint8:
-            raise TypeError(f"expected uint8 frames, got {t.dtype}")
-        single = t.dim() == 3
-        if single:
-            t = t.unsqueeze(0)
-        if t.dim() != 4 or t.shape[-1] != 3 or t.numel() == 0:
-            raise ValueError(f"expected non-empty [H,W,3] or [B,H,W,3] frames, got {tuple(frames_u8.shape)}")
-        t = t.to(dev.torch_device).contiguous()
+        dev, t, was_numpy, single = _frames_u8(self, frames_u8, out)
         pt, flags = _param_columns(dev, params, self._SPEC, t.shape[0], False)
         o8, o32 = dev.diff_enhance_u8(t, pt, flags, want_u8=out == "u8", want_f32=out == "float32")
-        res = o8 if out == "u8" else o32
-        if single:
-            res = res[0]
-        return res.cpu().numpy() if was_numpy else res
+        return _finish_u8(o8 if out == "u8" else o32, was_numpy, single)
 
 
 class GatedDifferentiableEnhancement(_EnhancementModule):
@@ -379,6 +387,22 @@ class GatedDifferentiableEnhancement(_EnhancementModule):
         if grad:
             return self._FUNCTION.apply(x, pt, True, dev)
         return dev.diff_gated_f32(x, pt, planar=True)
+
+    def enhance_u8(self, frames_u8, params, out: str = "u8"):
+        """The forward for uint8 frames in the byte domain (uwie_diff_gated_u8): inference only, no
+        autograd.  Arguments and results as ``DifferentiableEnhancement.enhance_u8``; ``params`` needs all four keys.  Per
+        image the module is a 3 x 256 table of the byte, so ``out="float32"`` gives the bits ``forward`` gives for
+        ``u8 / 255`` and ``out="u8"`` their ``(x * 255).astype(np.uint8)``.  One wait per call; an unindexable sorted position
+        raises what ``forward`` raises."""
+        for k in self.KEYS:
+            params[k]
+        dev, t, was_numpy, single = _frames_u8(self, frames_u8, out)
+        pt, _ = _param_columns(dev, params, self._SPEC, t.shape[0], False)
+        o8, o32 = dev.diff_gated_u8(t, pt, want_u8=out == "u8", want_f32=out == "float32")
+        if self._POLLS_RANK and dev.check_status(allow=_lib.STATUS_DIFF_RANK) & _lib.STATUS_DIFF_RANK:
+            _raise_rank_error(pt[:, :2].cpu().numpy(), t.shape[1] * t.shape[2])
+            raise _lib.UwieError("diff_gated_u8: the device flagged a sorted position that the host finds valid")
+        return _finish_u8(o8 if out == "u8" else o32, was_numpy, single)
 
 
 # ------------------------------------------------------------------ ReferenceLoss (deep_learning_parameters.py:170-196, N9)

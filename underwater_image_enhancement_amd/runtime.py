@@ -324,6 +324,28 @@ class Device:
         return self._module_bwd(self.lib.uwie_diff_gated_bwd_f32, self.lib.uwie_diff_gated_bwd_workspace_bytes, img, params,
                                 saved, grad_out, planar, 0, want_img)
 
+    def diff_gated_u8(self, u8, cols, want_u8: bool = True, want_f32: bool = False, saved: bool = False):
+        """The gated module in the byte domain (uwie_diff_gated_u8).  u8: uint8 cuda tensor [B,H,W,3], the
+        frame whose float image is u8 / 255; cols: float32 [B,4] = L_low, L_high, use_gamma, gamma.  Returns (out_u8 or None =
+        (uint8)(v * 255) of the module's output v, out_f32 or None = v, the bits diff_gated_f32 gives for u8_to_f32(u8)), and
+        with ``saved`` a third item, float32 [B,3,2] as diff_gated_save_f32 returns it.  An image without a valid sorted
+        position gets NaN / 0 and sets UWIE_STATUS_DIFF_RANK (check_status)."""
+        assert u8.dtype == torch.uint8
+        u8 = u8.contiguous()
+        B, H, W = self._bhw(u8)
+        assert cols.dtype == torch.float32 and tuple(cols.shape) == (B, 4)
+        cols = cols.contiguous()
+        n = self.lib.uwie_workspace_bytes_diff_gated_u8(B)
+        if n == 0:
+            raise _lib.UwieError("batch out of range")
+        ws = self.workspace(n)
+        out_u8 = self.empty((B, H, W, 3), torch.uint8) if want_u8 else None
+        out_f32 = self.empty((B, H, W, 3), torch.float32) if want_f32 else None
+        sv = self.empty((B, 3, 2), torch.float32) if saved else None
+        check(self.lib.uwie_diff_gated_u8(self._ctx, _ptr(u8), _ptr(out_u8), _ptr(out_f32), B, H, W, _ptr(cols), 0, _ptr(sv),
+                                          _ptr(ws), ws.numel(), self.stream()))
+        return (out_u8, out_f32, sv) if saved else (out_u8, out_f32)
+
     # ------------------------------------------------------------------ ReferenceLoss (uwie_ref_loss_*, DESIGN.md section 13)
     def ref_loss_f32(self, map_: int, img, params, ref, planar: bool, flags: int = 0, want_out: bool = False,
                      status: bool = False):
@@ -432,6 +454,37 @@ class Device:
         check(self.lib.uwie_param_net_f32(self._ctx, net, _ptr(img.contiguous()), _ptr(features), B, H, W, _ptr(out), _ptr(pooled),
                                           _ptr(ws), ws.numel(), self.stream()))
         return out, pooled
+
+    # ------------------------------------------------------------------ ParameterPredictor (uwie_mlp_*)
+    def mlp_create(self, params, feature_dim: int, hidden_dim: int, num_blocks: int):
+        """A uwie_mlp handle from the state dict's tensors flattened in state_dict() order (float32; include/uwie.h lists
+        the order).  The caller owns it (mlp_destroy)."""
+        flat = params.to(device=self.torch_device, dtype=torch.float32).contiguous()
+        h, half = int(hidden_dim), int(hidden_dim) // 2
+        assert flat.numel() == int(feature_dim) * h + h + int(num_blocks) * 2 * (h * h + h) + half * h + half + 4 * (half + 1)
+        torch.cuda.synchronize(self.index)  # the packing runs on the null stream
+        handle = ctypes.c_void_p()
+        check(self.lib.uwie_mlp_create(self._ctx, _ptr(flat), int(feature_dim), h, int(num_blocks), ctypes.byref(handle)))
+        return handle
+
+    def mlp_destroy(self, handle):
+        torch.cuda.synchronize(self.index)
+        self.lib.uwie_mlp_destroy(handle)
+
+    def mlp_forward(self, net, rows, hidden_dim: int):
+        """The eval-mode forward: rows float64 or float32 cuda [B, feature_dim] (float64 is rounded to float32 on load).
+        Returns float32 [B,4] = L_low, L_high, use_gamma, gamma.  Sets no status bit."""
+        assert rows.dtype in (torch.float32, torch.float64) and rows.dim() == 2
+        rows = rows.contiguous()
+        B = int(rows.shape[0])
+        n = self.lib.uwie_mlp_workspace_bytes(B, int(hidden_dim))
+        if n == 0:
+            raise _lib.UwieError(f"mlp_forward: batch out of range ({B})")
+        ws = torch.empty(int(n), dtype=torch.uint8, device=self.torch_device)
+        out = self.empty((B, 4), torch.float32)
+        check(self.lib.uwie_mlp_forward(self._ctx, net, _ptr(rows), int(rows.dtype == torch.float64), B, _ptr(out), _ptr(ws),
+                                        ws.numel(), self.stream()))
+        return out
 
     def u8_to_f32(self, frames):
         """uint8 cuda tensor of any shape -> float32 of that shape, u8.astype(float32) / 255.0 (uwie_u8_to_f32)."""
