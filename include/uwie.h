@@ -461,6 +461,53 @@ int uwie_mlp_forward(uwie_ctx *ctx, const uwie_mlp *net, const void *d_features,
                      void *d_workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * EndToEndTrainer.train_epoch's step for ParameterPredictor (deep_learning_parameters.py:265-306):
+ * the train-mode forward (:149-163 with the Dropouts of :104, :108, :127 live), its backward (loss.backward(), :288), and
+ * clip_grad_norm_ with torch.optim.Adam (:262, :291-293).  A trainer owns the parameters, the gradients and Adam's two
+ * moments, float32 on the device.  d_params / d_buf: flat in state_dict() order, all tensors, as uwie_mlp_create takes it.
+ * uwie_mlp_trainer_create: the limits of uwie_mlp_create; the moments and the step count start at 0.
+ * uwie_mlp_train_forward: d_features, d_out as uwie_mlp_forward; batch 1 .. 65536.  p in [0, 1): every Dropout's rate; a
+ *   dropped value is x * 0, a kept one x * float32(1 / (1 - p)); p = 0 has no dropout and gives uwie_mlp_forward's bits.
+ *   There are 1 + 2 * num_blocks sites of [batch][hidden], in call order: input_proj.2, then per block block.2 and dropout.
+ *   mask_mode UWIE_MASKS_GIVEN: d_masks uint8 [sites][batch][hidden], nonzero keeps (required when p > 0).
+ *   UWIE_MASKS_DRAWN: the keep bit of (site, row, column) is drawn by Philox4x32-10 from (seed, the trainer's step count, site,
+ *   row, column) alone; d_masks (NULL: not written) receives the masks.  The workspace
+ *   (uwie_mlp_train_workspace_bytes, 0: out of range) keeps what the backward needs and must stay untouched until it ran.
+ * uwie_mlp_backward: the gradients of the last uwie_mlp_train_forward (same d_features, batch, workspace) given d_grad_out
+ *   [batch][4] in the gated order, as uwie_ref_loss_bwd_f32 writes d_grad_params; its first two columns are never read.
+ *   Overwrites the trainer's gradients (zero_grad); the L_low and L_high heads get exact zeros.  Deterministic.
+ * uwie_mlp_adam_step: total_norm over all tensors but the L_low / L_high heads (they have no gradient in the reference, so
+ *   torch skips them), gradients *= min(max_norm / (total_norm + 1e-6), 1), then Adam's update with the step count + 1
+ *   (no weight decay); those heads stay as they are.  d_norm (NULL: not written): one float64, total_norm.  No host read.
+ * uwie_mlp_trainer_get / _set: copy one of the four arrays to / from d_buf; they wait for the device.
+ * uwie_mlp_trainer_eval: uwie_mlp_forward on the current weights (workspace: uwie_mlp_workspace_bytes).
+ */
+#define UWIE_MASKS_GIVEN 0
+#define UWIE_MASKS_DRAWN 1
+#define UWIE_TRAINER_PARAMS 0
+#define UWIE_TRAINER_GRADS 1
+#define UWIE_TRAINER_EXP_AVG 2
+#define UWIE_TRAINER_EXP_AVG_SQ 3
+typedef struct uwie_mlp_trainer uwie_mlp_trainer;
+int uwie_mlp_trainer_create(uwie_ctx *ctx, const float *d_params, int feature_dim, int hidden_dim, int num_blocks,
+                            uwie_mlp_trainer **out_trainer);
+void uwie_mlp_trainer_destroy(uwie_mlp_trainer *trainer);
+size_t uwie_mlp_train_workspace_bytes(int batch, int hidden_dim, int num_blocks);
+int uwie_mlp_train_forward(uwie_ctx *ctx, uwie_mlp_trainer *trainer, const void *d_features, int features_are_f64, int batch, double p,
+                           int mask_mode, uint8_t *d_masks, uint64_t seed, float *d_out, void *d_workspace, size_t workspace_bytes,
+                           void *stream);
+int uwie_mlp_backward(uwie_ctx *ctx, uwie_mlp_trainer *trainer, const void *d_features, int features_are_f64, int batch,
+                      const float *d_grad_out, void *d_workspace, size_t workspace_bytes, void *stream);
+int uwie_mlp_adam_step(uwie_ctx *ctx, uwie_mlp_trainer *trainer, double lr, double beta1, double beta2, double eps, double max_norm,
+                       double *d_norm, void *stream);
+int uwie_mlp_trainer_get(uwie_mlp_trainer *trainer, int which, float *d_buf);
+int uwie_mlp_trainer_set(uwie_mlp_trainer *trainer, int which, const float *d_buf);
+long long uwie_mlp_trainer_step_count(const uwie_mlp_trainer *trainer);
+int uwie_mlp_trainer_set_step_count(uwie_mlp_trainer *trainer, long long step);
+int uwie_mlp_trainer_eval(uwie_ctx *ctx, const uwie_mlp_trainer *trainer, const void *d_features, int features_are_f64, int batch,
+                          float *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
  * u8.astype(float32) / 255.0 of n bytes in any layout (each value (float)v / 255.0f, IEEE division): the float image of
  * EnhancementPredictor.enhance_image (use_trained_model.py:48-51) for decoded frames, kept in their [H][W][3] layout.
  * d_in 4-byte aligned, d_out 16-byte aligned; no workspace.

@@ -15,6 +15,8 @@ STATUS_CLASSIFY_NAN = 64  # include/uwie.h UWIE_STATUS_CLASSIFY_NAN
 LOSS_IDENTITY, LOSS_VGG, LOSS_GATED = 0, 1, 2  # include/uwie.h UWIE_LOSS_*
 VGG_F32, VGG_F16, VGG_PARAMS = 0, 1, 1735488  # include/uwie.h UWIE_VGG_F32, UWIE_VGG_F16, UWIE_VGG_PARAMS
 PARAM_NET_PARAMS = {True: 8500100, False: 8459652}  # include/uwie.h UWIE_PARAM_NET_PARAMS(use_features)
+MASKS_GIVEN, MASKS_DRAWN = 0, 1  # include/uwie.h UWIE_MASKS_*
+TRAINER_PARAMS, TRAINER_GRADS, TRAINER_EXP_AVG, TRAINER_EXP_AVG_SQ = 0, 1, 2, 3  # include/uwie.h UWIE_TRAINER_*
 FLIP_LR, FLIP_UD = 1, 2  # include/uwie.h UWIE_FLIP_LR, UWIE_FLIP_UD
 RESIZE_MAX_SIDE, RESIZE_MAX_SRC = 4096, 32768  # include/uwie.h UWIE_RESIZE_MAX_SIDE, UWIE_RESIZE_MAX_SRC
 INTER_F64, INTER_FX32, INTER_F32T = 0, 1, 2  # uwie_params.inter_dtype
@@ -134,6 +136,17 @@ SIGNATURES = {
     "uwie_mlp_destroy": [_VP],
     "uwie_mlp_workspace_bytes": [_I, _I],
     "uwie_mlp_forward": [_VP, _VP, _VP, _I, _I, _VP, _VP, _SZ, _VP],
+    "uwie_mlp_trainer_create": [_VP, _VP, _I, _I, _I, ctypes.POINTER(_VP)],
+    "uwie_mlp_trainer_destroy": [_VP],
+    "uwie_mlp_train_workspace_bytes": [_I, _I, _I],
+    "uwie_mlp_train_forward": [_VP, _VP, _VP, _I, _I, _D, _I, _VP, ctypes.c_uint64, _VP, _VP, _SZ, _VP],
+    "uwie_mlp_backward": [_VP, _VP, _VP, _I, _I, _VP, _VP, _SZ, _VP],
+    "uwie_mlp_adam_step": [_VP, _VP, _D, _D, _D, _D, _D, _VP, _VP],
+    "uwie_mlp_trainer_get": [_VP, _I, _VP],
+    "uwie_mlp_trainer_set": [_VP, _I, _VP],
+    "uwie_mlp_trainer_step_count": [_VP],
+    "uwie_mlp_trainer_set_step_count": [_VP, ctypes.c_longlong],
+    "uwie_mlp_trainer_eval": [_VP, _VP, _VP, _I, _I, _VP, _VP, _SZ, _VP],
     "uwie_u8_to_f32": [_VP, _VP, _VP, _SZ, _VP],
     "uwie_extract_features_u8": [_VP, _VP, _VP, _I, _I, _I, _VP, _SZ, _VP],
     "uwie_feature_extractor_count": [_I, _I],
@@ -190,6 +203,9 @@ _RESTYPES = {
     "uwie_workspace_bytes_diff_gated_u8": ctypes.c_size_t,
     "uwie_mlp_workspace_bytes": ctypes.c_size_t,
     "uwie_mlp_destroy": None,
+    "uwie_mlp_train_workspace_bytes": ctypes.c_size_t,
+    "uwie_mlp_trainer_destroy": None,
+    "uwie_mlp_trainer_step_count": ctypes.c_longlong,
 }
 
 _lib = None

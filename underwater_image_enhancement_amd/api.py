@@ -30,7 +30,7 @@ from . import _lib
 # the enhancement modules and ReferenceLoss live in modules.py; this module re-exports them
 from .modules import (DifferentiableEnhancement, DiffEnhanceFunction, DiffEnhanceLossFunction,  # noqa: F401
                       GatedDifferentiableEnhancement, GatedDiffEnhanceFunction, GatedDiffEnhanceLossFunction, ReferenceLoss,
-                      RefLossFunction, _loss_reference, _module_loss, _raise_rank_error, _read_loss)
+                      RefLossFunction, _image_batch, _loss_reference, _module_loss, _raise_rank_error, _read_loss)
 from .runtime import Device, get_device
 
 
@@ -1015,6 +1015,218 @@ class GatedEnhancementPredictor:
                 features = dev.feature_extractor((nhwc * 255).to(torch.uint8), nhwc)
             cols = self.model.columns(features, dev)
             return self.criterion.through(self.enhancer, x, self._dict(cols), references)
+
+
+# ------------------------------------------------------------------ EndToEndTrainer (N14)
+class _TrainerPredictor:
+    """``EndToEndTrainer.param_predictor``: the trainer's current weights behind ``ParameterPredictor``'s eval forward."""
+
+    def __init__(self, trainer):
+        self._trainer = trainer
+        self.feature_dim, self.hidden_dim, self.num_blocks = trainer.feature_dim, trainer.hidden_dim, trainer.num_blocks
+        self.device = trainer.device
+
+    def state_dict(self):
+        return self._trainer.state_dict()
+
+    def columns(self, rows, dev: Device | None = None):
+        dev = dev or get_device(self.device)
+        return dev.mlp_trainer_eval(self._trainer._handle, self._trainer._rows(dev, rows), self.hidden_dim)
+
+    def forward(self, rows):
+        cols = self.columns(rows)
+        at = {k: i for i, k in enumerate(GatedDifferentiableEnhancement.KEYS)}
+        return {k: cols[:, at[k]:at[k] + 1] for k in GATED_PARAM_KEYS}
+
+    __call__ = forward
+
+
+class EndToEndTrainer:
+    """``deep_learning_parameters.EndToEndTrainer`` (:253-349) on the device (k_mlp_train.hip).
+    ``state_or_predictor``: a ``uw.ParameterPredictor`` or anything it takes (a state dict, the module, a checkpoint or its
+    path).  The trainer owns the weights, their gradients and Adam's moments on the GPU; the reference's hyperparameters are
+    the defaults (Adam lr 1e-4, betas (0.9, 0.999), eps 1e-8; ``clip_grad_norm_`` at 1.0; every Dropout at 0.3).
+
+    ``train_step(images, references, features=None, masks=None)``: ``train_epoch``'s loop body (:273-298): features
+    (``None``: ``FeatureExtractor``'s rows of the images) -> train-mode MLP -> gated enhancement and ``ReferenceLoss`` in one
+    sweep -> their backward -> the MLP's backward -> clip and Adam.  Returns ``(loss, {'l1', 'l2'})`` as Python floats; the
+    loss is the one host read.  ``masks``: uint8 ``[1 + 2 * num_blocks, B, hidden]`` keep bits in the Dropouts' call order
+    (``None``: drawn from ``(seed, step)``).
+    ``train_epoch(batches)`` / ``validate(batches)``: the reference's dict batches (``'image'``, ``'reference'``,
+    ``'features'``) -> ``(avg_loss, {'l1', 'l2'})``.  ``param_predictor``: the current weights as an eval forward.
+    ``save_model`` / ``load_model``: the reference's checkpoint, ``torch.optim.Adam``'s state dict included."""
+
+    BETAS, EPS = (0.9, 0.999), 1e-8
+
+    def __init__(self, state_or_predictor, device: int | None = None, lr: float = 1e-4, max_norm: float = 1.0, dropout: float = 0.3,
+                 seed: int = 0):
+        if hasattr(state_or_predictor, "state_dict") and not isinstance(state_or_predictor, torch.nn.Module):
+            state_or_predictor = state_or_predictor.state_dict()
+        state, self.feature_dim, self.hidden_dim, self.num_blocks = _predictor_state(state_or_predictor)
+        self._layout = [(k, tuple(v.shape)) for k, v in state.items()]
+        self._count = sum(int(v.numel()) for v in state.values())
+        self.device, self.lr, self.betas, self.eps = device, float(lr), self.BETAS, self.EPS
+        self.max_norm, self.dropout, self.seed = float(max_norm), float(dropout), int(seed)
+        dev = get_device(device)
+        self._index = dev.index
+        self._handle = dev.mlp_trainer_create(torch.cat([t.reshape(-1) for t in state.values()]), self.feature_dim, self.hidden_dim,
+                                              self.num_blocks)
+        self.param_predictor = _TrainerPredictor(self)
+        self.enhancement = GatedDifferentiableEnhancement()
+        self.enhancement.device = device
+        self.criterion = ReferenceLoss(0.5, 0.5, device=device)
+        self._grad_loss = dev.tensor(np.array([0.5, 0.5], dtype=np.float32))  # d loss / d l1, d loss / d l2 (:190)
+
+    def close(self):
+        if getattr(self, "_handle", None) is not None:
+            get_device(self._index).mlp_trainer_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    @property
+    def step_count(self) -> int:
+        return int(get_device(self._index).lib.uwie_mlp_trainer_step_count(self._handle))
+
+    # ---- state
+    def _free_of_gradient(self):
+        """indices (in ``state_dict()`` order) of the L_low / L_high heads' tensors: no gradient in the reference, so no
+        Adam state"""
+        return {i for i, (k, _) in enumerate(self._layout) if k.startswith(("param_heads.L_low.", "param_heads.L_high."))}
+
+    def _split(self, flat):
+        out, at = {}, 0
+        flat = flat.cpu()
+        for key, shape in self._layout:
+            n = int(np.prod(shape))
+            out[key] = flat[at:at + n].reshape(shape).clone()
+            at += n
+        return out
+
+    def _array(self, which: int):
+        return self._split(get_device(self._index).mlp_trainer_get(self._handle, which, self._count))
+
+    def state_dict(self):
+        return self._array(_lib.TRAINER_PARAMS)
+
+    def gradients(self):
+        """the gradients of the last ``train_step`` (clipped, as ``p.grad`` after ``clip_grad_norm_``), by key"""
+        return self._array(_lib.TRAINER_GRADS)
+
+    def _set(self, which: int, tensors):
+        flat = torch.cat([torch.as_tensor(tensors[k]).detach().to(dtype=torch.float32, device="cpu").reshape(-1) for k, _ in self._layout])
+        get_device(self._index).mlp_trainer_set(self._handle, which, flat)
+
+    def optimizer_state_dict(self):
+        """``torch.optim.Adam(...).state_dict()`` of this trainer: no ``state`` entry for the gradient-free heads, ``step`` a
+        float32 0-dim tensor; empty ``state`` before the first step."""
+        n = len(self._layout)
+        probe = torch.optim.Adam([torch.nn.Parameter(torch.zeros(())) for _ in range(n)], lr=self.lr, betas=self.betas, eps=self.eps)
+        sd = probe.state_dict()
+        step = self.step_count
+        if step > 0:
+            m, v, skip = self._array(_lib.TRAINER_EXP_AVG), self._array(_lib.TRAINER_EXP_AVG_SQ), self._free_of_gradient()
+            sd["state"] = {i: {"step": torch.tensor(float(step), dtype=torch.float32), "exp_avg": m[k], "exp_avg_sq": v[k]}
+                           for i, (k, _) in enumerate(self._layout) if i not in skip}
+        return sd
+
+    def save_model(self, path):
+        torch.save({"param_predictor": self.state_dict(), "optimizer": self.optimizer_state_dict()}, path)
+
+    def load_model(self, path):
+        ckpt = path if isinstance(path, dict) else torch.load(path, map_location="cpu", weights_only=False)
+        state, f, h, nb = _predictor_state(ckpt["param_predictor"])
+        if (f, h, nb) != (self.feature_dim, self.hidden_dim, self.num_blocks):
+            raise ValueError(f"checkpoint of a ({f}, {h}, {nb}) network, this trainer holds ({self.feature_dim}, {self.hidden_dim}, "
+                             f"{self.num_blocks})")
+        opt = ckpt["optimizer"]
+        entries, steps = opt.get("state", {}), set()
+        zeros = {k: torch.zeros(shape) for k, shape in self._layout}
+        m, v = dict(zeros), dict(zeros)
+        for i, (k, shape) in enumerate(self._layout):
+            e = entries.get(i)
+            if e is None:
+                continue
+            if tuple(e["exp_avg"].shape) != shape or tuple(e["exp_avg_sq"].shape) != shape:
+                raise ValueError(f"optimizer state {i} does not have the shape of '{k}' {shape}")
+            m[k], v[k] = e["exp_avg"], e["exp_avg_sq"]
+            steps.add(int(float(e["step"])))
+        if len(steps) > 1:
+            raise ValueError(f"optimizer state with different step counts {sorted(steps)}")
+        dev = get_device(self._index)
+        self._set(_lib.TRAINER_PARAMS, state)
+        self._set(_lib.TRAINER_EXP_AVG, m)
+        self._set(_lib.TRAINER_EXP_AVG_SQ, v)
+        _lib.check(dev.lib.uwie_mlp_trainer_set_step_count(self._handle, steps.pop() if steps else 0))
+        for g in opt.get("param_groups", [])[:1]:
+            self.lr, self.betas, self.eps = float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"])
+
+    # ---- the step
+    def _rows(self, dev: Device, rows):
+        if not isinstance(rows, torch.Tensor):
+            rows = torch.from_numpy(np.ascontiguousarray(rows))
+        if rows.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"expected float32 or float64 feature rows, got {rows.dtype}")
+        if rows.dim() != 2 or rows.shape[1] != self.feature_dim or rows.shape[0] == 0:
+            raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({'x'.join(str(v) for v in rows.shape)} and "
+                               f"{self.feature_dim}x{self.hidden_dim})")
+        return rows.detach().to(dev.torch_device).contiguous()
+
+    def _features(self, dev: Device, x, features):
+        if features is None:
+            nhwc = x.permute(0, 2, 3, 1).contiguous()
+            features = dev.feature_extractor((nhwc * 255).to(torch.uint8), nhwc)
+        return self._rows(dev, features)
+
+    def train_step(self, images, references, features=None, masks=None):
+        dev = get_device(self._index)
+        x = _image_batch(dev, images).contiguous()
+        ref = _loss_reference(dev, x, references)
+        rows = self._features(dev, x, features)
+        if rows.shape[0] != x.shape[0]:
+            raise ValueError(f"{rows.shape[0]} feature rows for {x.shape[0]} images")
+        if masks is not None:
+            masks = dev.tensor(np.asarray(masks)) if not isinstance(masks, torch.Tensor) else masks.to(dev.torch_device)
+            want = (1 + 2 * self.num_blocks, int(rows.shape[0]), self.hidden_dim)
+            if tuple(masks.shape) != want:
+                raise ValueError(f"masks of shape {tuple(masks.shape)}, expected {want}")
+            masks = (masks != 0).to(torch.uint8).contiguous()
+        ws = dev.mlp_train_workspace(rows.shape[0], self.hidden_dim, self.num_blocks)
+        cols = dev.mlp_train_forward(self._handle, rows, ws, self.dropout, masks, self.seed)
+        _, saved, buf = dev.ref_loss_f32(_lib.LOSS_GATED, x, cols, ref, True, status=True)
+        _, grad_cols = dev.ref_loss_bwd_f32(_lib.LOSS_GATED, x, cols, saved, ref, self._grad_loss, True, want_img=False)
+        dev.mlp_backward(self._handle, rows, ws, grad_cols)
+        dev.mlp_adam_step(self._handle, self.lr, self.betas, self.eps, self.max_norm)
+        l1, l2 = _read_loss(dev, buf, x, cols)
+        return float(np.float32(0.5) * np.float32(l1) + np.float32(0.5) * np.float32(l2)), {"l1": l1, "l2": l2}
+
+    def validate_batch(self, images, references, features=None):
+        """``validate``'s loop body (:316-329): ``(loss, {'l1', 'l2'})`` of the current weights in eval mode, one host read."""
+        dev = get_device(self._index)
+        x = _image_batch(dev, images)
+        with torch.no_grad():
+            cols = self.param_predictor.columns(self._features(dev, x, features), dev)
+            _, parts = self.criterion.through(self.enhancement, x, GatedEnhancementPredictor._dict(cols), references)
+        return float(np.float32(0.5) * np.float32(parts["l1"]) + np.float32(0.5) * np.float32(parts["l2"])), parts
+
+    @staticmethod
+    def _average(results):
+        """(:303-306, :331-334) the averages over the batches"""
+        results = list(results)
+        n = len(results)
+        total = sum(loss for loss, _ in results)
+        parts = {k: sum(p[k] for _, p in results) / n for k in ("l1", "l2")}
+        return total / n, parts
+
+    def train_epoch(self, batches):
+        return self._average(self.train_step(b["image"], b["reference"], b.get("features")) for b in batches)
+
+    def validate(self, batches):
+        return self._average(self.validate_batch(b["image"], b["reference"], b.get("features")) for b in batches)
 
 
 QUALITY_KEYS = ("contrast", "sharpness", "entropy", "saturation", "brightness", "edge_density", "colorfulness", "naturalness")

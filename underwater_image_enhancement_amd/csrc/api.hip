@@ -1530,6 +1530,192 @@ int uwie_mlp_forward(uwie_ctx *ctx, const uwie_mlp *net, const void *d_features,
     return launch_mlp(net->net, d_features, features_are_f64 != 0, batch, d_out, d_workspace, (hipStream_t)stream);
 }
 
+// EndToEndTrainer's training step (k_mlp_train.hip)
+struct uwie_mlp_trainer {
+    int device;
+    Mlp net;            // device pointers into arrays[UWIE_TRAINER_PARAMS]
+    float *arrays[4];   // parameters, gradients, exp_avg, exp_avg_sq in the packed order (mlp_pack)
+    double *partial;    // the norm's per-block sums
+    long long step;     // Adam steps taken
+    int fwd_batch;      // the batch of the last train forward (0: none) and its dropout scale
+    float fwd_scale;
+};
+
+static void trainer_free(uwie_mlp_trainer *tr)
+{
+    for (float *a : tr->arrays) (void)hipFree(a);
+    (void)hipFree(tr->partial);
+    delete tr;
+}
+
+int uwie_mlp_trainer_create(uwie_ctx *ctx, const float *d_params, int feature_dim, int hidden_dim, int num_blocks,
+                            uwie_mlp_trainer **out_trainer)
+{
+    UWIE_REQUIRE(ctx && d_params && out_trainer, "mlp_trainer_create: NULL pointer");
+    *out_trainer = nullptr;
+    UWIE_REQUIRE(mlp_dims_ok(feature_dim, hidden_dim, num_blocks),
+                 "mlp_trainer_create: feature_dim 1 .. 1152, hidden_dim even 2 .. 1152, num_blocks 0 .. 64");
+    UWIE_SCOPE(ctx);
+    const size_t bytes = mlp_count(feature_dim, hidden_dim, num_blocks) * sizeof(float);
+    uwie_mlp_trainer *tr = new uwie_mlp_trainer{};
+    tr->device = ctx->device;
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 4 && e == hipSuccess; ++i) {
+        e = hipMalloc((void **)&tr->arrays[i], bytes);
+        if (e == hipSuccess && i > 0) e = hipMemset(tr->arrays[i], 0, bytes);
+    }
+    if (e == hipSuccess) e = hipMalloc((void **)&tr->partial, mlp_adam_scratch_bytes());
+    int rc = UWIE_OK;
+    if (e == hipSuccess) {
+        rc = mlp_pack(d_params, feature_dim, hidden_dim, num_blocks, tr->arrays[UWIE_TRAINER_PARAMS], &tr->net, nullptr);
+        if (rc == UWIE_OK) e = hipStreamSynchronize(nullptr);
+    }
+    if (rc != UWIE_OK || e != hipSuccess) {
+        trainer_free(tr);
+        if (e != hipSuccess) set_error("mlp_trainer_create: %s", hipGetErrorString(e));
+        return rc != UWIE_OK ? rc : UWIE_E_HIP;
+    }
+    *out_trainer = tr;
+    return UWIE_OK;
+}
+
+void uwie_mlp_trainer_destroy(uwie_mlp_trainer *trainer)
+{
+    if (!trainer) return;
+    int prev = -1;
+    const bool switch_dev = hipGetDevice(&prev) == hipSuccess && prev != trainer->device && hipSetDevice(trainer->device) == hipSuccess;
+    trainer_free(trainer);
+    if (switch_dev) (void)hipSetDevice(prev);
+}
+
+static bool train_batch_ok(int batch) { return batch >= 1 && batch <= 65536; }
+
+size_t uwie_mlp_train_workspace_bytes(int batch, int hidden_dim, int num_blocks)
+{
+    if (!train_batch_ok(batch) || !mlp_dims_ok(1, hidden_dim, num_blocks)) return 0;
+    return mlp_train_ws_bytes(batch, hidden_dim, num_blocks);
+}
+
+int uwie_mlp_train_forward(uwie_ctx *ctx, uwie_mlp_trainer *trainer, const void *d_features, int features_are_f64, int batch, double p,
+                           int mask_mode, uint8_t *d_masks, uint64_t seed, float *d_out, void *d_workspace, size_t workspace_bytes,
+                           void *stream)
+{
+    UWIE_REQUIRE(ctx && trainer && d_features && d_out, "mlp_train_forward: NULL pointer");
+    UWIE_REQUIRE(trainer->device == ctx->device, "mlp_train_forward: the trainer lives on another device");
+    UWIE_REQUIRE(train_batch_ok(batch), "mlp_train_forward: batch out of range (1 .. 65536)");
+    UWIE_REQUIRE(((uintptr_t)d_features & (features_are_f64 ? 7 : 3)) == 0 && ((uintptr_t)d_out & 3) == 0,
+                 "mlp_train_forward: d_features and d_out must be aligned for their element types");
+    UWIE_REQUIRE(p >= 0.0 && p < 1.0, "mlp_train_forward: the dropout rate p must lie in [0, 1)");
+    UWIE_REQUIRE(mask_mode == UWIE_MASKS_GIVEN || mask_mode == UWIE_MASKS_DRAWN, "mlp_train_forward: mask_mode is UWIE_MASKS_GIVEN or UWIE_MASKS_DRAWN");
+    UWIE_REQUIRE(mask_mode == UWIE_MASKS_DRAWN || p == 0.0 || d_masks, "mlp_train_forward: given masks need d_masks");
+    const Mlp &net = trainer->net;
+    UWIE_CHECK_WS(mlp_train_ws_bytes(batch, net.H, net.nb));
+    UWIE_SCOPE(ctx);
+    const bool drawn = mask_mode == UWIE_MASKS_DRAWN;
+    hipStream_t st = (hipStream_t)stream;
+    if (drawn && d_masks && p == 0.0)  // nothing is dropped and no site draws
+        UWIE_HIP_CHECK(hipMemsetAsync(d_masks, 1, (size_t)mlp_train_sites(net.nb) * batch * net.H, st));
+    UWIE_TRY(launch_mlp_train_forward(net, d_features, features_are_f64 != 0, batch, p, drawn ? nullptr : d_masks,
+                                      drawn ? d_masks : nullptr, seed, (uint32_t)trainer->step, d_out, d_workspace, st));
+    trainer->fwd_batch = batch;
+    trainer->fwd_scale = (float)(1.0 / (1.0 - p));
+    return UWIE_OK;
+}
+
+int uwie_mlp_backward(uwie_ctx *ctx, uwie_mlp_trainer *trainer, const void *d_features, int features_are_f64, int batch,
+                      const float *d_grad_out, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE(ctx && trainer && d_features && d_grad_out, "mlp_backward: NULL pointer");
+    UWIE_REQUIRE(trainer->device == ctx->device, "mlp_backward: the trainer lives on another device");
+    UWIE_REQUIRE(train_batch_ok(batch), "mlp_backward: batch out of range (1 .. 65536)");
+    UWIE_REQUIRE(((uintptr_t)d_features & (features_are_f64 ? 7 : 3)) == 0 && ((uintptr_t)d_grad_out & 3) == 0,
+                 "mlp_backward: d_features and d_grad_out must be aligned for their element types");
+    UWIE_REQUIRE(trainer->fwd_batch == batch, "mlp_backward: no uwie_mlp_train_forward of this batch precedes it");
+    const Mlp &net = trainer->net;
+    UWIE_CHECK_WS(mlp_train_ws_bytes(batch, net.H, net.nb));
+    UWIE_SCOPE(ctx);
+    return launch_mlp_backward(net, trainer->arrays[UWIE_TRAINER_GRADS], d_features, features_are_f64 != 0, batch, trainer->fwd_scale,
+                               d_grad_out, d_workspace, (hipStream_t)stream);
+}
+
+int uwie_mlp_adam_step(uwie_ctx *ctx, uwie_mlp_trainer *trainer, double lr, double beta1, double beta2, double eps, double max_norm,
+                       double *d_norm, void *stream)
+{
+    UWIE_REQUIRE(ctx && trainer, "mlp_adam_step: NULL pointer");
+    UWIE_REQUIRE(trainer->device == ctx->device, "mlp_adam_step: the trainer lives on another device");
+    UWIE_REQUIRE(lr >= 0.0 && lr < HUGE_VAL && eps >= 0.0 && eps < HUGE_VAL, "mlp_adam_step: lr and eps must be finite and >= 0");
+    UWIE_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "mlp_adam_step: the betas must lie in [0, 1)");
+    UWIE_REQUIRE(max_norm > 0.0, "mlp_adam_step: max_norm must be > 0");
+    UWIE_REQUIRE(((uintptr_t)d_norm & 7) == 0, "mlp_adam_step: d_norm must be 8-byte aligned");
+    UWIE_SCOPE(ctx);
+    // torch.optim.adam._single_tensor_adam: the bias corrections are Python floats of the step count
+    const double t = (double)(trainer->step + 1);
+    const double bc1 = 1.0 - pow(beta1, t), bc2 = 1.0 - pow(beta2, t);
+    const MlpAdam h{(float)max_norm, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)sqrt(bc2), (float)eps,
+                    (float)-(lr / bc1)};
+    UWIE_TRY(launch_mlp_adam(trainer->net, trainer->arrays[0], trainer->arrays[1], trainer->arrays[2], trainer->arrays[3],
+                             trainer->partial, h, d_norm, (hipStream_t)stream));
+    trainer->step += 1;
+    return UWIE_OK;
+}
+
+static int trainer_copy(uwie_mlp_trainer *tr, int which, float *d_buf, bool get, const char *who)
+{
+    if (!tr || !d_buf || which < 0 || which > 3 || ((uintptr_t)d_buf & 3)) {
+        set_error("%s: NULL or misaligned pointer, or which outside UWIE_TRAINER_PARAMS .. UWIE_TRAINER_EXP_AVG_SQ", who);
+        return UWIE_E_INVALID;
+    }
+    int prev = -1;
+    const bool switch_dev = hipGetDevice(&prev) == hipSuccess && prev != tr->device && hipSetDevice(tr->device) == hipSuccess;
+    const Mlp &n = tr->net;
+    hipError_t e = hipDeviceSynchronize();  // work on other streams that reads or writes the arrays
+    int rc = UWIE_OK;
+    if (e == hipSuccess) {
+        rc = get ? mlp_repack(tr->arrays[which], d_buf, n.F, n.H, n.nb, true, nullptr)
+                 : mlp_repack(d_buf, tr->arrays[which], n.F, n.H, n.nb, false, nullptr);
+        if (rc == UWIE_OK) e = hipStreamSynchronize(nullptr);
+    }
+    if (switch_dev) (void)hipSetDevice(prev);
+    if (e != hipSuccess) {
+        set_error("%s: %s", who, hipGetErrorString(e));
+        return UWIE_E_HIP;
+    }
+    return rc;
+}
+
+int uwie_mlp_trainer_get(uwie_mlp_trainer *trainer, int which, float *d_buf)
+{
+    return trainer_copy(trainer, which, d_buf, true, "mlp_trainer_get");
+}
+
+int uwie_mlp_trainer_set(uwie_mlp_trainer *trainer, int which, const float *d_buf)
+{
+    return trainer_copy(trainer, which, const_cast<float *>(d_buf), false, "mlp_trainer_set");
+}
+
+long long uwie_mlp_trainer_step_count(const uwie_mlp_trainer *trainer) { return trainer ? trainer->step : -1; }
+
+int uwie_mlp_trainer_set_step_count(uwie_mlp_trainer *trainer, long long step)
+{
+    UWIE_REQUIRE(trainer != nullptr, "mlp_trainer_set_step_count: NULL trainer");
+    UWIE_REQUIRE(step >= 0 && step < (1ll << 32), "mlp_trainer_set_step_count: step out of range (0 .. 2^32 - 1)");
+    trainer->step = step;
+    return UWIE_OK;
+}
+
+int uwie_mlp_trainer_eval(uwie_ctx *ctx, const uwie_mlp_trainer *trainer, const void *d_features, int features_are_f64, int batch,
+                          float *d_out, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE(ctx && trainer && d_features && d_out, "mlp_trainer_eval: NULL pointer");
+    UWIE_REQUIRE(trainer->device == ctx->device, "mlp_trainer_eval: the trainer lives on another device");
+    UWIE_REQUIRE(batch >= 1 && batch <= (1 << 20), "mlp_trainer_eval: batch out of range (1 .. 2^20)");
+    UWIE_REQUIRE(((uintptr_t)d_features & (features_are_f64 ? 7 : 3)) == 0 && ((uintptr_t)d_out & 3) == 0,
+                 "mlp_trainer_eval: d_features and d_out must be aligned for their element types");
+    UWIE_CHECK_WS(mlp_ws_bytes(batch, trainer->net.H));
+    UWIE_SCOPE(ctx);
+    return launch_mlp(trainer->net, d_features, features_are_f64 != 0, batch, d_out, d_workspace, (hipStream_t)stream);
+}
+
 int uwie_u8_to_f32(uwie_ctx *ctx, const uint8_t *d_in, float *d_out, size_t n, void *stream)
 {
     UWIE_REQUIRE(ctx && d_in && d_out, "u8_to_f32: NULL pointer");

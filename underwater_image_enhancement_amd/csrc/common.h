@@ -496,6 +496,22 @@ int mlp_pack(const float *d_params, int F, int H, int nb, float *blob, Mlp *net,
 size_t mlp_ws_bytes(int B, int hidden);
 // feat: [B][F] float32, or float64 (f64) rounded to float32 on load; out: [B][4] = L_low, L_high, use_gamma, gamma
 int launch_mlp(const Mlp &net, const void *feat, bool f64, int B, float *out, void *ws, hipStream_t st);
+// k_mlp_train.hip: EndToEndTrainer's training step for ParameterPredictor.  Parameters, gradients and
+// Adam's moments share mlp_pack's packed order.
+struct MlpAdam {  // torch.optim.Adam's scalars for one step, rounded to float32 as torch's kernels take them
+    float max_norm, w1, beta2, w2, bc2_sqrt, eps, neg_step;  // w1 = 1 - beta1, w2 = 1 - beta2, neg_step = -lr / (1 - beta1^t)
+};
+size_t mlp_train_ws_bytes(int B, int hidden, int nb);
+int mlp_train_sites(int nb);
+// given: uint8 [sites][B][H] or nullptr (drawn from seed, step); drawn_out: where the drawn masks go, or nullptr
+int launch_mlp_train_forward(const Mlp &net, const void *feat, bool f64, int B, double p, const uint8_t *given, uint8_t *drawn_out,
+                             uint64_t seed, uint32_t step, float *out, void *ws, hipStream_t st);
+int launch_mlp_backward(const Mlp &net, float *grads, const void *feat, bool f64, int B, float scale, const float *grad_out, void *ws,
+                        hipStream_t st);
+size_t mlp_adam_scratch_bytes();
+int launch_mlp_adam(const Mlp &net, float *params, float *grads, float *m, float *v, double *partial, const MlpAdam &h, double *norm_out,
+                    hipStream_t st);
+int mlp_repack(const float *src, float *dst, int F, int H, int nb, bool to_state, hipStream_t st);
 
 // k_fused.hip: the fused tail of the dehazing strategies
 // what the restored image (six_stadigy.py:183-188) is made of; consumers may recompute it from here (restore.h)

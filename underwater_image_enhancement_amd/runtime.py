@@ -486,6 +486,83 @@ class Device:
                                         ws.numel(), self.stream()))
         return out
 
+    # ------------------------------------------------------------------ EndToEndTrainer's step (uwie_mlp_trainer_*)
+    def mlp_trainer_create(self, params, feature_dim: int, hidden_dim: int, num_blocks: int):
+        """A uwie_mlp_trainer handle from the flat state_dict()-order parameters, as mlp_create.  The caller owns it."""
+        flat = params.to(device=self.torch_device, dtype=torch.float32).contiguous()
+        h, half = int(hidden_dim), int(hidden_dim) // 2
+        assert flat.numel() == int(feature_dim) * h + h + int(num_blocks) * 2 * (h * h + h) + half * h + half + 4 * (half + 1)
+        torch.cuda.synchronize(self.index)  # the packing runs on the null stream
+        handle = ctypes.c_void_p()
+        check(self.lib.uwie_mlp_trainer_create(self._ctx, _ptr(flat), int(feature_dim), h, int(num_blocks), ctypes.byref(handle)))
+        return handle
+
+    def mlp_trainer_destroy(self, handle):
+        torch.cuda.synchronize(self.index)
+        self.lib.uwie_mlp_trainer_destroy(handle)
+
+    def mlp_train_workspace(self, B: int, hidden_dim: int, num_blocks: int):
+        n = self.lib.uwie_mlp_train_workspace_bytes(int(B), int(hidden_dim), int(num_blocks))
+        if n == 0:
+            raise _lib.UwieError(f"mlp_train: batch out of range ({B})")
+        return torch.empty(int(n), dtype=torch.uint8, device=self.torch_device)
+
+    def mlp_train_forward(self, tr, rows, ws, p: float, masks=None, seed: int = 0, want_masks=None):
+        """The train-mode forward: rows as mlp_forward; ws from mlp_train_workspace (the backward reads it).  masks: uint8 cuda
+        [sites, B, hidden] (given), or None: drawn from (seed, the trainer's step count), written to want_masks (a uint8
+        tensor of that shape) when it is not None.  Returns float32 [B,4] = L_low, L_high, use_gamma, gamma."""
+        assert rows.dtype in (torch.float32, torch.float64) and rows.dim() == 2 and rows.is_contiguous()
+        B = int(rows.shape[0])
+        out = self.empty((B, 4), torch.float32)
+        if masks is not None:
+            assert masks.dtype == torch.uint8 and masks.is_contiguous() and masks.dim() == 3 and masks.shape[1] == B
+            mode, mptr = _lib.MASKS_GIVEN, _ptr(masks)
+        else:
+            assert want_masks is None or (want_masks.dtype == torch.uint8 and want_masks.is_contiguous() and want_masks.shape[1] == B)
+            mode, mptr = _lib.MASKS_DRAWN, _ptr(want_masks)
+        check(self.lib.uwie_mlp_train_forward(self._ctx, tr, _ptr(rows), int(rows.dtype == torch.float64), B, float(p), mode, mptr,
+                                              int(seed) & (2**64 - 1), _ptr(out), _ptr(ws), ws.numel(), self.stream()))
+        return out
+
+    def mlp_backward(self, tr, rows, ws, grad_out):
+        """The MLP's backward of the last mlp_train_forward (same rows and ws): grad_out float32 cuda [B,4] in the gated order
+        (its first two columns are not read).  Overwrites the trainer's gradients."""
+        assert grad_out.dtype == torch.float32 and tuple(grad_out.shape) == (rows.shape[0], 4) and grad_out.is_contiguous()
+        check(self.lib.uwie_mlp_backward(self._ctx, tr, _ptr(rows), int(rows.dtype == torch.float64), int(rows.shape[0]),
+                                         _ptr(grad_out), _ptr(ws), ws.numel(), self.stream()))
+
+    def mlp_adam_step(self, tr, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=1.0, norm=None):
+        """clip_grad_norm_(max_norm) and one torch.optim.Adam step on the trainer's arrays; norm: a float64 cuda [1] that
+        receives total_norm, or None.  No host read."""
+        assert norm is None or (norm.dtype == torch.float64 and norm.numel() == 1)
+        check(self.lib.uwie_mlp_adam_step(self._ctx, tr, float(lr), float(betas[0]), float(betas[1]), float(eps), float(max_norm),
+                                          _ptr(norm), self.stream()))
+
+    def mlp_trainer_get(self, tr, which: int, count: int):
+        """One of the trainer's arrays (_lib.TRAINER_*) as a float32 cuda [count] in state_dict() order."""
+        buf = self.empty((int(count),), torch.float32)
+        check(self.lib.uwie_mlp_trainer_get(tr, int(which), _ptr(buf)))
+        return buf
+
+    def mlp_trainer_set(self, tr, which: int, flat):
+        flat = flat.to(device=self.torch_device, dtype=torch.float32).contiguous()
+        torch.cuda.synchronize(self.index)
+        check(self.lib.uwie_mlp_trainer_set(tr, int(which), _ptr(flat)))
+
+    def mlp_trainer_eval(self, tr, rows, hidden_dim: int):
+        """mlp_forward on the trainer's current weights."""
+        assert rows.dtype in (torch.float32, torch.float64) and rows.dim() == 2
+        rows = rows.contiguous()
+        B = int(rows.shape[0])
+        n = self.lib.uwie_mlp_workspace_bytes(B, int(hidden_dim))
+        if n == 0:
+            raise _lib.UwieError(f"mlp_trainer_eval: batch out of range ({B})")
+        ws = torch.empty(int(n), dtype=torch.uint8, device=self.torch_device)
+        out = self.empty((B, 4), torch.float32)
+        check(self.lib.uwie_mlp_trainer_eval(self._ctx, tr, _ptr(rows), int(rows.dtype == torch.float64), B, _ptr(out), _ptr(ws),
+                                             ws.numel(), self.stream()))
+        return out
+
     def u8_to_f32(self, frames):
         """uint8 cuda tensor of any shape -> float32 of that shape, u8.astype(float32) / 255.0 (uwie_u8_to_f32)."""
         assert frames.dtype == torch.uint8
