@@ -287,7 +287,7 @@ int uwie_diff_enhance_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_
                               float *d_grad_params, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /*
- * The same module for u8 frames, in the byte domain (k_diffenh_u8.hip): what
+ * The same module for u8 frames, in the byte domain (k_diff_u8.hip): what
  * EnhancementPredictor.process_single_image does from a decoded frame to a u8 frame (use_trained_model.py:113-164).
  * d_in: [batch][H][W][3] uint8, the frame whose float image is u8 / 255.  x = (float)v / 255.0f is strictly increasing in
  * the byte v, so the two sorted positions are two bins of the channel's 256-bin histogram and the stretch takes at most
@@ -330,7 +330,7 @@ int uwie_diff_gated_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_pa
                             void *d_workspace, size_t workspace_bytes, void *stream);
 
 /*
- * The gated module for u8 frames, in the byte domain (k_diffgated_u8.hip): the inference route of
+ * The gated module for u8 frames, in the byte domain (k_diff_u8.hip): the inference route of
  * EndToEndTrainer's stack from a decoded frame to a u8 frame.  d_in: [batch][H][W][3] uint8, the frame whose float image is
  * u8 / 255.  Nothing after the stretch mixes channels, so per image and channel the module is a function of the byte alone:
  * count (256 bins per channel), one block per image that finds the two sorted positions (Python's indexing rules, as above)

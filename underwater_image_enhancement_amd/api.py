@@ -31,7 +31,7 @@ from . import _lib
 from .modules import (DifferentiableEnhancement, DiffEnhanceFunction, DiffEnhanceLossFunction,  # noqa: F401
                       GatedDifferentiableEnhancement, GatedDiffEnhanceFunction, GatedDiffEnhanceLossFunction, ReferenceLoss,
                       RefLossFunction, _image_batch, _loss_reference, _module_loss, _raise_rank_error, _read_loss)
-from .runtime import Device, get_device
+from .runtime import Device, HandleOwner, get_device
 
 
 class UnsupportedInputError(ValueError):
@@ -282,7 +282,7 @@ class PerceptualFunction(torch.autograd.Function):
         return (ctx.dev.perceptual_bwd_f32(ctx.handle, ctx.shape, ctx.ws, grad),) + (None,) * 5
 
 
-class PerceptualLoss(torch.nn.Module):
+class PerceptualLoss(HandleOwner, torch.nn.Module):
     """``vgg_16_UIE.PerceptualLoss`` (:257-269): ``crit(pred, target) = mse_loss(F(pred), F(target))`` with F =
     vgg16().features[:16], a 0-dim loss with ``grad_fn``.
 
@@ -305,28 +305,15 @@ class PerceptualLoss(torch.nn.Module):
         self._tensors = _vgg_tensors(weights)
         self.device = device
         self._torch = {}
-        self._handles = {}
         if device is not None:
             dev = get_device(device)
             for precision in (_lib.VGG_F32, _lib.VGG_F16):
                 self._handle(dev, precision)
 
-    def close(self):
-        for (index, _), h in list(self._handles.items()):
-            get_device(index).vgg_destroy(h)
-        self._handles.clear()
+    def _create_handle(self, dev: Device, precision: int):
+        return dev.vgg_create(torch.cat([t.reshape(-1) for t in self._tensors]), precision)
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
-
-    def _handle(self, dev: Device, precision: int):
-        key = (dev.index, precision)
-        if key not in self._handles:
-            self._handles[key] = dev.vgg_create(torch.cat([t.reshape(-1) for t in self._tensors]), precision)
-        return self._handles[key]
+    _destroy_handle = staticmethod(Device.vgg_destroy)
 
     def features(self, device=None) -> torch.nn.Sequential:
         """The torch module of these weights (vgg16_features16) on ``device`` (default: CPU), cached."""
@@ -538,7 +525,7 @@ def param_net_torch(weights, use_features: bool = True, hidden_dim: int = 256) -
     return net.eval()
 
 
-class VGGParameterNet:
+class VGGParameterNet(HandleOwner):
     """``vgg_16_UIE.ImprovedVGGParameterNet`` (:135-255) in eval mode on the device: ``net(img_tensor, feature_tensor)``
     returns the reference's dict of four ``(B, 1)`` float32 tensors (``omega``, ``gamma``, ``L_low``, ``L_high``);
     ``return_pooled=True`` adds ``'pooled'``, the ``[B, 1024]`` vector after the two global poolings.
@@ -558,29 +545,16 @@ class VGGParameterNet:
         self._state = _param_net_state(weights, self.use_features, hidden_dim)
         self.device = device
         self._torch = {}
-        self._handles = {}
         if device is not None:
             self._handle(get_device(device))
-
-    def close(self):
-        for index, h in list(self._handles.items()):
-            get_device(index).param_net_destroy(h)
-        self._handles.clear()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
 
     def state_dict(self):
         return dict(self._state)
 
-    def _handle(self, dev: Device):
-        if dev.index not in self._handles:
-            flat = torch.cat([t.reshape(-1) for t in self._state.values()])
-            self._handles[dev.index] = dev.param_net_create(flat, self.use_features)
-        return self._handles[dev.index]
+    def _create_handle(self, dev: Device):
+        return dev.param_net_create(torch.cat([t.reshape(-1) for t in self._state.values()]), self.use_features)
+
+    _destroy_handle = staticmethod(Device.param_net_destroy)
 
     def torch_module(self, device=None) -> torch.nn.Module:
         """The torch module of these weights (param_net_torch) on ``device`` (default: CPU), cached."""
@@ -631,28 +605,10 @@ class VGGParameterNet:
     __call__ = forward
 
 
-class EnhancementPredictor:
-    """``use_trained_model.EnhancementPredictor`` (:13-111) on the device, without torchvision or cv2: the network is
-    ``VGGParameterNet`` (use_features=True), the VGG input ``vgg_input``, the features ``extract_all_features``, the
-    enhancement ``DifferentiableEnhancement``.
-
-    Images are uint8 RGB frames, or float32 / float64 images equal to ``u8.astype(dtype) / 255`` in their own dtype (what
-    ``process_single_image`` makes, and NumPy's ``frame / 255``); any other float image raises ``UnsupportedInputError``.
-    For such an image every step of the reference sees the frame's own values: ``(img * 255).astype(uint8)`` gives the
-    frame back, and its float32 cast is ``u8.astype(float32) / 255`` for both dtypes.  ``predict_parameters(img)`` returns the reference's dict of six
-    Python floats (clamped as :70-79); for a ``[B,H,W,3]`` batch, one float64 array per key.  ``enhance_image(img, params)``
-    returns float32 HxWx3, clipped to [0, 1] with NaN and infinities replaced as :101-111.  ``enhance_batch(frames)`` runs
-    the whole chain for a batch as one device pipeline (no host read between the stages) and returns ``[B,H,W,3]`` float32
-    on the device, equal to B ``enhance_image`` calls bit for bit.  ``enhance_batch_u8(frames)`` goes on to the uint8
-    frame ``process_single_image`` writes, in the byte domain; ``process_frames(list)`` is ``process_folder``'s loop for
-    decoded frames of mixed sizes."""
-
-    def __init__(self, weights, input_size: int = 224, device: int | None = None):
-        self.input_size = int(input_size)
-        self.device = device
-        self.model = VGGParameterNet(weights, use_features=True, device=device)
-        self.enhancer = DifferentiableEnhancement()
-        self.enhancer.device = device
+class _FramePredictor:
+    """What ``EnhancementPredictor`` and ``GatedEnhancementPredictor`` share: uint8 frames in, uint8 frames out.  A subclass
+    has ``device``, ``_batch_u8(dev, u8) -> (out_u8, the module's float32 [B,4] parameters, the network's raw [B,4])`` with no
+    host read between its stages, and ``_param_dicts(raw on the host)``: ``predict_parameters``' dict per row."""
 
     @staticmethod
     def _frame_u8(img):
@@ -680,6 +636,82 @@ class EnhancementPredictor:
         """(uint8 [B,H,W,3] on ``dev``, single) from a frame or a batch, uint8 or exactly u8 / 255."""
         batch, _, single = _as_batch_u8(cls._frame_u8(img), dev)
         return batch, single
+
+    def enhance_batch_u8(self, frames):
+        """``process_single_image``'s u8 result (use_trained_model.py:118-127) for a batch, as one device pipeline:
+        ``(out_u8 [B,H,W,3] uint8 on the device, params float32 [B,4])``, ``params`` in the order and with the clamping that
+        the class's enhancement module takes them.  ``frames`` as for ``enhance_batch``; ``out_u8`` equals
+        ``(enhance_batch(frames) * 255).to(uint8)``.  The enhancement runs on the frames' bytes (DESIGN.md sections 16, 17): no
+        float image is made.  No host read: ``Device.check_status`` reports an unindexable sorted position."""
+        dev = get_device(self.device)
+        u8, _ = self._frames(frames, dev)
+        out, params, _ = self._batch_u8(dev, u8)
+        return out, params
+
+    def process_frames(self, frames, filenames=None):
+        """``process_folder``'s loop (use_trained_model.py:145-164) without the file I/O, for decoded frames whose sizes may
+        differ: ``frames`` is a sequence of HxWx3 frames (uint8, or float images equal to u8 / 255), ``filenames`` optional
+        names for the messages.  Frames of equal shape go through one ``enhance_batch_u8`` pipeline per shape.  Returns
+        ``(outputs, params)`` in input order: ``outputs[i]`` the enhanced uint8 HxWx3 NumPy frame, ``params[i]`` the dict
+        ``predict_parameters`` gives for it.  A frame that raises does not stop the others (:163-164): its output is ``None``
+        and its ``params`` entry is the exception's message (prefixed with its file name when names are given).  Input
+        errors are found per frame before any launch; an error of a group's device run fails that group's frames."""
+        frames = list(frames)
+        if filenames is not None and len(filenames) != len(frames):
+            raise ValueError(f"{len(filenames)} file names for {len(frames)} frames")
+        dev = get_device(self.device)
+        outputs, params = [None] * len(frames), [None] * len(frames)
+
+        def fail(i, e):
+            outputs[i] = None
+            params[i] = f"{filenames[i]}: {e}" if filenames is not None else str(e)
+
+        groups = {}
+        for i, f in enumerate(frames):
+            try:
+                u8, single = self._frames(f, dev)
+                if not single:
+                    raise ValueError(f"process_frames takes HxWx3 frames, got {tuple(u8.shape)}")
+                groups.setdefault(tuple(u8.shape), []).append((i, u8))
+            except Exception as e:  # noqa: BLE001 - the reference's loop catches everything (:163)
+                fail(i, e)
+
+        for members in groups.values():
+            try:
+                out, _, raw = self._batch_u8(dev, torch.cat([u8 for _, u8 in members]))
+                out, raw = out.cpu().numpy(), raw.cpu().numpy()
+                dev.check_status()
+            except Exception as e:  # noqa: BLE001 - a device error: the whole group fails, nothing is launched again for it
+                for i, _ in members:
+                    fail(i, e)
+                continue
+            for (i, _), o, d in zip(members, out, self._param_dicts(raw)):
+                outputs[i], params[i] = o, d
+        return outputs, params
+
+
+class EnhancementPredictor(_FramePredictor):
+    """``use_trained_model.EnhancementPredictor`` (:13-111) on the device, without torchvision or cv2: the network is
+    ``VGGParameterNet`` (use_features=True), the VGG input ``vgg_input``, the features ``extract_all_features``, the
+    enhancement ``DifferentiableEnhancement``.
+
+    Images are uint8 RGB frames, or float32 / float64 images equal to ``u8.astype(dtype) / 255`` in their own dtype (what
+    ``process_single_image`` makes, and NumPy's ``frame / 255``); any other float image raises ``UnsupportedInputError``.
+    For such an image every step of the reference sees the frame's own values: ``(img * 255).astype(uint8)`` gives the
+    frame back, and its float32 cast is ``u8.astype(float32) / 255`` for both dtypes.  ``predict_parameters(img)`` returns the reference's dict of six
+    Python floats (clamped as :70-79); for a ``[B,H,W,3]`` batch, one float64 array per key.  ``enhance_image(img, params)``
+    returns float32 HxWx3, clipped to [0, 1] with NaN and infinities replaced as :101-111.  ``enhance_batch(frames)`` runs
+    the whole chain for a batch as one device pipeline (no host read between the stages) and returns ``[B,H,W,3]`` float32
+    on the device, equal to B ``enhance_image`` calls bit for bit.  ``enhance_batch_u8(frames)`` goes on to the uint8
+    frame ``process_single_image`` writes, in the byte domain; ``process_frames(list)`` is ``process_folder``'s loop for
+    decoded frames of mixed sizes."""
+
+    def __init__(self, weights, input_size: int = 224, device: int | None = None):
+        self.input_size = int(input_size)
+        self.device = device
+        self.model = VGGParameterNet(weights, use_features=True, device=device)
+        self.enhancer = DifferentiableEnhancement()
+        self.enhancer.device = device
 
     def _raw(self, dev: Device, u8):
         """The network's float32 [B,4] (omega, gamma, L_low, L_high) for uint8 frames on the device."""
@@ -746,16 +778,6 @@ class EnhancementPredictor:
         out, _ = dev.diff_enhance_u8(u8, clipped[:, [2, 3, 0, 1]].contiguous(), 3, want_u8=True, want_f32=False)
         return out, clipped, raw
 
-    def enhance_batch_u8(self, frames):
-        """``process_single_image``'s u8 result (use_trained_model.py:118-127) for a batch, as one device pipeline:
-        ``(out_u8 [B,H,W,3] uint8 on the device, params float32 [B,4] = omega, gamma, L_low, L_high, clamped)``.  ``frames`` as
-        for ``enhance_batch``; ``out_u8`` equals ``(enhance_batch(frames) * 255).to(uint8)``.  The enhancement runs on the
-        frames' bytes: no float image is made."""
-        dev = get_device(self.device)
-        u8, _ = self._frames(frames, dev)
-        out, clipped, _ = self._batch_u8(dev, u8)
-        return out, clipped
-
     @staticmethod
     def _param_dicts(raw):
         """predict_parameters' dicts (six Python floats each) from the network's raw outputs, float32 [B,4] on the host."""
@@ -768,57 +790,30 @@ class EnhancementPredictor:
             dicts.append(d)
         return dicts
 
-    def process_frames(self, frames, filenames=None):
-        """``process_folder``'s loop (use_trained_model.py:145-164) without the file I/O, for decoded frames whose sizes may
-        differ: ``frames`` is a sequence of HxWx3 frames (uint8, or float images equal to u8 / 255), ``filenames`` optional
-        names for the messages.  Frames of equal shape go through one ``enhance_batch_u8`` call per shape.  Returns
-        ``(outputs, params)`` in input order: ``outputs[i]`` the enhanced uint8 HxWx3 NumPy frame, ``params[i]`` the dict
-        ``predict_parameters`` gives for it.  A frame that raises does not stop the others (:163-164): its output is ``None``
-        and its ``params`` entry is the exception's message (prefixed with its file name when names are given).  Input
-        errors are found per frame before any launch; an error of a group's device run fails that group's frames."""
-        return _process_frames(self, frames, filenames)
-
-
-def _process_frames(predictor, frames, filenames):
-    """``process_frames`` of ``EnhancementPredictor`` and ``GatedEnhancementPredictor``: grouping by shape and keep-going.
-    ``predictor`` has ``device``, ``_frames(frame, dev)``, ``_batch_u8(dev, u8) -> (out_u8, params, raw)`` and
-    ``_param_dicts(raw on the host)``."""
-    frames = list(frames)
-    if filenames is not None and len(filenames) != len(frames):
-        raise ValueError(f"{len(filenames)} file names for {len(frames)} frames")
-    dev = get_device(predictor.device)
-    outputs, params = [None] * len(frames), [None] * len(frames)
-
-    def fail(i, e):
-        outputs[i] = None
-        params[i] = f"{filenames[i]}: {e}" if filenames is not None else str(e)
-
-    groups = {}
-    for i, f in enumerate(frames):
-        try:
-            u8, single = predictor._frames(f, dev)
-            if not single:
-                raise ValueError(f"process_frames takes HxWx3 frames, got {tuple(u8.shape)}")
-            groups.setdefault(tuple(u8.shape), []).append((i, u8))
-        except Exception as e:  # noqa: BLE001 - the reference's loop catches everything (:163)
-            fail(i, e)
-
-    for members in groups.values():
-        try:
-            out, _, raw = predictor._batch_u8(dev, torch.cat([u8 for _, u8 in members]))
-            out, raw = out.cpu().numpy(), raw.cpu().numpy()
-            dev.check_status()
-        except Exception as e:  # noqa: BLE001 - a device error: the whole group fails, nothing is launched again for it
-            for i, _ in members:
-                fail(i, e)
-            continue
-        for (i, _), o, d in zip(members, out, predictor._param_dicts(raw)):
-            outputs[i], params[i] = o, d
-    return outputs, params
-
 
 # ------------------------------------------------------------------ ParameterPredictor / GatedEnhancementPredictor (N13)
 GATED_PARAM_KEYS = ("gamma", "L_low", "L_high", "use_gamma")  # param_heads order (deep_learning_parameters.py:142-147)
+
+
+def _gated_columns_dict(cols, keys=GATED_PARAM_KEYS):
+    """``{key: its [B,1] column}`` for ``keys`` from a ``[B,4]`` tensor or array whose columns are in the gated module's order
+    (``GatedDifferentiableEnhancement.KEYS``)."""
+    at = {k: i for i, k in enumerate(GatedDifferentiableEnhancement.KEYS)}
+    return {k: cols[:, at[k]:at[k] + 1] for k in keys}
+
+
+def _feature_rows(dev: Device, rows, feature_dim: int, hidden_dim: int, promote_1d: bool = False):
+    """Feature rows for the MLP on ``dev``: float32 or float64 ``[B, feature_dim]`` (NumPy or torch), B >= 1."""
+    if not isinstance(rows, torch.Tensor):
+        rows = torch.from_numpy(np.ascontiguousarray(rows))
+    if rows.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"expected float32 or float64 feature rows, got {rows.dtype}")
+    if promote_1d and rows.dim() == 1:
+        rows = rows[None]
+    if rows.dim() != 2 or rows.shape[1] != feature_dim or rows.shape[0] == 0:
+        raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({'x'.join(str(v) for v in rows.shape)} and "
+                           f"{feature_dim}x{hidden_dim})")
+    return rows.detach().to(dev.torch_device).contiguous()
 
 
 def _predictor_state(state):
@@ -864,7 +859,7 @@ def _predictor_state(state):
     return out, f, h, nb
 
 
-class ParameterPredictor:
+class ParameterPredictor(HandleOwner):
     """``deep_learning_parameters.ParameterPredictor`` (:114-163) in eval mode on the device (k_param_net.hip, DESIGN.md
     section 17).  ``state``: a state dict, the ``nn.Module``, or a checkpoint dict / path with the ``'param_predictor'`` key
     that ``EndToEndTrainer.save_model`` writes; ``feature_dim``, ``hidden_dim`` and ``num_blocks`` come from the tensors'
@@ -876,53 +871,31 @@ class ParameterPredictor:
     def __init__(self, state, device: int | None = None):
         self._state, self.feature_dim, self.hidden_dim, self.num_blocks = _predictor_state(state)
         self.device = device
-        self._handles = {}
         if device is not None:
             self._handle(get_device(device))
-
-    def close(self):
-        for index, h in list(self._handles.items()):
-            get_device(index).mlp_destroy(h)
-        self._handles.clear()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
 
     def state_dict(self):
         return dict(self._state)
 
-    def _handle(self, dev: Device):
-        if dev.index not in self._handles:
-            flat = torch.cat([t.reshape(-1) for t in self._state.values()])
-            self._handles[dev.index] = dev.mlp_create(flat, self.feature_dim, self.hidden_dim, self.num_blocks)
-        return self._handles[dev.index]
+    def _create_handle(self, dev: Device):
+        flat = torch.cat([t.reshape(-1) for t in self._state.values()])
+        return dev.mlp_create(flat, self.feature_dim, self.hidden_dim, self.num_blocks)
+
+    _destroy_handle = staticmethod(Device.mlp_destroy)
 
     def columns(self, rows, dev: Device | None = None):
         """float32 ``[B,4]`` on the device in the gated module's order (``GatedDifferentiableEnhancement.KEYS``)."""
         dev = dev or get_device(self.device)
-        if not isinstance(rows, torch.Tensor):
-            rows = torch.from_numpy(np.ascontiguousarray(rows))
-        if rows.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"expected float32 or float64 feature rows, got {rows.dtype}")
-        if rows.dim() == 1:
-            rows = rows[None]
-        if rows.dim() != 2 or rows.shape[1] != self.feature_dim or rows.shape[0] == 0:
-            raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({'x'.join(str(v) for v in rows.shape)} and "
-                               f"{self.feature_dim}x{self.hidden_dim})")
-        return dev.mlp_forward(self._handle(dev), rows.detach().to(dev.torch_device), self.hidden_dim)
+        rows = _feature_rows(dev, rows, self.feature_dim, self.hidden_dim, promote_1d=True)
+        return dev.mlp_forward(self._handle(dev), rows, self.hidden_dim)
 
     def forward(self, rows):
-        cols = self.columns(rows)
-        at = {k: i for i, k in enumerate(GatedDifferentiableEnhancement.KEYS)}
-        return {k: cols[:, at[k]:at[k] + 1] for k in GATED_PARAM_KEYS}
+        return _gated_columns_dict(self.columns(rows))
 
     __call__ = forward
 
 
-class GatedEnhancementPredictor:
+class GatedEnhancementPredictor(_FramePredictor):
     """The inference route of ``EndToEndTrainer``'s stack (deep_learning_parameters.py) on the device, the counterpart of
     ``EnhancementPredictor``: ``FeatureExtractor`` rows -> ``ParameterPredictor`` -> the gated ``DifferentiableEnhancement``.
     ``state`` as for ``ParameterPredictor`` (``feature_dim`` 79).  Frames are uint8 RGB, or float images equal to
@@ -945,10 +918,6 @@ class GatedEnhancementPredictor:
         self.enhancer.device = device
         self.criterion = ReferenceLoss(0.5, 0.5, device=device)
 
-    @staticmethod
-    def _frames(img, dev: Device):
-        return EnhancementPredictor._frames(img, dev)
-
     def _cols(self, dev: Device, u8):
         """The network's float32 [B,4] (gated order) for uint8 frames on the device."""
         rows = dev.feature_extractor(u8)
@@ -966,8 +935,7 @@ class GatedEnhancementPredictor:
         u8, single = self._frames(frames, dev)
         raw = self._cols(dev, u8).double().cpu().numpy()
         dev.check_status()
-        at = {k: i for i, k in enumerate(GatedDifferentiableEnhancement.KEYS)}
-        params = {k: raw[:, at[k]] for k in GATED_PARAM_KEYS}
+        params = {k: v[:, 0] for k, v in _gated_columns_dict(raw).items()}
         return {k: float(v[0]) for k, v in params.items()} if single else params
 
     def enhance_batch(self, frames):
@@ -983,24 +951,10 @@ class GatedEnhancementPredictor:
         out, _ = dev.diff_gated_u8(u8, cols, want_u8=True, want_f32=False)
         return out, cols, cols
 
-    def enhance_batch_u8(self, frames):
-        """``(out_u8 [B,H,W,3] uint8 on the device, params float32 [B,4] = L_low, L_high, use_gamma, gamma)``; ``out_u8``
-        equals ``(enhance_batch(frames) * 255).to(uint8)``.  No host read: ``Device.check_status`` reports an unindexable
-        sorted position (the network's ranges leave none)."""
-        dev = get_device(self.device)
-        u8, _ = self._frames(frames, dev)
-        out, cols, _ = self._batch_u8(dev, u8)
-        return out, cols
-
     @staticmethod
     def _param_dicts(raw):
-        at = {k: i for i, k in enumerate(GatedDifferentiableEnhancement.KEYS)}
-        return [{k: float(row[at[k]]) for k in GATED_PARAM_KEYS} for row in np.asarray(raw, dtype=np.float64)]
-
-    def process_frames(self, frames, filenames=None):
-        """``EnhancementPredictor.process_frames`` for this stack: ``(outputs, params)`` in input order, frames of equal
-        shape in one ``enhance_batch_u8`` call per shape, a failing frame does not stop the others."""
-        return _process_frames(self, frames, filenames)
+        cols = _gated_columns_dict(np.asarray(raw, dtype=np.float64))
+        return [{k: float(v[r, 0]) for k, v in cols.items()} for r in range(len(raw))]
 
     def validate_batch(self, images, references, features=None):
         """``EndToEndTrainer.validate``'s loop body (:316-329) for one batch: ``images`` / ``references`` float32
@@ -1033,15 +987,10 @@ class _TrainerPredictor:
         dev = dev or get_device(self.device)
         return dev.mlp_trainer_eval(self._trainer._handle, self._trainer._rows(dev, rows), self.hidden_dim)
 
-    def forward(self, rows):
-        cols = self.columns(rows)
-        at = {k: i for i, k in enumerate(GatedDifferentiableEnhancement.KEYS)}
-        return {k: cols[:, at[k]:at[k] + 1] for k in GATED_PARAM_KEYS}
-
-    __call__ = forward
+    forward = __call__ = ParameterPredictor.forward
 
 
-class EndToEndTrainer:
+class EndToEndTrainer(HandleOwner):
     """``deep_learning_parameters.EndToEndTrainer`` (:253-349) on the device (k_mlp_train.hip).
     ``state_or_predictor``: a ``uw.ParameterPredictor`` or anything it takes (a state dict, the module, a checkpoint or its
     path).  The trainer owns the weights, their gradients and Adam's moments on the GPU; the reference's hyperparameters are
@@ -1069,24 +1018,20 @@ class EndToEndTrainer:
         self.max_norm, self.dropout, self.seed = float(max_norm), float(dropout), int(seed)
         dev = get_device(device)
         self._index = dev.index
-        self._handle = dev.mlp_trainer_create(torch.cat([t.reshape(-1) for t in state.values()]), self.feature_dim, self.hidden_dim,
-                                              self.num_blocks)
+        flat = torch.cat([t.reshape(-1) for t in state.values()])
+        self._handles = {(dev.index,): (dev, dev.mlp_trainer_create(flat, self.feature_dim, self.hidden_dim, self.num_blocks))}
         self.param_predictor = _TrainerPredictor(self)
         self.enhancement = GatedDifferentiableEnhancement()
         self.enhancement.device = device
         self.criterion = ReferenceLoss(0.5, 0.5, device=device)
         self._grad_loss = dev.tensor(np.array([0.5, 0.5], dtype=np.float32))  # d loss / d l1, d loss / d l2 (:190)
 
-    def close(self):
-        if getattr(self, "_handle", None) is not None:
-            get_device(self._index).mlp_trainer_destroy(self._handle)
-            self._handle = None
+    _destroy_handle = staticmethod(Device.mlp_trainer_destroy)
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
+    @property
+    def _handle(self):
+        """the one uwie_mlp_trainer, made by ``__init__`` from the initial state; None after ``close()``"""
+        return next(iter(self._handles.values()), (None, None))[1]
 
     @property
     def step_count(self) -> int:
@@ -1167,14 +1112,7 @@ class EndToEndTrainer:
 
     # ---- the step
     def _rows(self, dev: Device, rows):
-        if not isinstance(rows, torch.Tensor):
-            rows = torch.from_numpy(np.ascontiguousarray(rows))
-        if rows.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"expected float32 or float64 feature rows, got {rows.dtype}")
-        if rows.dim() != 2 or rows.shape[1] != self.feature_dim or rows.shape[0] == 0:
-            raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({'x'.join(str(v) for v in rows.shape)} and "
-                               f"{self.feature_dim}x{self.hidden_dim})")
-        return rows.detach().to(dev.torch_device).contiguous()
+        return _feature_rows(dev, rows, self.feature_dim, self.hidden_dim)
 
     def _features(self, dev: Device, x, features):
         if features is None:

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import check
+from .runtime import HandleOwner
 
 KIND_RF, KIND_GB, KIND_SVC = 0, 1, 2  # include/uwie.h UWIE_MODEL_*
 KIND_NAMES = {KIND_RF: "RandomForestClassifier", KIND_GB: "GradientBoostingClassifier", KIND_SVC: "SVC"}
@@ -191,7 +192,7 @@ def _json_value(v):
     return v.tolist() if hasattr(v, "tolist") else list(v)
 
 
-class StrategyClassifier:
+class StrategyClassifier(HandleOwner):
     """A fitted strategy classifier (main.py:225-335 trains it, :398-433 predicts with it) run on the device.
 
     ``clf.predict(frames)`` is main.py's ``predict`` for one frame or a batch; ``predict_rows`` classifies given feature
@@ -213,7 +214,6 @@ class StrategyClassifier:
         rc = model_check(self.arrays)
         if rc != 0:
             raise ValueError(f"invalid model: {_lib.load().uwie_last_error().decode()}")
-        self._models = {}  # device index -> uwie_model handle
 
     # ------------------------------------------------------------------ construction
     @classmethod
@@ -245,28 +245,17 @@ class StrategyClassifier:
         return cls(arrays, strategies)
 
     # ------------------------------------------------------------------ device
-    def _model(self, dev):
-        h = self._models.get(dev.index)
-        if h is None:
-            m, _keep = model_desc(self.arrays)
-            h = ctypes.c_void_p()
-            check(dev.lib.uwie_model_create(dev._ctx, ctypes.byref(m), ctypes.byref(h)))
-            self._models[dev.index] = h
+    def _create_handle(self, dev):
+        m, _keep = model_desc(self.arrays)
+        h = ctypes.c_void_p()
+        check(dev.lib.uwie_model_create(dev._ctx, ctypes.byref(m), ctypes.byref(h)))
         return h
 
-    def close(self):
-        from .runtime import get_device
+    @staticmethod
+    def _destroy_handle(dev, handle):
+        dev._net_destroy(dev.lib.uwie_model_destroy, handle)
 
-        for index, h in list(self._models.items()):
-            torch.cuda.synchronize(index)
-            get_device(index).lib.uwie_model_destroy(h)
-        self._models.clear()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
+    _model = HandleOwner._handle  # the uwie_model of this classifier on ``dev``
 
     def _raise_nan(self, labels_h):
         bad = np.flatnonzero(labels_h < 0)

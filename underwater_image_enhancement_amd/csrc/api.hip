@@ -3,6 +3,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "common.h"
 
@@ -531,6 +532,92 @@ static size_t float_ws_bytes(int batch, int H, int W, const uwie_params *p)
     Carver c(nullptr);
     carve_float<T>(c, Shape{batch, H, W}, p);
     return c.total();
+}
+
+// ---------------------------------------------------------------- the learned stack's handles
+// A handle's device made current for a scope and the previous one put back; nothing when it is current already or the
+// query fails.  (The handle's functions that take no context: *_destroy, uwie_mlp_trainer_get / _set.)
+class DeviceGuard {
+public:
+    explicit DeviceGuard(int device)
+        : switched_(hipGetDevice(&prev_) == hipSuccess && prev_ != device && hipSetDevice(device) == hipSuccess)
+    {
+    }
+    ~DeviceGuard()
+    {
+        if (switched_) (void)hipSetDevice(prev_);
+    }
+    DeviceGuard(const DeviceGuard &) = delete;
+
+private:
+    int prev_ = -1;  // declared (so initialised) before switched_
+    bool switched_;
+};
+
+// uwie_vgg, uwie_param_net, uwie_mlp and uwie_model: a network of device pointers into one allocation on `device`
+template <class Net>
+struct Handle {
+    int device;
+    Net net;
+    void *blob;
+};
+
+template <class H>
+void handle_destroy(H *h)
+{
+    if (!h) return;
+    DeviceGuard on(h->device);
+    (void)hipFree(h->blob);
+    delete h;
+}
+
+// The end of every *_create (who): rc of the pack on the null stream, then its completion.  On either failure `cleanup`
+// runs, and a HIP error becomes the message.
+template <class F>
+int pack_finish(int rc, const char *who, F cleanup, const char *what = "packing failed: ")
+{
+    const hipError_t e = rc == UWIE_OK ? hipStreamSynchronize(nullptr) : hipSuccess;
+    if (rc == UWIE_OK && e == hipSuccess) return UWIE_OK;
+    cleanup();
+    if (e != hipSuccess) set_error("%s: %s%s", who, what, hipGetErrorString(e));
+    return rc != UWIE_OK ? rc : UWIE_E_HIP;
+}
+
+#define UWIE_REQUIRE_F(cond, ...)       \
+    do {                                \
+        if (!(cond)) {                  \
+            set_error(__VA_ARGS__);     \
+            return UWIE_E_INVALID;      \
+        }                               \
+    } while (0)
+
+// What the entry points that take rows of an MLP share, in their order: NULL pointers, the device of the handle (a
+// uwie_mlp, "the network", or a uwie_mlp_trainer), the batch (an eval forward takes more rows than a training step keeps
+// activations for), the alignment of the rows and of the float32 array `d_other` that goes with them.
+constexpr int kMlpEvalBatch = 1 << 20, kMlpTrainBatch = 65536;
+template <class H>
+int mlp_rows_check(const char *who, const uwie_ctx *ctx, const H *h, const void *d_features, int features_are_f64, int batch,
+                   bool training, const float *d_other, const char *other_name)
+{
+    UWIE_REQUIRE_F(ctx && h && d_features && d_other, "%s: NULL pointer", who);
+    UWIE_REQUIRE_F(h->device == ctx->device, "%s: the %s lives on another device", who,
+                   std::is_same<H, uwie_mlp>::value ? "network" : "trainer");
+    UWIE_REQUIRE_F(batch >= 1 && batch <= (training ? kMlpTrainBatch : kMlpEvalBatch), "%s: batch out of range (1 .. %s)", who,
+                   training ? "65536" : "2^20");
+    UWIE_REQUIRE_F(((uintptr_t)d_features & (features_are_f64 ? 7 : 3)) == 0 && ((uintptr_t)d_other & 3) == 0,
+                   "%s: d_features and %s must be aligned for their element types", who, other_name);
+    return UWIE_OK;
+}
+
+// The flags of an enhancement module (map: UWIE_LOSS_VGG, or UWIE_LOSS_GATED whose flags are reserved) and what the entry
+// point `who` says about bad ones; ReferenceLoss, which takes either module, names it as well.
+bool module_flags_ok(int map, int flags) { return map == UWIE_LOSS_VGG ? (flags & ~3) == 0 : flags == 0; }
+int module_flags_check(const char *who, int map, int flags, bool name_module = false)
+{
+    const bool vgg = map == UWIE_LOSS_VGG;
+    UWIE_REQUIRE_F(module_flags_ok(map, flags), "%s: %sflags are %s", who, !name_module ? "" : vgg ? "vgg " : "gated ",
+                   vgg ? "UWIE_DIFF_OMEGA | UWIE_DIFF_GAMMA" : "reserved (0)");
+    return UWIE_OK;
 }
 
 }  // namespace
@@ -1086,10 +1173,13 @@ static int module_select(uwie_ctx *ctx, int map, const float *d_img, int planar,
     return UWIE_OK;
 }
 
-// a module forward after its entry point's own checks (d_saved: the _save_f32 form)
-static int module_fwd(uwie_ctx *ctx, int map, const float *d_img, float *d_out, int batch, int H, int W, int planar,
+// a module forward after its entry point's NULL check (who: the entry point in messages; d_saved: the _save_f32 form)
+static int module_fwd(const char *who, uwie_ctx *ctx, int map, const float *d_img, float *d_out, int batch, int H, int W, int planar,
                       const float *d_params, int flags, float *d_saved, void *d_workspace, size_t workspace_bytes, void *stream)
 {
+    UWIE_SCOPE(ctx);
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_TRY(module_flags_check(who, map, flags));
     const Shape s{batch, H, W};
     UWIE_CHECK_WS(select_ws_bytes(s));
     hipStream_t st = (hipStream_t)stream;
@@ -1099,27 +1189,48 @@ static int module_fwd(uwie_ctx *ctx, int map, const float *d_img, float *d_out, 
     return launch_diff_gated(d_img, planar ? 1 : 0, s, d_params, os, d_out, st, d_saved);
 }
 
-// a module backward after its entry point's NULL, shape and flags checks: alias is that entry point's message
-static int module_bwd(int map, const float *d_img, const float *d_params, int flags, int planar, int batch, int H, int W,
-                      const float *d_saved, const float *d_grad_out, float *d_grad_img, float *d_grad_params, const char *alias,
+// a module backward after its entry point's NULL check
+static int module_bwd(const char *who, uwie_ctx *ctx, int map, const float *d_img, const float *d_params, int flags, int planar,
+                      int batch, int H, int W, const float *d_saved, const float *d_grad_out, float *d_grad_img, float *d_grad_params,
                       void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    UWIE_REQUIRE((const void *)d_grad_img != (const void *)d_img && (const void *)d_grad_img != (const void *)d_grad_out, alias);
+    UWIE_SCOPE(ctx);
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_TRY(module_flags_check(who, map, flags));
+    UWIE_REQUIRE_F((const void *)d_grad_img != (const void *)d_img && (const void *)d_grad_img != (const void *)d_grad_out,
+                   "%s: d_grad_img must not alias d_img or d_grad_out", who);
     const Shape s{batch, H, W};
     UWIE_CHECK_WS(diff_enhance_bwd_ws_bytes(s));
     return launch_module_bwd(map, d_img, planar ? 1 : 0, s, d_params, flags, d_saved, nullptr, d_grad_out, nullptr, d_grad_img,
                              d_grad_params, d_workspace, (hipStream_t)stream);
 }
 
+// a module for u8 frames in the byte domain (k_diff_u8.hip).  Every argument check needs no device and runs ahead of the scope.
+static int module_u8(const char *who, uwie_ctx *ctx, int map, const uint8_t *d_in, uint8_t *d_out_u8, float *d_out_f32, int batch,
+                     int H, int W, const float *d_params, int flags, float *d_saved, void *d_workspace, size_t workspace_bytes,
+                     void *stream)
+{
+    const bool gated = map == UWIE_LOSS_GATED;
+    UWIE_REQUIRE_F(ctx && d_in && d_params, "%s: NULL pointer", who);
+    UWIE_REQUIRE_F(d_out_u8 || d_out_f32, "%s: at least one of d_out_u8, d_out_f32", who);
+    UWIE_REQUIRE_F(((uintptr_t)d_in & 3) == 0, "%s: d_in must be 4-byte aligned", who);  // k_frame_hist reads dwords
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_REQUIRE_F(!gated || batch <= 65535, "%s: batch is at most 65535", who);  // k_dg8_table's grid: one row per image
+    UWIE_TRY(module_flags_check(who, map, flags));
+    const Shape s{batch, H, W};
+    UWIE_CHECK_WS(gated ? diff_gated_u8_ws_bytes(batch) : diff_u8_ws_bytes(s));
+    UWIE_SCOPE(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    if (gated) return launch_diff_gated_u8(d_in, s, d_params, ctx->d_status, d_out_u8, d_out_f32, d_saved, d_workspace, st);
+    return launch_diff_enhance_u8(d_in, s, d_params, flags, d_out_u8, d_out_f32, d_saved, d_workspace, st);
+}
+
 int uwie_diff_enhance_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, int planar,
                           const float *d_params, int flags, void *d_workspace, size_t workspace_bytes, void *stream)
 {
     UWIE_REQUIRE(ctx && d_img && d_out && d_params, "diff_enhance: NULL pointer");
-    UWIE_SCOPE(ctx);
-    UWIE_CHECK_SHAPE(batch, H, W);
-    UWIE_REQUIRE((flags & ~3) == 0, "diff_enhance: flags are UWIE_DIFF_OMEGA | UWIE_DIFF_GAMMA");
-    return module_fwd(ctx, UWIE_LOSS_VGG, d_img, d_out, batch, H, W, planar, d_params, flags, nullptr, d_workspace, workspace_bytes,
-                      stream);
+    return module_fwd("diff_enhance", ctx, UWIE_LOSS_VGG, d_img, d_out, batch, H, W, planar, d_params, flags, nullptr, d_workspace,
+                      workspace_bytes, stream);
 }
 
 int uwie_diff_enhance_save_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, int planar,
@@ -1127,11 +1238,8 @@ int uwie_diff_enhance_save_f32(uwie_ctx *ctx, const float *d_img, float *d_out, 
                                void *stream)
 {
     UWIE_REQUIRE(ctx && d_img && d_out && d_params && d_saved, "diff_enhance_save: NULL pointer");
-    UWIE_SCOPE(ctx);
-    UWIE_CHECK_SHAPE(batch, H, W);
-    UWIE_REQUIRE((flags & ~3) == 0, "diff_enhance_save: flags are UWIE_DIFF_OMEGA | UWIE_DIFF_GAMMA");
-    return module_fwd(ctx, UWIE_LOSS_VGG, d_img, d_out, batch, H, W, planar, d_params, flags, d_saved, d_workspace, workspace_bytes,
-                      stream);
+    return module_fwd("diff_enhance_save", ctx, UWIE_LOSS_VGG, d_img, d_out, batch, H, W, planar, d_params, flags, d_saved,
+                      d_workspace, workspace_bytes, stream);
 }
 
 size_t uwie_diff_enhance_bwd_workspace_bytes(int batch, int H, int W)
@@ -1145,11 +1253,8 @@ int uwie_diff_enhance_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_
                               float *d_grad_params, void *d_workspace, size_t workspace_bytes, void *stream)
 {
     UWIE_REQUIRE(ctx && d_img && d_params && d_saved && d_grad_out && d_grad_params, "diff_enhance_bwd: NULL pointer");
-    UWIE_SCOPE(ctx);
-    UWIE_CHECK_SHAPE(batch, H, W);
-    UWIE_REQUIRE((flags & ~3) == 0, "diff_enhance_bwd: flags are UWIE_DIFF_OMEGA | UWIE_DIFF_GAMMA");
-    return module_bwd(UWIE_LOSS_VGG, d_img, d_params, flags, planar, batch, H, W, d_saved, d_grad_out, d_grad_img, d_grad_params,
-                      "diff_enhance_bwd: d_grad_img must not alias d_img or d_grad_out", d_workspace, workspace_bytes, stream);
+    return module_bwd("diff_enhance_bwd", ctx, UWIE_LOSS_VGG, d_img, d_params, flags, planar, batch, H, W, d_saved, d_grad_out,
+                      d_grad_img, d_grad_params, d_workspace, workspace_bytes, stream);
 }
 
 size_t uwie_workspace_bytes_diff_u8(int batch, int H, int W)
@@ -1161,15 +1266,8 @@ size_t uwie_workspace_bytes_diff_u8(int batch, int H, int W)
 int uwie_diff_enhance_u8(uwie_ctx *ctx, const uint8_t *d_in, uint8_t *d_out_u8, float *d_out_f32, int batch, int H, int W,
                          const float *d_params, int flags, float *d_saved, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    UWIE_REQUIRE(ctx && d_in && d_params, "diff_enhance_u8: NULL pointer");
-    UWIE_REQUIRE(d_out_u8 || d_out_f32, "diff_enhance_u8: at least one of d_out_u8, d_out_f32");
-    UWIE_REQUIRE(((uintptr_t)d_in & 3) == 0, "diff_enhance_u8: d_in must be 4-byte aligned");  // k_frame_hist reads dwords
-    UWIE_CHECK_SHAPE(batch, H, W);
-    UWIE_REQUIRE((flags & ~3) == 0, "diff_enhance_u8: flags are UWIE_DIFF_OMEGA | UWIE_DIFF_GAMMA");
-    const Shape s{batch, H, W};
-    UWIE_CHECK_WS(diff_u8_ws_bytes(s));
-    UWIE_SCOPE(ctx);  // every argument check above needs no device
-    return launch_diff_enhance_u8(d_in, s, d_params, flags, d_out_u8, d_out_f32, d_saved, d_workspace, (hipStream_t)stream);
+    return module_u8("diff_enhance_u8", ctx, UWIE_LOSS_VGG, d_in, d_out_u8, d_out_f32, batch, H, W, d_params, flags, d_saved,
+                     d_workspace, workspace_bytes, stream);
 }
 
 size_t uwie_workspace_bytes_diff_gated_u8(int batch)
@@ -1181,27 +1279,16 @@ size_t uwie_workspace_bytes_diff_gated_u8(int batch)
 int uwie_diff_gated_u8(uwie_ctx *ctx, const uint8_t *d_in, uint8_t *d_out_u8, float *d_out_f32, int batch, int H, int W,
                        const float *d_params, int flags, float *d_saved, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    UWIE_REQUIRE(ctx && d_in && d_params, "diff_gated_u8: NULL pointer");
-    UWIE_REQUIRE(d_out_u8 || d_out_f32, "diff_gated_u8: at least one of d_out_u8, d_out_f32");
-    UWIE_REQUIRE(((uintptr_t)d_in & 3) == 0, "diff_gated_u8: d_in must be 4-byte aligned");  // k_frame_hist reads dwords
-    UWIE_CHECK_SHAPE(batch, H, W);
-    UWIE_REQUIRE(batch <= 65535, "diff_gated_u8: batch is at most 65535");  // one grid row per image
-    UWIE_REQUIRE(flags == 0, "diff_gated_u8: flags are reserved (0)");
-    UWIE_CHECK_WS(diff_gated_u8_ws_bytes(batch));
-    UWIE_SCOPE(ctx);  // every argument check above needs no device
-    return launch_diff_gated_u8(d_in, Shape{batch, H, W}, d_params, ctx->d_status, d_out_u8, d_out_f32, d_saved, d_workspace,
-                                (hipStream_t)stream);
+    return module_u8("diff_gated_u8", ctx, UWIE_LOSS_GATED, d_in, d_out_u8, d_out_f32, batch, H, W, d_params, flags, d_saved,
+                     d_workspace, workspace_bytes, stream);
 }
 
 int uwie_diff_gated_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, int planar,
                         const float *d_params, int flags, void *d_workspace, size_t workspace_bytes, void *stream)
 {
     UWIE_REQUIRE(ctx && d_img && d_out && d_params, "diff_gated: NULL pointer");
-    UWIE_SCOPE(ctx);
-    UWIE_CHECK_SHAPE(batch, H, W);
-    UWIE_REQUIRE(flags == 0, "diff_gated: flags are reserved (0)");
-    return module_fwd(ctx, UWIE_LOSS_GATED, d_img, d_out, batch, H, W, planar, d_params, 0, nullptr, d_workspace, workspace_bytes,
-                      stream);
+    return module_fwd("diff_gated", ctx, UWIE_LOSS_GATED, d_img, d_out, batch, H, W, planar, d_params, flags, nullptr, d_workspace,
+                      workspace_bytes, stream);
 }
 
 int uwie_diff_gated_save_f32(uwie_ctx *ctx, const float *d_img, float *d_out, int batch, int H, int W, int planar,
@@ -1209,11 +1296,8 @@ int uwie_diff_gated_save_f32(uwie_ctx *ctx, const float *d_img, float *d_out, in
                              void *stream)
 {
     UWIE_REQUIRE(ctx && d_img && d_out && d_params && d_saved, "diff_gated_save: NULL pointer");
-    UWIE_SCOPE(ctx);
-    UWIE_CHECK_SHAPE(batch, H, W);
-    UWIE_REQUIRE(flags == 0, "diff_gated_save: flags are reserved (0)");
-    return module_fwd(ctx, UWIE_LOSS_GATED, d_img, d_out, batch, H, W, planar, d_params, 0, d_saved, d_workspace, workspace_bytes,
-                      stream);
+    return module_fwd("diff_gated_save", ctx, UWIE_LOSS_GATED, d_img, d_out, batch, H, W, planar, d_params, flags, d_saved,
+                      d_workspace, workspace_bytes, stream);
 }
 
 size_t uwie_diff_gated_bwd_workspace_bytes(int batch, int H, int W)
@@ -1226,11 +1310,8 @@ int uwie_diff_gated_bwd_f32(uwie_ctx *ctx, const float *d_img, const float *d_pa
                             void *d_workspace, size_t workspace_bytes, void *stream)
 {
     UWIE_REQUIRE(ctx && d_img && d_params && d_saved && d_grad_out && d_grad_params, "diff_gated_bwd: NULL pointer");
-    UWIE_SCOPE(ctx);
-    UWIE_CHECK_SHAPE(batch, H, W);
-    UWIE_REQUIRE(flags == 0, "diff_gated_bwd: flags are reserved (0)");
-    return module_bwd(UWIE_LOSS_GATED, d_img, d_params, 0, planar, batch, H, W, d_saved, d_grad_out, d_grad_img, d_grad_params,
-                      "diff_gated_bwd: d_grad_img must not alias d_img or d_grad_out", d_workspace, workspace_bytes, stream);
+    return module_bwd("diff_gated_bwd", ctx, UWIE_LOSS_GATED, d_img, d_params, flags, planar, batch, H, W, d_saved, d_grad_out,
+                      d_grad_img, d_grad_params, d_workspace, workspace_bytes, stream);
 }
 
 // ReferenceLoss: the forward workspace holds the selection and the loss partials; the backward's is the module backward's
@@ -1255,9 +1336,7 @@ static int ref_loss_check_map(int map, const float *d_params, const float *d_sav
                  "ref_loss: map is UWIE_LOSS_IDENTITY, UWIE_LOSS_VGG or UWIE_LOSS_GATED");
     if (map == UWIE_LOSS_IDENTITY) return UWIE_OK;
     UWIE_REQUIRE(d_params && d_saved, "ref_loss: NULL pointer (d_params, d_saved)");
-    if (map == UWIE_LOSS_VGG) UWIE_REQUIRE((flags & ~3) == 0, "ref_loss: vgg flags are UWIE_DIFF_OMEGA | UWIE_DIFF_GAMMA");
-    else UWIE_REQUIRE(flags == 0, "ref_loss: gated flags are reserved (0)");
-    return UWIE_OK;
+    return module_flags_check("ref_loss", map, flags, true);
 }
 
 int uwie_ref_loss_f32(uwie_ctx *ctx, int map, const float *d_img, const float *d_params, int flags, int planar, int batch, int H,
@@ -1307,11 +1386,7 @@ int uwie_ref_loss_bwd_f32(uwie_ctx *ctx, int map, const float *d_img, const floa
 }
 
 // PerceptualLoss (k_vgg.hip)
-struct uwie_vgg {
-    int device;
-    VggNet net;  // device pointers into blob
-    void *blob;
-};
+struct uwie_vgg : Handle<VggNet> {};
 
 static bool perceptual_shape_ok(int batch, int H, int W)
 {
@@ -1332,26 +1407,12 @@ int uwie_vgg_create(uwie_ctx *ctx, const float *d_params, int precision, uwie_vg
     void *blob = nullptr;
     UWIE_HIP_CHECK(hipMalloc(&blob, vgg_blob_bytes(precision)));
     VggNet net{};
-    int rc = vgg_pack(d_params, precision, blob, &net, nullptr);
-    hipError_t e = rc == UWIE_OK ? hipStreamSynchronize(nullptr) : hipSuccess;
-    if (rc != UWIE_OK || e != hipSuccess) {
-        (void)hipFree(blob);
-        if (e != hipSuccess) set_error("vgg_create: packing failed: %s", hipGetErrorString(e));
-        return rc != UWIE_OK ? rc : UWIE_E_HIP;
-    }
-    *out_vgg = new uwie_vgg{ctx->device, net, blob};
+    UWIE_TRY(pack_finish(vgg_pack(d_params, precision, blob, &net, nullptr), "vgg_create", [&] { (void)hipFree(blob); }));
+    *out_vgg = new uwie_vgg{{ctx->device, net, blob}};
     return UWIE_OK;
 }
 
-void uwie_vgg_destroy(uwie_vgg *vgg)
-{
-    if (!vgg) return;
-    int prev = -1;
-    const bool switch_dev = hipGetDevice(&prev) == hipSuccess && prev != vgg->device && hipSetDevice(vgg->device) == hipSuccess;
-    (void)hipFree(vgg->blob);
-    if (switch_dev) (void)hipSetDevice(prev);
-    delete vgg;
-}
+void uwie_vgg_destroy(uwie_vgg *vgg) { handle_destroy(vgg); }
 
 size_t uwie_perceptual_workspace_bytes(int batch, int H, int W, int precision)
 {
@@ -1393,11 +1454,7 @@ int uwie_perceptual_bwd_f32(uwie_ctx *ctx, const uwie_vgg *vgg, int batch, int H
 }
 
 // ImprovedVGGParameterNet (k_param_net.hip)
-struct uwie_param_net {
-    int device;
-    ParamNet net;  // device pointers into blob
-    void *blob;
-};
+struct uwie_param_net : Handle<ParamNet> {};
 
 static bool param_net_shape_ok(int batch, int H, int W)
 {
@@ -1423,27 +1480,15 @@ int uwie_param_net_create(uwie_ctx *ctx, const float *d_params, int use_features
         return UWIE_E_HIP;
     }
     ParamNet net{};
-    const int rc = param_net_pack(d_params, uf, blob, static_cast<float *>(scratch), &net, nullptr);
-    e = rc == UWIE_OK ? hipStreamSynchronize(nullptr) : hipSuccess;
+    const int rc = pack_finish(param_net_pack(d_params, uf, blob, static_cast<float *>(scratch), &net, nullptr),
+                               "param_net_create", [&] { (void)hipFree(blob); });
     (void)hipFree(scratch);  // the data-gradient copy of conv4_x: not needed for inference
-    if (rc != UWIE_OK || e != hipSuccess) {
-        (void)hipFree(blob);
-        if (e != hipSuccess) set_error("param_net_create: packing failed: %s", hipGetErrorString(e));
-        return rc != UWIE_OK ? rc : UWIE_E_HIP;
-    }
-    *out_net = new uwie_param_net{ctx->device, net, blob};
+    UWIE_TRY(rc);
+    *out_net = new uwie_param_net{{ctx->device, net, blob}};
     return UWIE_OK;
 }
 
-void uwie_param_net_destroy(uwie_param_net *net)
-{
-    if (!net) return;
-    int prev = -1;
-    const bool switch_dev = hipGetDevice(&prev) == hipSuccess && prev != net->device && hipSetDevice(net->device) == hipSuccess;
-    (void)hipFree(net->blob);
-    if (switch_dev) (void)hipSetDevice(prev);
-    delete net;
-}
+void uwie_param_net_destroy(uwie_param_net *net) { handle_destroy(net); }
 
 size_t uwie_param_net_workspace_bytes(int batch, int H, int W)
 {
@@ -1469,11 +1514,7 @@ int uwie_param_net_f32(uwie_ctx *ctx, const uwie_param_net *net, const float *d_
 }
 
 // ParameterPredictor (k_param_net.hip)
-struct uwie_mlp {
-    int device;
-    Mlp net;  // device pointers into blob
-    void *blob;
-};
+struct uwie_mlp : Handle<Mlp> {};
 
 static bool mlp_dims_ok(int F, int Hd, int nb)
 {
@@ -1490,44 +1531,34 @@ int uwie_mlp_create(uwie_ctx *ctx, const float *d_params, int feature_dim, int h
     void *blob = nullptr;
     UWIE_HIP_CHECK(hipMalloc(&blob, mlp_count(feature_dim, hidden_dim, num_blocks) * sizeof(float)));
     Mlp net{};
-    const int rc = mlp_pack(d_params, feature_dim, hidden_dim, num_blocks, static_cast<float *>(blob), &net, nullptr);
-    const hipError_t e = rc == UWIE_OK ? hipStreamSynchronize(nullptr) : hipSuccess;
-    if (rc != UWIE_OK || e != hipSuccess) {
-        (void)hipFree(blob);
-        if (e != hipSuccess) set_error("mlp_create: packing failed: %s", hipGetErrorString(e));
-        return rc != UWIE_OK ? rc : UWIE_E_HIP;
-    }
-    *out_net = new uwie_mlp{ctx->device, net, blob};
+    UWIE_TRY(pack_finish(mlp_pack(d_params, feature_dim, hidden_dim, num_blocks, static_cast<float *>(blob), &net, nullptr),
+                         "mlp_create", [&] { (void)hipFree(blob); }));
+    *out_net = new uwie_mlp{{ctx->device, net, blob}};
     return UWIE_OK;
 }
 
-void uwie_mlp_destroy(uwie_mlp *net)
-{
-    if (!net) return;
-    int prev = -1;
-    const bool switch_dev = hipGetDevice(&prev) == hipSuccess && prev != net->device && hipSetDevice(net->device) == hipSuccess;
-    (void)hipFree(net->blob);
-    if (switch_dev) (void)hipSetDevice(prev);
-    delete net;
-}
+void uwie_mlp_destroy(uwie_mlp *net) { handle_destroy(net); }
 
 size_t uwie_mlp_workspace_bytes(int batch, int hidden_dim)
 {
-    if (batch < 1 || batch > (1 << 20) || !mlp_dims_ok(1, hidden_dim, 0)) return 0;
+    if (batch < 1 || batch > kMlpEvalBatch || !mlp_dims_ok(1, hidden_dim, 0)) return 0;
     return mlp_ws_bytes(batch, hidden_dim);
+}
+
+// the eval forward of a network or of a trainer's current parameters
+static int mlp_eval(const Mlp &net, uwie_ctx *ctx, const void *d_features, int features_are_f64, int batch, float *d_out,
+                    void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    UWIE_CHECK_WS(mlp_ws_bytes(batch, net.H));
+    UWIE_SCOPE(ctx);
+    return launch_mlp(net, d_features, features_are_f64 != 0, batch, d_out, d_workspace, (hipStream_t)stream);
 }
 
 int uwie_mlp_forward(uwie_ctx *ctx, const uwie_mlp *net, const void *d_features, int features_are_f64, int batch, float *d_out,
                      void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    UWIE_REQUIRE(ctx && net && d_features && d_out, "mlp_forward: NULL pointer");
-    UWIE_REQUIRE(net->device == ctx->device, "mlp_forward: the network lives on another device");
-    UWIE_REQUIRE(batch >= 1 && batch <= (1 << 20), "mlp_forward: batch out of range (1 .. 2^20)");
-    UWIE_REQUIRE(((uintptr_t)d_features & (features_are_f64 ? 7 : 3)) == 0 && ((uintptr_t)d_out & 3) == 0,
-                 "mlp_forward: d_features and d_out must be aligned for their element types");
-    UWIE_CHECK_WS(mlp_ws_bytes(batch, net->net.H));
-    UWIE_SCOPE(ctx);
-    return launch_mlp(net->net, d_features, features_are_f64 != 0, batch, d_out, d_workspace, (hipStream_t)stream);
+    UWIE_TRY(mlp_rows_check("mlp_forward", ctx, net, d_features, features_are_f64, batch, false, d_out, "d_out"));
+    return mlp_eval(net->net, ctx, d_features, features_are_f64, batch, d_out, d_workspace, workspace_bytes, stream);
 }
 
 // EndToEndTrainer's training step (k_mlp_train.hip)
@@ -1565,16 +1596,13 @@ int uwie_mlp_trainer_create(uwie_ctx *ctx, const float *d_params, int feature_di
         if (e == hipSuccess && i > 0) e = hipMemset(tr->arrays[i], 0, bytes);
     }
     if (e == hipSuccess) e = hipMalloc((void **)&tr->partial, mlp_adam_scratch_bytes());
-    int rc = UWIE_OK;
-    if (e == hipSuccess) {
-        rc = mlp_pack(d_params, feature_dim, hidden_dim, num_blocks, tr->arrays[UWIE_TRAINER_PARAMS], &tr->net, nullptr);
-        if (rc == UWIE_OK) e = hipStreamSynchronize(nullptr);
-    }
-    if (rc != UWIE_OK || e != hipSuccess) {
+    if (e != hipSuccess) {
         trainer_free(tr);
-        if (e != hipSuccess) set_error("mlp_trainer_create: %s", hipGetErrorString(e));
-        return rc != UWIE_OK ? rc : UWIE_E_HIP;
+        set_error("mlp_trainer_create: %s", hipGetErrorString(e));
+        return UWIE_E_HIP;
     }
+    UWIE_TRY(pack_finish(mlp_pack(d_params, feature_dim, hidden_dim, num_blocks, tr->arrays[UWIE_TRAINER_PARAMS], &tr->net, nullptr),
+                         "mlp_trainer_create", [&] { trainer_free(tr); }, ""));
     *out_trainer = tr;
     return UWIE_OK;
 }
@@ -1582,13 +1610,11 @@ int uwie_mlp_trainer_create(uwie_ctx *ctx, const float *d_params, int feature_di
 void uwie_mlp_trainer_destroy(uwie_mlp_trainer *trainer)
 {
     if (!trainer) return;
-    int prev = -1;
-    const bool switch_dev = hipGetDevice(&prev) == hipSuccess && prev != trainer->device && hipSetDevice(trainer->device) == hipSuccess;
+    DeviceGuard on(trainer->device);
     trainer_free(trainer);
-    if (switch_dev) (void)hipSetDevice(prev);
 }
 
-static bool train_batch_ok(int batch) { return batch >= 1 && batch <= 65536; }
+static bool train_batch_ok(int batch) { return batch >= 1 && batch <= kMlpTrainBatch; }
 
 size_t uwie_mlp_train_workspace_bytes(int batch, int hidden_dim, int num_blocks)
 {
@@ -1600,11 +1626,7 @@ int uwie_mlp_train_forward(uwie_ctx *ctx, uwie_mlp_trainer *trainer, const void 
                            int mask_mode, uint8_t *d_masks, uint64_t seed, float *d_out, void *d_workspace, size_t workspace_bytes,
                            void *stream)
 {
-    UWIE_REQUIRE(ctx && trainer && d_features && d_out, "mlp_train_forward: NULL pointer");
-    UWIE_REQUIRE(trainer->device == ctx->device, "mlp_train_forward: the trainer lives on another device");
-    UWIE_REQUIRE(train_batch_ok(batch), "mlp_train_forward: batch out of range (1 .. 65536)");
-    UWIE_REQUIRE(((uintptr_t)d_features & (features_are_f64 ? 7 : 3)) == 0 && ((uintptr_t)d_out & 3) == 0,
-                 "mlp_train_forward: d_features and d_out must be aligned for their element types");
+    UWIE_TRY(mlp_rows_check("mlp_train_forward", ctx, trainer, d_features, features_are_f64, batch, true, d_out, "d_out"));
     UWIE_REQUIRE(p >= 0.0 && p < 1.0, "mlp_train_forward: the dropout rate p must lie in [0, 1)");
     UWIE_REQUIRE(mask_mode == UWIE_MASKS_GIVEN || mask_mode == UWIE_MASKS_DRAWN, "mlp_train_forward: mask_mode is UWIE_MASKS_GIVEN or UWIE_MASKS_DRAWN");
     UWIE_REQUIRE(mask_mode == UWIE_MASKS_DRAWN || p == 0.0 || d_masks, "mlp_train_forward: given masks need d_masks");
@@ -1625,11 +1647,7 @@ int uwie_mlp_train_forward(uwie_ctx *ctx, uwie_mlp_trainer *trainer, const void 
 int uwie_mlp_backward(uwie_ctx *ctx, uwie_mlp_trainer *trainer, const void *d_features, int features_are_f64, int batch,
                       const float *d_grad_out, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    UWIE_REQUIRE(ctx && trainer && d_features && d_grad_out, "mlp_backward: NULL pointer");
-    UWIE_REQUIRE(trainer->device == ctx->device, "mlp_backward: the trainer lives on another device");
-    UWIE_REQUIRE(train_batch_ok(batch), "mlp_backward: batch out of range (1 .. 65536)");
-    UWIE_REQUIRE(((uintptr_t)d_features & (features_are_f64 ? 7 : 3)) == 0 && ((uintptr_t)d_grad_out & 3) == 0,
-                 "mlp_backward: d_features and d_grad_out must be aligned for their element types");
+    UWIE_TRY(mlp_rows_check("mlp_backward", ctx, trainer, d_features, features_are_f64, batch, true, d_grad_out, "d_grad_out"));
     UWIE_REQUIRE(trainer->fwd_batch == batch, "mlp_backward: no uwie_mlp_train_forward of this batch precedes it");
     const Mlp &net = trainer->net;
     UWIE_CHECK_WS(mlp_train_ws_bytes(batch, net.H, net.nb));
@@ -1665,8 +1683,7 @@ static int trainer_copy(uwie_mlp_trainer *tr, int which, float *d_buf, bool get,
         set_error("%s: NULL or misaligned pointer, or which outside UWIE_TRAINER_PARAMS .. UWIE_TRAINER_EXP_AVG_SQ", who);
         return UWIE_E_INVALID;
     }
-    int prev = -1;
-    const bool switch_dev = hipGetDevice(&prev) == hipSuccess && prev != tr->device && hipSetDevice(tr->device) == hipSuccess;
+    DeviceGuard on(tr->device);
     const Mlp &n = tr->net;
     hipError_t e = hipDeviceSynchronize();  // work on other streams that reads or writes the arrays
     int rc = UWIE_OK;
@@ -1675,7 +1692,6 @@ static int trainer_copy(uwie_mlp_trainer *tr, int which, float *d_buf, bool get,
                  : mlp_repack(d_buf, tr->arrays[which], n.F, n.H, n.nb, false, nullptr);
         if (rc == UWIE_OK) e = hipStreamSynchronize(nullptr);
     }
-    if (switch_dev) (void)hipSetDevice(prev);
     if (e != hipSuccess) {
         set_error("%s: %s", who, hipGetErrorString(e));
         return UWIE_E_HIP;
@@ -1706,14 +1722,8 @@ int uwie_mlp_trainer_set_step_count(uwie_mlp_trainer *trainer, long long step)
 int uwie_mlp_trainer_eval(uwie_ctx *ctx, const uwie_mlp_trainer *trainer, const void *d_features, int features_are_f64, int batch,
                           float *d_out, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    UWIE_REQUIRE(ctx && trainer && d_features && d_out, "mlp_trainer_eval: NULL pointer");
-    UWIE_REQUIRE(trainer->device == ctx->device, "mlp_trainer_eval: the trainer lives on another device");
-    UWIE_REQUIRE(batch >= 1 && batch <= (1 << 20), "mlp_trainer_eval: batch out of range (1 .. 2^20)");
-    UWIE_REQUIRE(((uintptr_t)d_features & (features_are_f64 ? 7 : 3)) == 0 && ((uintptr_t)d_out & 3) == 0,
-                 "mlp_trainer_eval: d_features and d_out must be aligned for their element types");
-    UWIE_CHECK_WS(mlp_ws_bytes(batch, trainer->net.H));
-    UWIE_SCOPE(ctx);
-    return launch_mlp(trainer->net, d_features, features_are_f64 != 0, batch, d_out, d_workspace, (hipStream_t)stream);
+    UWIE_TRY(mlp_rows_check("mlp_trainer_eval", ctx, trainer, d_features, features_are_f64, batch, false, d_out, "d_out"));
+    return mlp_eval(trainer->net, ctx, d_features, features_are_f64, batch, d_out, d_workspace, workspace_bytes, stream);
 }
 
 int uwie_u8_to_f32(uwie_ctx *ctx, const uint8_t *d_in, float *d_out, size_t n, void *stream)
@@ -1776,11 +1786,7 @@ int uwie_feature_extractor_u8(uwie_ctx *ctx, const uint8_t *d_u8, const float *d
 }
 
 // ---------------------------------------------------------------- strategy classifier (k_classify.hip)
-struct uwie_model {
-    int device;
-    ClsModel m;  // device pointers into blob
-    void *blob;
-};
+struct uwie_model : Handle<ClsModel> {};
 
 int uwie_model_check(const uwie_model_desc *desc) { return classify_model_check(desc); }
 
@@ -1806,26 +1812,18 @@ int uwie_model_create(uwie_ctx *ctx, const uwie_model_desc *desc, uwie_model **o
         set_error("model_create: upload of %zu bytes failed: %s", bytes, hipGetErrorString(e));
         return UWIE_E_HIP;
     }
-    *out_model = new uwie_model{ctx->device, m, blob};
+    *out_model = new uwie_model{{ctx->device, m, blob}};
     return UWIE_OK;
 }
 
-void uwie_model_destroy(uwie_model *model)
-{
-    if (!model) return;
-    int prev = -1;
-    const bool switch_dev = hipGetDevice(&prev) == hipSuccess && prev != model->device && hipSetDevice(model->device) == hipSuccess;
-    (void)hipFree(model->blob);
-    if (switch_dev) (void)hipSetDevice(prev);
-    delete model;
-}
+void uwie_model_destroy(uwie_model *model) { handle_destroy(model); }
 
 int uwie_model_info(const uwie_model *model, int *kind, int *n_classes, int *n_features)
 {
     UWIE_REQUIRE(model != nullptr, "model_info: NULL model");
-    if (kind) *kind = model->m.kind;
-    if (n_classes) *n_classes = model->m.C;
-    if (n_features) *n_features = model->m.F;
+    if (kind) *kind = model->net.kind;
+    if (n_classes) *n_classes = model->net.C;
+    if (n_features) *n_features = model->net.F;
     return UWIE_OK;
 }
 
@@ -1835,12 +1833,12 @@ int uwie_classify_f64(uwie_ctx *ctx, const uwie_model *model, const double *d_ro
     UWIE_REQUIRE(ctx && model && d_rows && d_label && d_proba, "classify: NULL pointer");
     UWIE_REQUIRE(model->device == ctx->device, "classify: the model lives on another device");
     UWIE_REQUIRE(batch >= 1 && batch <= (1 << 24), "classify: batch must be 1..2^24");
-    if (n_features != model->m.F) {
-        set_error("classify: rows have %d features, the model expects %d", n_features, model->m.F);
+    if (n_features != model->net.F) {
+        set_error("classify: rows have %d features, the model expects %d", n_features, model->net.F);
         return UWIE_E_INVALID;
     }
     UWIE_SCOPE(ctx);
-    return launch_classify(model->m, d_rows, batch, d_label, d_proba, ctx->d_status, (hipStream_t)stream);
+    return launch_classify(model->net, d_rows, batch, d_label, d_proba, ctx->d_status, (hipStream_t)stream);
 }
 
 size_t uwie_workspace_bytes_predict(int batch, int H, int W)
@@ -1864,8 +1862,8 @@ int uwie_predict_strategy_u8(uwie_ctx *ctx, const uwie_model *model, const uint8
     UWIE_REQUIRE(batch <= 65535, "predict: batch must be <= 65535");
     UWIE_REQUIRE(gray_shift == 14 || gray_shift == 15, "gray_shift must be 14 or 15");
     const int n = feature_extractor_count(H, W);
-    if (n != model->m.F) {
-        set_error("predict: a %dx%d frame gives %d feature values, the model expects %d", H, W, n, model->m.F);
+    if (n != model->net.F) {
+        set_error("predict: a %dx%d frame gives %d feature values, the model expects %d", H, W, n, model->net.F);
         return UWIE_E_INVALID;
     }
     const Shape s{batch, H, W};
@@ -1876,7 +1874,7 @@ int uwie_predict_strategy_u8(uwie_ctx *ctx, const uwie_model *model, const uint8
     if (d_rows) rows = d_rows;
     hipStream_t st = (hipStream_t)stream;
     UWIE_TRY(launch_feature_extractor(ctx, d_u8, d_f32, s, gray_shift, rows, fx_ws, st));
-    return launch_classify(model->m, rows, batch, d_label, d_proba, ctx->d_status, st);
+    return launch_classify(model->net, rows, batch, d_label, d_proba, ctx->d_status, st);
 }
 
 int uwie_resize_rgb_u8(uwie_ctx *ctx, const uwie_frame_desc *d_desc, int batch, int out_h, int out_w, const uint8_t *d_flips,

@@ -417,12 +417,12 @@ int select_begin_gated_ranks(Shape s, const float *d_params, int stride, uint32_
 // d_saved (optional): [B][3][2] float = {p_lo, p_hi} per plane, what the backward needs from the forward
 int launch_diff_enhance(const float *d_img, int planar, Shape s, const float *d_params, int flags, const float *d_os,
                         float *d_out, hipStream_t st, float *d_saved = nullptr);
-// k_diffenh_u8.hip: the same module from the frame's bytes (histogram -> the two bins -> per-block stretch tables -> apply);
+// k_diff_u8.hip: the same module from the frame's bytes (histogram -> the two bins -> per-block stretch tables -> apply);
 // d_out_u8 / d_out_f32 / d_saved optional (at least one output), ws: diff_u8_ws_bytes
 size_t diff_u8_ws_bytes(Shape s);
 int launch_diff_enhance_u8(const uint8_t *d_in, Shape s, const float *d_params, int flags, uint8_t *d_out_u8, float *d_out_f32,
                            float *d_saved, void *ws, hipStream_t st);
-// k_diffgated_u8.hip: the gated module for u8 frames in the byte domain: per image a 3 x 256 table.
+// k_diff_u8.hip: the gated module for u8 frames in the byte domain: per image a 3 x 256 table.
 // d_out_u8 / d_out_f32 / d_saved optional (at least one output), ws: diff_gated_u8_ws_bytes (independent of H x W)
 size_t diff_gated_u8_ws_bytes(int B);
 int launch_diff_gated_u8(const uint8_t *d_in, Shape s, const float *d_params, uint32_t *d_status, uint8_t *d_out_u8,

@@ -168,7 +168,7 @@ __device__ __forceinline__ float pow_f32_fast(float x, float g)
 }
 
 // vgg_16_UIE.DifferentiableEnhancement.forward per pixel (k_diffenh.hip's vgg_px), in two halves so that the float32
-// kernels and the byte-domain ones (k_diffenh_u8.hip, which tabulates the first half per byte value) share one source:
+// kernels and the byte-domain ones (k_diff_u8.hip, which tabulates the first half per byte value) share one source:
 //   vgg_stretch        clamp((x - p_low) / (p_high - p_low + 1e-8), 0, 1) of one channel value
 //   vgg_after_stretch  [UWIE_DIFF_OMEGA] dehaze with A = 0.6 -> [UWIE_DIFF_GAMMA] pow(v + 1e-8, gamma) -> clamp(0, 1), in place.
 //                      fmaxf(NaN, 0) = 0: the final clamp leaves no NaN behind
@@ -191,7 +191,7 @@ __device__ __forceinline__ void vgg_after_stretch(float (&v)[3], float omega, fl
 }
 
 // deep_learning_parameters.DifferentiableEnhancement.forward (:44-54) for one channel value, the source of k_diff_gated, the
-// fused loss sweeps (k_diffenh.hip) and the byte-domain table (k_diffgated_u8.hip): s = clamp((x - p_low) / rng, 0, 1) with
+// fused loss sweeps (k_diffenh.hip) and the byte-domain table (k_diff_u8.hip): s = clamp((x - p_low) / rng, 0, 1) with
 // rng = p_high - p_low + 1e-8, z = pow(s + 1e-8, e) with e = 1.0f / gamma, clamp(u * z + om * s, 0, 1) with om = 1 - u.
 // ok = false (no valid sorted position) gives NaN.
 __device__ __forceinline__ float gated_px(float x, float lo, float rng, float u, float e, float om, bool ok)
@@ -335,6 +335,21 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v)
         if (lane >= o) v += t;
     }
     return v;
+}
+
+// 16-byte accesses at an address aligned only for its element type: the copy through a local lets the compiler emit one
+// global_load / store_dwordx4 (gfx950 takes unaligned addresses) without a cast that promises more alignment than there is
+template <typename V, typename T>
+__device__ __forceinline__ V load16(const T *p)
+{
+    V v;
+    __builtin_memcpy(&v, p, sizeof(V));
+    return v;
+}
+template <typename V, typename T>
+__device__ __forceinline__ void store16(T *p, const V &v)
+{
+    __builtin_memcpy(p, &v, sizeof(V));
 }
 
 }  // namespace uwie

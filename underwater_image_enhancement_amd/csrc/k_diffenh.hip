@@ -29,7 +29,7 @@ namespace {
 // The per-pixel forwards, shared by the inference kernels and the loss sweep (k_refloss_*): the clamp masks of the loss
 // backward recompute these values, so both must see the same bits.
 // vgg: v = clamp(stretch -> [dehaze] -> [gamma]) of one pixel's three channels (flags: UWIE_DIFF_OMEGA | UWIE_DIFF_GAMMA);
-// the two halves are in devutil.h, where the byte-domain kernels (k_diffenh_u8.hip) take them from too
+// the two halves are in devutil.h, where the byte-domain kernels (k_diff_u8.hip) take them from too
 __device__ __forceinline__ void vgg_px(const float (&x)[3], const float (&lo)[3], const float (&rng)[3], float omega, float gamma,
                                        int flags, float (&v)[3])
 {
@@ -38,7 +38,7 @@ __device__ __forceinline__ void vgg_px(const float (&x)[3], const float (&lo)[3]
     vgg_after_stretch(v, omega, gamma, flags);
 }
 
-// gated: gated_px (devutil.h), one channel value; the byte-domain table (k_diffgated_u8.hip) compiles the same source
+// gated: gated_px (devutil.h), one channel value; the byte-domain table (k_diff_u8.hip) compiles the same source
 
 // planar: img/out [B][3][n];  interleaved: [B][n][3].  os: [B*3][kSelOsStride] floats, entries 0/1 = p_low, p_high.
 __global__ void __launch_bounds__(256) k_diff_enhance(const float *__restrict__ img, int planar, int n,

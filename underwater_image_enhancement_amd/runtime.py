@@ -21,7 +21,17 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
-class Device:
+class _ClosedOnDel:
+    """``close()`` when the object is collected; at interpreter shutdown what ``close()`` needs may be gone already."""
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+class Device(_ClosedOnDel):
     """A libuwie context bound to one MI355X.  Not thread-safe; use one per host thread / stream."""
 
     def __init__(self, device: int = 0):
@@ -42,12 +52,6 @@ class Device:
             self.lib.uwie_destroy(self._ctx)
             self._ctx = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
-
     # ------------------------------------------------------------------ plumbing
     def stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.index).cuda_stream)
@@ -67,11 +71,16 @@ class Device:
             setattr(p, key, value)
         return p
 
+    def _sized_workspace(self, n: int, message: str, fresh: bool = False):
+        """The workspace for what a uwie_*workspace_bytes function answered: 0 means arguments out of range (``message``).
+        The cached workspace, or with ``fresh`` a tensor of this call's own (one that has to outlive the next call)."""
+        if n == 0:
+            raise _lib.UwieError(message)
+        return torch.empty(int(n), dtype=torch.uint8, device=self.torch_device) if fresh else self.workspace(n)
+
     def workspace_for(self, B, H, W, p: UwieParams | None = None):
         n = self.lib.uwie_workspace_bytes_ctx(self._ctx, B, H, W, ctypes.byref(p) if p is not None else None)
-        if n == 0:
-            raise _lib.UwieError("batch/H/W out of range")
-        return self.workspace(n)
+        return self._sized_workspace(n, "batch/H/W out of range")
 
     def tensor(self, array, dtype=None):
         t = torch.as_tensor(np.ascontiguousarray(array))
@@ -287,26 +296,28 @@ class Device:
         return self._module_bwd(self.lib.uwie_diff_enhance_bwd_f32, self.lib.uwie_diff_enhance_bwd_workspace_bytes, img, params,
                                 saved, grad_out, planar, flags, want_img)
 
-    def diff_enhance_u8(self, u8, cols, flags: int = 3, want_u8: bool = True, want_f32: bool = False, saved: bool = False):
-        """The module in the byte domain (uwie_diff_enhance_u8, DESIGN.md section 16).  u8: uint8 cuda tensor [B,H,W,3], the
-        frame whose float image is u8 / 255; cols: float32 [B,4] = L_low, L_high, omega, gamma.  Returns (out_u8 or None =
-        (uint8)(v * 255) of the module's output v, out_f32 or None = v, the bits diff_enhance_f32 gives for u8_to_f32(u8)),
-        and with ``saved`` a third item, float32 [B,3,2] as diff_enhance_save_f32 returns it."""
+    def _module_u8(self, fn, ws_bytes, ws_message: str, u8, cols, flags: int, want_u8: bool, want_f32: bool, saved: bool):
+        """A module in the byte domain (fn = uwie_diff_*_u8, ws_bytes = its workspace size for (B, H, W))."""
         assert u8.dtype == torch.uint8
         u8 = u8.contiguous()
         B, H, W = self._bhw(u8)
         assert cols.dtype == torch.float32 and tuple(cols.shape) == (B, 4)
         cols = cols.contiguous()
-        n = self.lib.uwie_workspace_bytes_diff_u8(B, H, W)
-        if n == 0:
-            raise _lib.UwieError("batch/H/W out of range")
-        ws = self.workspace(n)
+        ws = self._sized_workspace(ws_bytes(B, H, W), ws_message)
         out_u8 = self.empty((B, H, W, 3), torch.uint8) if want_u8 else None
         out_f32 = self.empty((B, H, W, 3), torch.float32) if want_f32 else None
         sv = self.empty((B, 3, 2), torch.float32) if saved else None
-        check(self.lib.uwie_diff_enhance_u8(self._ctx, _ptr(u8), _ptr(out_u8), _ptr(out_f32), B, H, W, _ptr(cols), int(flags),
-                                            _ptr(sv), _ptr(ws), ws.numel(), self.stream()))
+        check(fn(self._ctx, _ptr(u8), _ptr(out_u8), _ptr(out_f32), B, H, W, _ptr(cols), int(flags), _ptr(sv), _ptr(ws), ws.numel(),
+                 self.stream()))
         return (out_u8, out_f32, sv) if saved else (out_u8, out_f32)
+
+    def diff_enhance_u8(self, u8, cols, flags: int = 3, want_u8: bool = True, want_f32: bool = False, saved: bool = False):
+        """The module in the byte domain (uwie_diff_enhance_u8, DESIGN.md section 16).  u8: uint8 cuda tensor [B,H,W,3], the
+        frame whose float image is u8 / 255; cols: float32 [B,4] = L_low, L_high, omega, gamma.  Returns (out_u8 or None =
+        (uint8)(v * 255) of the module's output v, out_f32 or None = v, the bits diff_enhance_f32 gives for u8_to_f32(u8)),
+        and with ``saved`` a third item, float32 [B,3,2] as diff_enhance_save_f32 returns it."""
+        return self._module_u8(self.lib.uwie_diff_enhance_u8, self.lib.uwie_workspace_bytes_diff_u8, "batch/H/W out of range",
+                               u8, cols, flags, want_u8, want_f32, saved)
 
     def diff_gated_f32(self, img, params, planar: bool):
         """deep_learning_parameters.DifferentiableEnhancement's forward (uwie_diff_gated_f32): img float32 cuda [B,3,H,W]
@@ -330,21 +341,8 @@ class Device:
         (uint8)(v * 255) of the module's output v, out_f32 or None = v, the bits diff_gated_f32 gives for u8_to_f32(u8)), and
         with ``saved`` a third item, float32 [B,3,2] as diff_gated_save_f32 returns it.  An image without a valid sorted
         position gets NaN / 0 and sets UWIE_STATUS_DIFF_RANK (check_status)."""
-        assert u8.dtype == torch.uint8
-        u8 = u8.contiguous()
-        B, H, W = self._bhw(u8)
-        assert cols.dtype == torch.float32 and tuple(cols.shape) == (B, 4)
-        cols = cols.contiguous()
-        n = self.lib.uwie_workspace_bytes_diff_gated_u8(B)
-        if n == 0:
-            raise _lib.UwieError("batch out of range")
-        ws = self.workspace(n)
-        out_u8 = self.empty((B, H, W, 3), torch.uint8) if want_u8 else None
-        out_f32 = self.empty((B, H, W, 3), torch.float32) if want_f32 else None
-        sv = self.empty((B, 3, 2), torch.float32) if saved else None
-        check(self.lib.uwie_diff_gated_u8(self._ctx, _ptr(u8), _ptr(out_u8), _ptr(out_f32), B, H, W, _ptr(cols), 0, _ptr(sv),
-                                          _ptr(ws), ws.numel(), self.stream()))
-        return (out_u8, out_f32, sv) if saved else (out_u8, out_f32)
+        return self._module_u8(self.lib.uwie_diff_gated_u8, lambda B, H, W: self.lib.uwie_workspace_bytes_diff_gated_u8(B),
+                               "batch out of range", u8, cols, 0, want_u8, want_f32, saved)
 
     # ------------------------------------------------------------------ ReferenceLoss (uwie_ref_loss_*, DESIGN.md section 13)
     def ref_loss_f32(self, map_: int, img, params, ref, planar: bool, flags: int = 0, want_out: bool = False,
@@ -383,19 +381,26 @@ class Device:
         return grad_img, grad_params
 
     # ------------------------------------------------------------------ PerceptualLoss (uwie_perceptual_*)
+    def _net_create(self, fn, params, count: int, *args):
+        """A handle from fn = uwie_*_create(ctx, the ``count`` flat float32 parameters, *args, &handle).  The caller owns it."""
+        flat = params.to(device=self.torch_device, dtype=torch.float32).contiguous()
+        assert flat.numel() == count
+        torch.cuda.synchronize(self.index)  # the packing runs on the null stream
+        handle = ctypes.c_void_p()
+        check(fn(self._ctx, _ptr(flat), *args, ctypes.byref(handle)))
+        return handle
+
+    def _net_destroy(self, fn, handle):
+        torch.cuda.synchronize(self.index)  # work in flight may still read the handle's arrays
+        fn(handle)
+
     def vgg_create(self, params, precision: int):
         """A uwie_vgg handle of ``precision`` (_lib.VGG_F32 / VGG_F16) from torchvision's 14 tensors flattened in features.N
         order (float32, _lib.VGG_PARAMS values).  The caller owns it (vgg_destroy)."""
-        flat = params.to(device=self.torch_device, dtype=torch.float32).contiguous()
-        assert flat.numel() == _lib.VGG_PARAMS
-        torch.cuda.synchronize(self.index)  # the packing runs on the null stream
-        h = ctypes.c_void_p()
-        check(self.lib.uwie_vgg_create(self._ctx, _ptr(flat), int(precision), ctypes.byref(h)))
-        return h
+        return self._net_create(self.lib.uwie_vgg_create, params, _lib.VGG_PARAMS, int(precision))
 
     def vgg_destroy(self, handle):
-        torch.cuda.synchronize(self.index)
-        self.lib.uwie_vgg_destroy(handle)
+        self._net_destroy(self.lib.uwie_vgg_destroy, handle)
 
     def perceptual_f32(self, vgg, precision: int, pred, target):
         """mse_loss(F(pred), F(target)) on the device.  Returns (buf float32 [1] = the loss, ws = this call's workspace, which
@@ -404,10 +409,8 @@ class Device:
         assert pred.dtype == torch.float32 and target.dtype == torch.float32 and pred.dim() == 4 and pred.shape[1] == 3
         assert tuple(pred.shape) == tuple(target.shape)
         B, _, H, W = (int(v) for v in pred.shape)
-        n = self.lib.uwie_perceptual_workspace_bytes(B, H, W, int(precision))
-        if n == 0:
-            raise _lib.UwieError(f"perceptual: batch/H/W out of range ({B}, {H}, {W})")
-        ws = torch.empty(int(n), dtype=torch.uint8, device=self.torch_device)
+        ws = self._sized_workspace(self.lib.uwie_perceptual_workspace_bytes(B, H, W, int(precision)),
+                                   f"perceptual: batch/H/W out of range ({B}, {H}, {W})", fresh=True)
         buf = self.empty((1,), torch.float32)
         check(self.lib.uwie_perceptual_f32(self._ctx, vgg, _ptr(pred.contiguous()), _ptr(target.contiguous()), B, H, W, _ptr(buf),
                                            _ptr(ws), ws.numel(), self.stream()))
@@ -426,16 +429,11 @@ class Device:
     def param_net_create(self, params, use_features: bool):
         """A uwie_param_net handle from the state dict's float tensors flattened in state-dict order (float32,
         _lib.PARAM_NET_PARAMS[use_features] values; include/uwie.h lists the order).  The caller owns it (param_net_destroy)."""
-        flat = params.to(device=self.torch_device, dtype=torch.float32).contiguous()
-        assert flat.numel() == _lib.PARAM_NET_PARAMS[bool(use_features)]
-        torch.cuda.synchronize(self.index)  # the packing runs on the null stream
-        h = ctypes.c_void_p()
-        check(self.lib.uwie_param_net_create(self._ctx, _ptr(flat), int(bool(use_features)), ctypes.byref(h)))
-        return h
+        return self._net_create(self.lib.uwie_param_net_create, params, _lib.PARAM_NET_PARAMS[bool(use_features)],
+                                int(bool(use_features)))
 
     def param_net_destroy(self, handle):
-        torch.cuda.synchronize(self.index)
-        self.lib.uwie_param_net_destroy(handle)
+        self._net_destroy(self.lib.uwie_param_net_destroy, handle)
 
     def param_net_f32(self, net, img, features=None, want_pooled: bool = False):
         """The eval-mode forward: img float32 cuda [B,3,H,W], features float32 cuda [B,79] or None.  Returns (float32 [B,4] =
@@ -445,10 +443,8 @@ class Device:
         if features is not None:
             assert features.dtype == torch.float32 and tuple(features.shape) == (B, 79)
             features = features.contiguous()
-        n = self.lib.uwie_param_net_workspace_bytes(B, H, W)
-        if n == 0:
-            raise _lib.UwieError(f"param_net: batch/H/W out of range ({B}, {H}, {W})")
-        ws = torch.empty(int(n), dtype=torch.uint8, device=self.torch_device)
+        ws = self._sized_workspace(self.lib.uwie_param_net_workspace_bytes(B, H, W),
+                                   f"param_net: batch/H/W out of range ({B}, {H}, {W})", fresh=True)
         out = self.empty((B, 4), torch.float32)
         pooled = self.empty((B, 1024), torch.float32) if want_pooled else None
         check(self.lib.uwie_param_net_f32(self._ctx, net, _ptr(img.contiguous()), _ptr(features), B, H, W, _ptr(out), _ptr(pooled),
@@ -456,56 +452,51 @@ class Device:
         return out, pooled
 
     # ------------------------------------------------------------------ ParameterPredictor (uwie_mlp_*)
+    @staticmethod
+    def mlp_param_count(feature_dim: int, hidden_dim: int, num_blocks: int) -> int:
+        """The values of a ParameterPredictor's state_dict(): input layer, the blocks' two layers each, the neck, four heads."""
+        f, h, half = int(feature_dim), int(hidden_dim), int(hidden_dim) // 2
+        return f * h + h + int(num_blocks) * 2 * (h * h + h) + half * h + half + 4 * (half + 1)
+
+    def _mlp_create(self, fn, params, feature_dim: int, hidden_dim: int, num_blocks: int):
+        dims = (int(feature_dim), int(hidden_dim), int(num_blocks))
+        return self._net_create(fn, params, self.mlp_param_count(*dims), *dims)
+
     def mlp_create(self, params, feature_dim: int, hidden_dim: int, num_blocks: int):
         """A uwie_mlp handle from the state dict's tensors flattened in state_dict() order (float32; include/uwie.h lists
         the order).  The caller owns it (mlp_destroy)."""
-        flat = params.to(device=self.torch_device, dtype=torch.float32).contiguous()
-        h, half = int(hidden_dim), int(hidden_dim) // 2
-        assert flat.numel() == int(feature_dim) * h + h + int(num_blocks) * 2 * (h * h + h) + half * h + half + 4 * (half + 1)
-        torch.cuda.synchronize(self.index)  # the packing runs on the null stream
-        handle = ctypes.c_void_p()
-        check(self.lib.uwie_mlp_create(self._ctx, _ptr(flat), int(feature_dim), h, int(num_blocks), ctypes.byref(handle)))
-        return handle
+        return self._mlp_create(self.lib.uwie_mlp_create, params, feature_dim, hidden_dim, num_blocks)
 
     def mlp_destroy(self, handle):
-        torch.cuda.synchronize(self.index)
-        self.lib.uwie_mlp_destroy(handle)
+        self._net_destroy(self.lib.uwie_mlp_destroy, handle)
+
+    def _mlp_eval(self, fn, who: str, handle, rows, hidden_dim: int):
+        """fn = uwie_mlp_forward or uwie_mlp_trainer_eval on its handle."""
+        assert rows.dtype in (torch.float32, torch.float64) and rows.dim() == 2
+        rows = rows.contiguous()
+        B = int(rows.shape[0])
+        ws = self._sized_workspace(self.lib.uwie_mlp_workspace_bytes(B, int(hidden_dim)), f"{who}: batch out of range ({B})",
+                                   fresh=True)
+        out = self.empty((B, 4), torch.float32)
+        check(fn(self._ctx, handle, _ptr(rows), int(rows.dtype == torch.float64), B, _ptr(out), _ptr(ws), ws.numel(), self.stream()))
+        return out
 
     def mlp_forward(self, net, rows, hidden_dim: int):
         """The eval-mode forward: rows float64 or float32 cuda [B, feature_dim] (float64 is rounded to float32 on load).
         Returns float32 [B,4] = L_low, L_high, use_gamma, gamma.  Sets no status bit."""
-        assert rows.dtype in (torch.float32, torch.float64) and rows.dim() == 2
-        rows = rows.contiguous()
-        B = int(rows.shape[0])
-        n = self.lib.uwie_mlp_workspace_bytes(B, int(hidden_dim))
-        if n == 0:
-            raise _lib.UwieError(f"mlp_forward: batch out of range ({B})")
-        ws = torch.empty(int(n), dtype=torch.uint8, device=self.torch_device)
-        out = self.empty((B, 4), torch.float32)
-        check(self.lib.uwie_mlp_forward(self._ctx, net, _ptr(rows), int(rows.dtype == torch.float64), B, _ptr(out), _ptr(ws),
-                                        ws.numel(), self.stream()))
-        return out
+        return self._mlp_eval(self.lib.uwie_mlp_forward, "mlp_forward", net, rows, hidden_dim)
 
     # ------------------------------------------------------------------ EndToEndTrainer's step (uwie_mlp_trainer_*, DESIGN.md section 18)
     def mlp_trainer_create(self, params, feature_dim: int, hidden_dim: int, num_blocks: int):
         """A uwie_mlp_trainer handle from the flat state_dict()-order parameters, as mlp_create.  The caller owns it."""
-        flat = params.to(device=self.torch_device, dtype=torch.float32).contiguous()
-        h, half = int(hidden_dim), int(hidden_dim) // 2
-        assert flat.numel() == int(feature_dim) * h + h + int(num_blocks) * 2 * (h * h + h) + half * h + half + 4 * (half + 1)
-        torch.cuda.synchronize(self.index)  # the packing runs on the null stream
-        handle = ctypes.c_void_p()
-        check(self.lib.uwie_mlp_trainer_create(self._ctx, _ptr(flat), int(feature_dim), h, int(num_blocks), ctypes.byref(handle)))
-        return handle
+        return self._mlp_create(self.lib.uwie_mlp_trainer_create, params, feature_dim, hidden_dim, num_blocks)
 
     def mlp_trainer_destroy(self, handle):
-        torch.cuda.synchronize(self.index)
-        self.lib.uwie_mlp_trainer_destroy(handle)
+        self._net_destroy(self.lib.uwie_mlp_trainer_destroy, handle)
 
     def mlp_train_workspace(self, B: int, hidden_dim: int, num_blocks: int):
-        n = self.lib.uwie_mlp_train_workspace_bytes(int(B), int(hidden_dim), int(num_blocks))
-        if n == 0:
-            raise _lib.UwieError(f"mlp_train: batch out of range ({B})")
-        return torch.empty(int(n), dtype=torch.uint8, device=self.torch_device)
+        return self._sized_workspace(self.lib.uwie_mlp_train_workspace_bytes(int(B), int(hidden_dim), int(num_blocks)),
+                                     f"mlp_train: batch out of range ({B})", fresh=True)
 
     def mlp_train_forward(self, tr, rows, ws, p: float, masks=None, seed: int = 0, want_masks=None):
         """The train-mode forward: rows as mlp_forward; ws from mlp_train_workspace (the backward reads it).  masks: uint8 cuda
@@ -551,17 +542,7 @@ class Device:
 
     def mlp_trainer_eval(self, tr, rows, hidden_dim: int):
         """mlp_forward on the trainer's current weights."""
-        assert rows.dtype in (torch.float32, torch.float64) and rows.dim() == 2
-        rows = rows.contiguous()
-        B = int(rows.shape[0])
-        n = self.lib.uwie_mlp_workspace_bytes(B, int(hidden_dim))
-        if n == 0:
-            raise _lib.UwieError(f"mlp_trainer_eval: batch out of range ({B})")
-        ws = torch.empty(int(n), dtype=torch.uint8, device=self.torch_device)
-        out = self.empty((B, 4), torch.float32)
-        check(self.lib.uwie_mlp_trainer_eval(self._ctx, tr, _ptr(rows), int(rows.dtype == torch.float64), B, _ptr(out), _ptr(ws),
-                                             ws.numel(), self.stream()))
-        return out
+        return self._mlp_eval(self.lib.uwie_mlp_trainer_eval, "mlp_trainer_eval", tr, rows, hidden_dim)
 
     def u8_to_f32(self, frames):
         """uint8 cuda tensor of any shape -> float32 of that shape, u8.astype(float32) / 255.0 (uwie_u8_to_f32)."""
@@ -849,6 +830,26 @@ class Device:
         check(self.lib.uwie_equalize_hist_u8(self._ctx, _ptr(planes), _ptr(out), B, H, W, _ptr(ws), ws.numel(),
                                              self.stream()))
         return out
+
+
+class HandleOwner(_ClosedOnDel):
+    """What owns device handles of frozen weights (uwie_vgg, uwie_param_net, uwie_mlp, uwie_mlp_trainer, uwie_model): one per
+    key -- the GPU, then whatever else ``_handle`` is given -- made at first use and freed by ``close()``, which ``__del__``
+    runs too.  A subclass says how: ``_create_handle(dev, *key)`` and ``_destroy_handle(dev, handle)``.  Both synchronise
+    the GPU.  After ``close()`` the next use creates again."""
+
+    def _handle(self, dev: Device, *key):
+        handles = self.__dict__.setdefault("_handles", {})  # (GPU index, *key) -> (dev, handle)
+        at = (dev.index,) + key
+        if at not in handles:
+            handles[at] = dev, self._create_handle(dev, *key)
+        return handles[at][1]
+
+    def close(self):
+        handles = self.__dict__.get("_handles", {})
+        while handles:
+            dev, handle = handles.popitem()[1]
+            self._destroy_handle(dev, handle)
 
 
 _devices: dict[int, Device] = {}
