@@ -165,8 +165,10 @@ int uwie_params_init(uwie_params *p, int surface, int strategy);
  *     ranks against the predicted windows; 0: the histogram sweep), q_hist (1: quadtree levels decided from byte histograms where
  *     the score intervals allow; 0: NumPy-order kernels only; 2: histograms taken, never used; 3: both, and every reference-order
  *     score is checked against its interval -- UWIE_STATUS_QTREE_BOUNDS), canny_prepass (1),
- *     streams (1; 2 .. 4 = sub-batches on internal streams), gf_fuse (1: the transmission's first half is evaluated inside the
- *     guided filter for window 15, same float32 operations; 0: k_trans_init writes a t0 plane first),
+ *     streams (1; 2 .. 4 = sub-batches on internal streams), gf_fuse (2: the transmission's first half is evaluated inside the
+ *     guided filter for window 15 (k_guided_split8, same float32 operations, no t0 plane) on jobs that fill the device: strips x bands
+ *     x batch (uwie_guided_fill) at least one round of its compute units x 8; 1: whenever the split plan exists; 0: never,
+ *     k_trans_init writes a t0 plane first),
  *     entry_fuse (1, round 4; SIX surface with cast detection, strategies 1-3, frames whose width is a multiple of 8: the
  *     level-0 quadrant histograms of estimate_atmospheric_light (S6:49-157) are counted by detect_image_type's own pass over
  *     the frame (S6:292) and that pass writes the gray plane (S6:149,177) for a cast kind guessed from 2048 pixels -- frames
@@ -725,6 +727,11 @@ int uwie_guided_filter(uwie_ctx *ctx, const uint8_t *d_gray, const float *d_t0, 
  * For benchmarks that price each kernel by the pixels it covers.  The function has no context: it answers for the DEFAULT
  * tuning (gf_split = 1, gf_bands = 0); a context with other settings runs a different plan. */
 int uwie_guided_plan(int batch, int H, int W, int ksize, int *split_row0, int *split_rows);
+
+/* The strip-wavefronts of that plan: strips x bands x batch, 0 where uwie_guided_plan answers 0 rows.  A strip-wavefront is
+ * one wavefront that filters one band of one 100-column strip (ksize 15); a compute unit holds eight at a time.  Tuning
+ * gf_fuse = 2 holds this number against the device's compute units x 8 (see uwie_set_tuning).  No context, as above. */
+int uwie_guided_fill(int batch, int H, int W, int ksize, long long *items);
 
 /* restore_image (S6:183-188): float32 [batch][H][W][3]. */
 int uwie_restore(uwie_ctx *ctx, const uint8_t *d_in, const int32_t *d_kind, const float *d_A, const double *d_t,

@@ -101,6 +101,7 @@ SIGNATURES = {
     "uwie_cast_classify_f32": [_VP, _VP, _I, _I, _I, _VP, _VP, _VP],
     "uwie_color_correct_f32": [_VP, _VP, _VP, _VP, _I, _I, _I, _VP],
     "uwie_guided_plan": [_I, _I, _I, _I, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
+    "uwie_guided_fill": [_I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)],
     "uwie_enhance_u8": [_VP, _VP, _VP, _VP, _I, _I, _I, _PP, _VP, _SZ, _VP],
     "uwie_enhance_u8_f64": [_VP, _VP, _VP, _VP, _I, _I, _I, _PP, _VP, _SZ, _VP],
     "uwie_enhance_percentiles": [_VP, _VP, _SZ, _I, _I, _I, _PP, _VP, _VP],

@@ -641,10 +641,13 @@ int uwie_create(int device, uwie_ctx **out_ctx)
     }
     UWIE_REQUIRE(device >= 0 && device < count, "device index out of range");
     UWIE_HIP_CHECK(hipSetDevice(device));
+    int cus = 0;
+    UWIE_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
     uwie_ctx *ctx = new uwie_ctx();
     ctx->aux_ready = false;
     ctx->prof = prof_create();
     ctx->device = device;
+    ctx->cus = cus;
     tuning_from_env(&ctx->tune);
     LabTables *lab = new LabTables();
     CastTables *cast = new CastTables();
@@ -1980,6 +1983,16 @@ int uwie_guided_plan(int batch, int H, int W, int ksize, int *split_row0, int *s
     const bool split = g.route == GF_SPLIT;
     *split_row0 = split ? g.iy0 : 0;
     *split_rows = split ? g.rows : 0;
+    return UWIE_OK;
+}
+
+int uwie_guided_fill(int batch, int H, int W, int ksize, long long *items)
+{
+    UWIE_REQUIRE(items, "guided_fill: NULL pointer");
+    UWIE_CHECK_SHAPE(batch, H, W);
+    const Shape s{batch, H, W};
+    const GuidedPlan g = plan_guided(s, {ksize, 1.0});
+    *items = g.route == GF_SPLIT ? guided_items(s, g) : 0;
     return UWIE_OK;
 }
 

@@ -101,7 +101,9 @@ struct Tuning {
     int lin_predict_shift = 0;  // predicted windows moved by this many bins (large: every prediction misses)
     int streams = 1;            // uwie_enhance_u8: sub-batches on this many internal streams (1 .. 4)
     int canny_prepass = 1;      // quadtree: the streaming "any strong pixel?" pass before Canny
-    int gf_fuse = 0;            // ... with t0 computed from the frame's bytes inside it (k_guided_split8: -0.08 ms per 4K x 64 step, opt-in; 0: k_trans_init + t0 plane)
+    int gf_fuse = 2;            // ... with t0 computed from the frame's bytes inside it (k_guided_split8, no k_trans_init and no t0 plane).  0: never;
+                                // 1: whenever eligible; 2: auto -- eligible jobs of at least kFuseRounds rounds of the chip's resident
+                                // strip-wavefronts (plan_guided; 4K x 64: 8.99 - 9.04 ms per step against 9.29 - 9.38)
     int rank_sweep = 1;         // strategies 1-2: the rank-counting restore sweep on jobs of >= 16 MP (0: the histogram sweep; 2: any size)
     int canny_fault_inject = 0; // tests only: k_canny_gradnms leaves out the root labels (the round-3 defect): uwie_device_status must report it
     int entry_fuse = 1;         // frames with W % 8 == 0: the level-0 quadrant histograms come out of cast detection's chunk pass and the
@@ -118,6 +120,7 @@ struct uwie_ctx {
     bool attr_cast_resolve = false;  // k_cast_resolve (the rounding table of every binade: 70 KB),
     int attr_gf_fast = 0;       // k_guided_fast<TH> (bit TH)
     int attr_gf_split8 = 0;     // k_guided_split8<15, double / float> (bits 1 / 2)
+    int cus = 0;                // compute units of the device (uwie_create): what "the job fills the chip" is measured against
     uwie::LabTables *d_lab;
     uwie::CastTables *d_cast;
     uwie::Profiler *prof;
@@ -277,7 +280,7 @@ enum GuidedRoute {
     GF_FAST,   // k_guided_fast<TH>: LDS strips (windows and frames the wavefront kernels do not take)
     GF_PIPE,   // k_guided_pipe: the general wavefront kernel, float64 or fixed-point a/b ring
     GF_SPLIT,  // k_guided_split (+ a k_guided_pipe border launch for even windows): large jobs
-    GF_FUSED,  // k_guided_split8: GF_SPLIT with t0 computed from the frame inside it (tuning gf_fuse)
+    GF_FUSED,  // k_guided_split8: GF_SPLIT with t0 computed from the frame inside it (tuning gf_fuse: chip-filling jobs by default)
 };
 struct GuidedRequest {
     int k;
@@ -302,6 +305,8 @@ struct GuidedPlan {
     int pipe_bands;           // GF_PIPE and GF_SPLIT's border launch: bands per strip of the general kernel
 };
 GuidedPlan plan_guided(Shape s, const GuidedRequest &r);
+// strip-wavefronts of a split plan (strips x bands x images): what tuning gf_fuse = 2 holds against the chip's resident set
+inline long long guided_items(Shape s, const GuidedPlan &g) { return (long long)cdiv(s.W, 128 - 2 * (g.k - 1)) * g.nb * s.B; }
 // t0 from the u8 frame: 1 - omega * min_c(img / (A + norm_eps)), clipped to [0.1, 1] with pre_clip (k_trans_init)
 struct FuseT0Args {
     const uint8_t *rgb;    // [B][H][W][3]

@@ -743,7 +743,8 @@ __device__ __forceinline__ void split_body(const uint8_t *__restrict__ gray, con
 // 2.45 / 2.50 ms against 2.49 / 2.55 -- one load and its row arithmetic less per step.
 #define SPLIT_RAW_G 1
 #endif
-    // (k = 15 without the fused transmission only: k = 10 with its five row buffers and the fused kernel spill with them)
+    // (k = 15 without the fused transmission only: k = 10 with its five row buffers and the fused kernel spill with them -- the
+    // fused kernel, four strips to a workgroup: 256 registers and 21 / 22 spilled for float32 / float64 t, 228 and none without)
     constexpr bool RAWG = SPLIT_RAW_G && RAWREG && K == 15 && !FUSE;
     struct In {
         uint32_t te[2];         // entering raw row: float bits of the two slots
@@ -1157,14 +1158,24 @@ k_guided_split(const uint8_t *__restrict__ gray, const float *__restrict__ t0, T
 // The table is 3 KB: one per wavefront would cost the eighth wavefront of a CU (8 x 19.2 KB of ring and staging lines leave
 // 10 KB), so eight strips share a workgroup and ONE table.  Nothing else is shared: every wavefront keeps its own LDS
 // region and its own pace (one barrier, after the table is filled).  grid (ceil(strips * bands / 8), 1, B), block 512.
+// Then FOUR strips and a table of their own per workgroup, two workgroups per CU (2 x 79 744 B of the 160 KB; block 256, still two
+// wavefronts per SIMD): a CU's two workgroups start and end on their own, so half of it keeps working while the other half
+// drains and refills.  4K x 64, alternating in one run: 2.63 - 2.70 ms per launch against 2.84 - 2.96, the step 8.87 - 8.94 ms
+// against 9.07 - 9.15 (profiles/r05_fuse_variants_ab.txt).  Two strips do not fit four to a CU (165 632 B).
+// Measured and dropped on top of it: the band prologue's 15 rows loaded like the steady loop's on interior strips (a dword and a
+// short of the frame, a short of the guide, instead of four single bytes per slot) -- 8.85 - 8.96 ms, inside the spread.
+#ifndef SPLIT8_WAVES
+#define SPLIT8_WAVES 4  // strips per workgroup: 4 (two workgroups per CU), 8 (one: the first shape, A/B builds)
+#endif
 template <int K, typename TOut>
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
+__global__ void __launch_bounds__(64 * SPLIT8_WAVES) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_guided_split8(const uint8_t *__restrict__ gray, FuseT0Args fz, TOut *__restrict__ tout, SplitGeom g, PipeConsts cs, int nstrips)
 {
     extern __shared__ double2 lds_raw[];
     char *lds = reinterpret_cast<char *>(lds_raw);
     constexpr int per_wave = SplitCfg<K>::lds_bytes;
-    float *tab = reinterpret_cast<float *>(lds + 8 * per_wave);
+    constexpr int NW = SPLIT8_WAVES;
+    float *tab = reinterpret_cast<float *>(lds + NW * per_wave);
     // (readfirstlane: the compiler has to KNOW that the wavefront index is uniform -- strip, band and every row offset derive
     // from it, and a row offset it takes for divergent turns each buffer access into a waterfall loop: 803 loops in the first build)
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
@@ -1180,13 +1191,13 @@ k_guided_split8(const uint8_t *__restrict__ gray, FuseT0Args fz, TOut *__restric
     }
     {
         const int kd = fz.kind ? fz.kind[b] : 0;
-        for (int i = threadIdx.x; i < 768; i += 512) {
+        for (int i = threadIdx.x; i < 768; i += 64 * NW) {
             const int c = i >> 8;
             tab[i] = px_val(i & 255, px_atten(kd, c)) / (fz.A[b * 3 + c] + fz.norm_eps);  // S6:170 / ES:221, as k_trans_init
         }
     }
     __syncthreads();
-    const int item = grp * 8 + wave;
+    const int item = grp * NW + wave;
     if (item >= nstrips * g.nbands) return;  // (wavefront-uniform; no barrier follows)
     const int3 bid = {item % nstrips, item / nstrips, b};
     const int x_lo = bid.x * PipeCfg<K>::NV;
@@ -1201,8 +1212,9 @@ int launch_split8(const uint8_t *d_gray, const FuseT0Args &fz, Shape s, const Pi
                   int y_end, hipStream_t st)
 {
     using C = PipeCfg<K>;
-    constexpr int lds = 8 * SplitCfg<K>::lds_bytes + 768 * 4;
-    static_assert(lds <= 160 * 1024, "eight strips and the table have to fit one CU");
+    constexpr int NW = SPLIT8_WAVES;
+    constexpr int lds = NW * SplitCfg<K>::lds_bytes + 768 * 4;
+    static_assert(8 % NW == 0 && (8 / NW) * lds <= 160 * 1024, "eight strips and their tables have to fit one CU");
 #ifndef UWIE_SPLIT8_FOLD
 #define UWIE_SPLIT8_FOLD 1
 #endif
@@ -1217,7 +1229,7 @@ int launch_split8(const uint8_t *d_gray, const FuseT0Args &fz, Shape s, const Pi
     }
     {
         UWIE_PROF("k_guided_split8", st);
-        hipLaunchKernelGGL((k_guided_split8<K, TOut>), dim3(cdiv((long long)nstrips * nbands, 8), 1, s.B), dim3(512), (size_t)lds, st, d_gray,
+        hipLaunchKernelGGL((k_guided_split8<K, TOut>), dim3(cdiv((long long)nstrips * nbands, NW), 1, s.B), dim3(64 * NW), (size_t)lds, st, d_gray,
                            fz, d_t, g, cs, nstrips);
     }
     UWIE_LAUNCH_CHECK();
@@ -1384,6 +1396,14 @@ int launch_wave(const GuidedPlan &g, const uint8_t *d_gray, const float *d_t0, S
 
 }  // namespace
 
+// Tuning gf_fuse = 2: the fused route from this many rounds of the chip's resident strip-wavefronts (CUs x 8) on.
+// Measured (profiles/gf_bench.py --sweep, profiles/r05_fuse_route_sweep.txt: whole strategy-2 calls, gf_fuse 1 against 0 alternating):
+// the fused route wins at every job of the sweep that has a split plan from 0.91 rounds on (4K x 4: -0.02 ms; 1.83 rounds: -0.03;
+// 3.7: -0.07; 7.3: -0.12; 8.5, the 4K x 64 step: -0.34) and ties at 0.59 rounds (1080p x 10: +0.003 ms).  The crossover lies
+// below one round; a job of less than one round cannot fill the chip with workgroups of four strips, so one round is the rule.
+// 4K and 1080p frames were measured; for other frame sizes the rule is an extrapolation.
+constexpr long long kFuseRounds = 1;
+
 GuidedPlan plan_guided(Shape s, const GuidedRequest &r)
 {
     GuidedPlan g{};
@@ -1409,10 +1429,16 @@ GuidedPlan plan_guided(Shape s, const GuidedRequest &r)
     g.route = GF_PIPE;
     if (!g.ring_fx && tu.gf_split && split_plan(s, r.k, tu.gf_bands, &g.iy0, &g.band, &g.nb, &g.rows)) {
         g.route = GF_SPLIT;
-        // the transmission's first half (S6:170-174) evaluated inside the filter: no t0 plane
+        // the transmission's first half (S6:170-174) evaluated inside the filter: no t0 plane.  gf_fuse = 2 (the default): only
+        // where the job fills the chip -- the fused kernel packs SPLIT8_WAVES strips into a workgroup, so a job of less than a
+        // few rounds of the resident strip-wavefronts (8 per CU) leaves CUs empty that k_guided_split's lone wavefronts reach
         if (r.k == 15 && r.t0_from_frame && !r.fx && tu.gf_fuse) {
-            g.route = GF_FUSED;
-            g.t0 = false;
+            const uwie_ctx *ctx = current_ctx();
+            const long long resident = 8LL * (ctx ? ctx->cus : 0);  // (no context: no device to measure against, the split route)
+            if (tu.gf_fuse == 1 || (tu.gf_fuse == 2 && resident > 0 && guided_items(s, g) >= kFuseRounds * resident)) {
+                g.route = GF_FUSED;
+                g.t0 = false;
+            }
         }
     }
     return g;
