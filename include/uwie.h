@@ -733,6 +733,24 @@ int uwie_guided_plan(int batch, int H, int W, int ksize, int *split_row0, int *s
  * gf_fuse = 2 holds this number against the device's compute units x 8 (see uwie_set_tuning).  No context, as above. */
 int uwie_guided_fill(int batch, int H, int W, int ksize, long long *items);
 
+/* How the CLAHE tail of a call is launched: the fused tail of strategies 1-2 (k_stretch_lab_lut<0|1> + k_clahe_apply_u8 /
+ * k_clahe_apply_f32) and the code-domain tail of strategies 4-6 and dict clahe_enhancement (k_stretch_lab_lut<2> +
+ * k_clahe_apply_codes).  The launchers themselves run on this plan, so a test can ask which route a shape takes.
+ *   tile_w, tile_h   tile size on the frame as OpenCV pads it (both directions as soon as either is ragged: `padded`)
+ *   clip_limit       the integer limit max(int(clip_limit * tile area / 256), 1); 0 for clip_limit <= 0 (no clipping)
+ *   wide_lut         1: the 1024-thread LUT kernel (k_stretch_lab_lut_wide).  Only a recomputed source has it
+ *                    (`recomputed` != 0: strategies 1-2 without uwie_set_tuning restore_store); few, large tiles
+ *   nchunk           row chunks per interpolation cell of the apply kernel: its grid is (tiles_x+1)(tiles_y+1) nchunk x batch
+ *   cells_walk       interpolation cells that hold pixels and whose blocks walk down the rows of fixed 4-pixel columns
+ *   cells_flat       ... and whose blocks take the flat loop over all 4-pixel groups (cells wider than 1024 px, or of a
+ *                    width that would leave more than an eighth of a column-walking block idle)
+ * No context, as above: nothing here depends on a tuning. */
+typedef struct uwie_clahe_plan_info {
+    int32_t tile_w, tile_h, padded, clip_limit, wide_lut, nchunk, cells_walk, cells_flat;
+} uwie_clahe_plan_info;
+int uwie_clahe_plan(int batch, int H, int W, int tiles_x, int tiles_y, double clip_limit, int recomputed,
+                    uwie_clahe_plan_info *out);
+
 /* restore_image (S6:183-188): float32 [batch][H][W][3]. */
 int uwie_restore(uwie_ctx *ctx, const uint8_t *d_in, const int32_t *d_kind, const float *d_A, const double *d_t,
                  int batch, int H, int W, float *d_out_f32, void *stream);

@@ -305,10 +305,11 @@ class SixStrategyOracle:
         return cls.stretch(img, pct, 100 - pct)
 
     @staticmethod
-    def clahe(img, clip=2.0):
-        """apply_clahe: six_stadigy.py:202-208 (LAB lightness, 8x8 tiles, float32 result)."""
+    def clahe(img, clip=2.0, tiles=(8, 8)):
+        """apply_clahe: six_stadigy.py:202-208 (LAB lightness, 8x8 tiles, float32 result).  ``tiles``: uwie_params'
+        tiles_x / tiles_y, which the reference fixes at 8 x 8."""
         lab = cv_rgb2lab_u8((img * 255).astype(np.uint8))
-        lab[:, :, 0] = cv_clahe_u8(lab[:, :, 0], clip, (8, 8))
+        lab[:, :, 0] = cv_clahe_u8(lab[:, :, 0], clip, tiles)
         return cv_lab2rgb_u8(lab).astype(np.float32) / 255.0
 
     @staticmethod
@@ -321,35 +322,51 @@ class SixStrategyOracle:
         A = atmospheric_light(img, 1, cls.gray_shift)
         return cls.restore(img, A, cls.transmission(img, A, omega, ksize, eps))
 
+    CLAHE_CLIP = {1: 3.0, 2: 2.0, 4: 4.0, 5: 1.5, 6: 3.5}  # six_stadigy.py:230-285
+
     @classmethod
-    def strategy(cls, number, img):
-        """strategy1..6: six_stadigy.py:230-285."""
+    def before_clahe(cls, number, img):
+        """What strategy 1, 2, 4, 5 or 6 hands to apply_clahe."""
         if number == 1:
-            y = cls.stretch(cls.dehaze(img, 0.3, 20, 5e-1), 5, 98)
-            return cls.gamma(cls.clahe(y, 3.0), 1.5)
+            return cls.stretch(cls.dehaze(img, 0.3, 20, 5e-1), 5, 98)
         if number == 2:
-            y = cls.stretch(cls.dehaze(img, 0.5, 15, 5e-1), 15, 95)
-            return cls.clahe(y, 2.0)
+            return cls.stretch(cls.dehaze(img, 0.5, 15, 5e-1), 15, 95)
+        if number == 4:
+            return img
+        if number == 5:
+            return cls.stretch(cls.white_balance(img, 2), 15, 90)
+        if number == 6:
+            return cls.stretch(img, 5, 98)
+        raise ValueError(f"strategy {number} has no CLAHE stage")
+
+    @classmethod
+    def after_clahe(cls, number, y):
+        """What strategy 1, 2, 4, 5 or 6 does with apply_clahe's result."""
+        if number == 2:
+            return y
+        if number == 4:
+            return cls.gamma(cls.white_balance(cls.stretch(y, 10, 95), 3), 1.3)
+        return cls.gamma(y, {1: 1.5, 5: 1.2, 6: 1.4}[number])
+
+    @classmethod
+    def strategy(cls, number, img, tiles=(8, 8), clip=None):
+        """strategy1..6: six_stadigy.py:230-285.  ``tiles`` / ``clip``: uwie_params' tiles_x, tiles_y and clip_limit in
+        place of the reference's 8 x 8 and per-strategy limit (None)."""
         if number == 3:
             y = cls.stretch(cls.dehaze(img, 0.7, 10, 1e-1), 20, 85)
             return cls.white_balance(y, 2)
-        if number == 4:
-            y = cls.stretch(cls.clahe(img, 4.0), 10, 95)
-            return cls.gamma(cls.white_balance(y, 3), 1.3)
-        if number == 5:
-            y = cls.stretch(cls.white_balance(img, 2), 15, 90)
-            return cls.gamma(cls.clahe(y, 1.5), 1.2)
-        if number == 6:
-            return cls.gamma(cls.clahe(cls.stretch(img, 5, 98), 3.5), 1.4)
-        raise ValueError(f"unknown strategy number {number}")
+        if number not in cls.CLAHE_CLIP:
+            raise ValueError(f"unknown strategy number {number}")
+        y = cls.clahe(cls.before_clahe(number, img), cls.CLAHE_CLIP[number] if clip is None else clip, tiles)
+        return cls.after_clahe(number, y)
 
 
-def enhance_u8(frame_u8, strategy=2, cast_correct=True):
+def enhance_u8(frame_u8, strategy=2, cast_correct=True, tiles=(8, 8), clip=None):
     """Canonical ``enhance(u8 HxWx3) -> u8 HxWx3`` (six_stadigy.py:406-431)."""
     x = normalise_u8(frame_u8)
     if cast_correct:
         x = correct_cast(x, classify_cast(x))
-    return quantise_u8(SixStrategyOracle.strategy(strategy, x))
+    return quantise_u8(SixStrategyOracle.strategy(strategy, x, tiles, clip))
 
 
 # --------------------------------------------------------------------------

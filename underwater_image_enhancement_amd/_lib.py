@@ -74,6 +74,21 @@ class UwieModelDesc(ctypes.Structure):
                 ("gamma", ctypes.c_double)]
 
 
+class UwieClahePlan(ctypes.Structure):
+    """Mirror of ``struct uwie_clahe_plan_info`` (include/uwie.h): how the CLAHE tail of a call is launched."""
+
+    _fields_ = [(name, ctypes.c_int32) for name in ("tile_w", "tile_h", "padded", "clip_limit", "wide_lut", "nchunk",
+                                                    "cells_walk", "cells_flat")]
+
+
+def clahe_plan(batch, H, W, tiles=(8, 8), clip_limit=2.0, recomputed=False) -> UwieClahePlan:
+    """uwie_clahe_plan: needs the library, not a device."""
+    out = UwieClahePlan()
+    check(load().uwie_clahe_plan(batch, H, W, int(tiles[0]), int(tiles[1]), float(clip_limit), int(bool(recomputed)),
+                                 ctypes.byref(out)))
+    return out
+
+
 # name -> argument types (return type is int unless listed in _RESTYPES)
 _VP, _SZ, _I, _D = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_double
 _PP = ctypes.POINTER(UwieParams)
@@ -102,6 +117,7 @@ SIGNATURES = {
     "uwie_color_correct_f32": [_VP, _VP, _VP, _VP, _I, _I, _I, _VP],
     "uwie_guided_plan": [_I, _I, _I, _I, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
     "uwie_guided_fill": [_I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)],
+    "uwie_clahe_plan": [_I, _I, _I, _I, _I, _D, _I, ctypes.POINTER(UwieClahePlan)],
     "uwie_enhance_u8": [_VP, _VP, _VP, _VP, _I, _I, _I, _PP, _VP, _SZ, _VP],
     "uwie_enhance_u8_f64": [_VP, _VP, _VP, _VP, _I, _I, _I, _PP, _VP, _SZ, _VP],
     "uwie_enhance_percentiles": [_VP, _VP, _SZ, _I, _I, _I, _PP, _VP, _VP],

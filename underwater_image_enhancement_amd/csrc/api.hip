@@ -1996,6 +1996,16 @@ int uwie_guided_fill(int batch, int H, int W, int ksize, long long *items)
     return UWIE_OK;
 }
 
+int uwie_clahe_plan(int batch, int H, int W, int tiles_x, int tiles_y, double clip_limit, int recomputed,
+                    uwie_clahe_plan_info *out)
+{
+    UWIE_REQUIRE(out, "clahe_plan: NULL pointer");
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_REQUIRE(tiles_x >= 1 && tiles_y >= 1 && tiles_x * tiles_y <= 4096, "clahe_plan: bad tile grid");
+    clahe_plan_info(Shape{batch, H, W}, clip_limit, tiles_x, tiles_y, recomputed != 0, out);
+    return UWIE_OK;
+}
+
 int uwie_restore(uwie_ctx *ctx, const uint8_t *d_in, const int32_t *d_kind, const float *d_A, const double *d_t,
                  int batch, int H, int W, float *d_out_f32, void *stream)
 {

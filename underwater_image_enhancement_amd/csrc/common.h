@@ -536,6 +536,8 @@ int launch_restore_planar_hist(const uint8_t *d_in, const int32_t *d_kind, const
 int launch_restore_rank(const RestoreSrc &src, Shape s, const SelectPlan &plan, hipStream_t st);
 int select_rank_run(const SelectPlan &plan, Shape s, hipStream_t st, const RestoreSrc &src);
 size_t tail_ws_bytes(Shape s, int tx, int ty);
+// the launch plan of the CLAHE tail (uwie_clahe_plan): the same arithmetic the three launchers below run on
+void clahe_plan_info(Shape s, double clip, int tx, int ty, bool recomputed, uwie_clahe_plan_info *out);
 // d_pct: [B][3][pct_stride] = lo1, hi1 [, lo2, hi2]; two = second stretch present; gamma_mode 0/1/2
 int launch_tail_clahe(uwie_ctx *ctx, const float *d_planar, const float *d_pct, int pct_stride, float eps, int two,
                       Shape s, double clip, int tx, int ty, int gamma_mode, double gamma, uint8_t *d_out_u8,

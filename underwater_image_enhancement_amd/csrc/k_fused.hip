@@ -931,6 +931,22 @@ __device__ __forceinline__ int ab_to_xz_cubic(int i)
     return (int)(__umul24(sq, (uint32_t)i) >> 14);
 }
 
+// k_clahe_apply_out's per-block choice, by the 4-pixel groups per row of its cell (gpr): true = every thread keeps one
+// column group and walks down the rows (256 / gpr rows per step; taken when that leaves at most an eighth of the block
+// idle); false = the flat loop over all groups of the block (cells wider than 1024 px, and widths that would idle more).
+// The kernel and the plan query (clahe_plan_info) decide with the same text: a macro, because a shared __host__ __device__
+// function changed the kernel's code (its 256 / max(gpr, 1) was compiled a second time, 13 more instructions per block;
+// profiles/isa_summary.py).  The host side evaluates it in clahe_apply_walks with its own rstep, pinned below.
+#define UWIE_APPLY_WALKS(gpr, rstep) ((gpr) <= 256 && (rstep) * (gpr) * 8 >= 256 * 7)
+constexpr bool clahe_apply_walks(int gpr) { return UWIE_APPLY_WALKS(gpr, 256 / (gpr > 1 ? gpr : 1)); }
+// cell widths 4 gpr - 3 .. 4 gpr: up to 340 px walk (three or more rows per step), 341 .. 444 flat, 445 .. 512 walk (two rows),
+// 513 .. 892 flat, 893 .. 1024 walk (one row), wider cells flat
+static_assert(clahe_apply_walks(1) && clahe_apply_walks(45) && clahe_apply_walks(85), "walk: narrow cells");
+static_assert(!clahe_apply_walks(86) && !clahe_apply_walks(90) && !clahe_apply_walks(111), "flat: 341 .. 444 px");
+static_assert(clahe_apply_walks(112) && clahe_apply_walks(128), "walk: 445 .. 512 px");
+static_assert(!clahe_apply_walks(129) && !clahe_apply_walks(223), "flat: 513 .. 892 px");
+static_assert(clahe_apply_walks(224) && clahe_apply_walks(256) && !clahe_apply_walks(257), "walk up to 1024 px, flat beyond");
+
 // One block per (interpolation cell, row chunk) and image.  Between the centres of four neighbouring tiles the four
 // tile LUTs a pixel blends are fixed, so the block copies them (a 4x4 window of tiles around the cell, which also
 // covers a boundary pixel that float rounding puts into the next cell) into LDS once; the four per-pixel LUT gathers
@@ -1180,7 +1196,7 @@ __global__ void __launch_bounds__(256) k_clahe_apply_out(const LabTables *__rest
         }
     };
     const int rows = cy1 - cy0, rstep = 256 / max(gpr, 1);
-    if (gpr <= 256 && rstep * gpr * 8 >= 256 * 7) {
+    if (UWIE_APPLY_WALKS(gpr, rstep)) {
         // a thread keeps its 4-pixel column group and walks down the rows: the column terms are computed once
         if (tid < rstep * gpr) {
             const int xg = tid % gpr;
@@ -1356,12 +1372,24 @@ __global__ void __launch_bounds__(256) k_stretch64_out(const double *__restrict_
     }
 }
 
-ClaheGeom make_geom(Shape s, double clip, int tx, int ty)
-{
+// The launch arithmetic of the CLAHE tail, once: launch_tail_clahe, launch_codes_lab_lut, launch_clahe_apply_codes and the
+// plan query (uwie_clahe_plan) all read it from here.
+struct ClaheLaunch {
     ClaheGeom g;
+    bool padded;  // the frame is ragged in either direction: OpenCV pads BOTH
+    bool wide;    // k_stretch_lab_lut<1, 1024>: a recomputed source, few tiles, large tiles
+    int cells;    // interpolation cells: (tx + 1) * (ty + 1)
+    int nchunk;   // row chunks per cell of k_clahe_apply_out
+};
+
+ClaheLaunch plan_clahe(Shape s, double clip, int tx, int ty, bool recomputed)
+{
+    ClaheLaunch L;
+    ClaheGeom &g = L.g;
     g.H = s.H; g.W = s.W; g.tx = tx; g.ty = ty;
     int We = s.W, He = s.H;
-    if (s.W % tx != 0 || s.H % ty != 0) {
+    L.padded = s.W % tx != 0 || s.H % ty != 0;
+    if (L.padded) {
         We = s.W + (tx - s.W % tx);
         He = s.H + (ty - s.H % ty);
     }
@@ -1374,7 +1402,15 @@ ClaheGeom make_geom(Shape s, double clip, int tx, int ty)
         g.clip = (int)(clip * area / 256);
         if (g.clip < 1) g.clip = 1;
     }
-    return g;
+    L.wide = recomputed && (long)tx * ty * s.B < 512 && (long)g.tw * g.th >= 8192;
+    // row chunks per interpolation cell: enough blocks to fill the chip, at least ~16 rows each
+    L.cells = (tx + 1) * (ty + 1);
+#ifndef UWIE_APPLY_TOTAL
+#define UWIE_APPLY_TOTAL 25920
+#endif
+    const int nchunk = cdiv(UWIE_APPLY_TOTAL, L.cells * s.B);  // ~14 rounds of the 1792 resident blocks (7 per CU by registers)
+    L.nchunk = std::max(1, std::min(nchunk, std::max(1, g.th / 16)));
+    return L;
 }
 
 float gamma_exponent(int mode, double g) { return mode == 1 ? (float)g : mode == 2 ? (float)(1.0 / g) : 1.0f; }
@@ -1426,6 +1462,28 @@ int launch_planar_hist(const RestoreSrc &S, Shape s, V *d_planar, uint32_t *d_gh
 }
 
 }  // namespace
+
+void clahe_plan_info(Shape s, double clip, int tx, int ty, bool recomputed, uwie_clahe_plan_info *out)
+{
+    const ClaheLaunch L = plan_clahe(s, clip, tx, ty, recomputed);
+    const ClaheGeom &g = L.g;
+    out->tile_w = g.tw;
+    out->tile_h = g.th;
+    out->padded = L.padded;
+    out->clip_limit = g.clip;
+    out->wide_lut = L.wide;
+    out->nchunk = L.nchunk;
+    out->cells_walk = out->cells_flat = 0;
+    // the cells of k_clahe_apply_out that hold pixels (its own rectangle arithmetic), by the loop their blocks take
+    int rows = 0;
+    for (int cyi = 0; cyi <= ty; ++cyi)
+        rows += std::max(cyi * g.th - g.th / 2, 0) < std::min((cyi + 1) * g.th - g.th / 2, g.H);
+    for (int cxi = 0; cxi <= tx; ++cxi) {
+        const int cx0 = std::max(cxi * g.tw - g.tw / 2, 0), cx1 = std::min((cxi + 1) * g.tw - g.tw / 2, g.W);
+        if (cx0 >= cx1) continue;
+        (clahe_apply_walks((cx1 - cx0 + 3) / 4) ? out->cells_walk : out->cells_flat) += rows;
+    }
+}
 
 int launch_restore_planar_hist(const uint8_t *d_in, const int32_t *d_kind, const float *d_A, const double *d_t, Shape s,
                                float *d_planar, uint32_t *d_ghist, hipStream_t st, bool linear, const SelectPlan *plan, int t32)
@@ -1479,9 +1537,10 @@ int launch_tail_clahe(uwie_ctx *ctx, const float *d_planar, const float *d_pct, 
     Carver c(ws);
     uint8_t *lut = c.take<uint8_t>((size_t)s.B * tx * ty * 256);
     uint8_t *lab = c.take<uint8_t>((size_t)s.B * s.npx() * 3);
-    const ClaheGeom g = make_geom(s, clip, tx, ty);
+    const ClaheLaunch L = plan_clahe(s, clip, tx, ty, src != nullptr);
+    const ClaheGeom &g = L.g;
     const auto k_stretch_lab_lut_wide = k_stretch_lab_lut<1, 1024>;  // (name as the profiler reports it)
-    if (src && (long)tx * ty * s.B < 512 && (long)g.tw * g.th >= 8192)
+    if (L.wide)
         UWIE_LAUNCH(k_stretch_lab_lut_wide, dim3(tx * ty, s.B), dim3(1024), 0, st, ctx->d_lab, d_planar, *src, d_pct, pct_stride,
                     eps, two, (const uint8_t *)nullptr, g, lab, lut);
     else if (src)
@@ -1491,13 +1550,7 @@ int launch_tail_clahe(uwie_ctx *ctx, const float *d_planar, const float *d_pct, 
         UWIE_LAUNCH(k_stretch_lab_lut<0>, dim3(tx * ty, s.B), dim3(256), 0, st, ctx->d_lab, d_planar, RestoreSrc{}, d_pct,
                     pct_stride, eps, two, (const uint8_t *)nullptr, g, lab, lut);
     UWIE_LAUNCH_CHECK();
-    // row chunks per interpolation cell: enough blocks to fill the chip, at least ~16 rows each
-    const int cells = (tx + 1) * (ty + 1);
-#ifndef UWIE_APPLY_TOTAL
-#define UWIE_APPLY_TOTAL 25920
-#endif
-    int nchunk = cdiv(UWIE_APPLY_TOTAL, cells * s.B);  // ~14 rounds of the 1792 resident blocks (7 per CU by registers)
-    nchunk = std::max(1, std::min(nchunk, std::max(1, g.th / 16)));
+    const int cells = L.cells, nchunk = L.nchunk;
     const auto k_clahe_apply_u8 = k_clahe_apply_out<false, false>;  // (names as the profiler reports them)
     const auto k_clahe_apply_f32 = k_clahe_apply_out<false, true>;
     if (d_out_f32)
@@ -1517,10 +1570,9 @@ int launch_clahe_apply_codes(uwie_ctx *ctx, const uint8_t *d_lab, const uint8_t 
                              int ty, const uint8_t *d_fin_code, const float *d_fin_val, uint8_t *d_out_u8, float *d_out_f32,
                              uint8_t *d_codes_out, uint32_t *d_hist, hipStream_t st)
 {
-    const ClaheGeom g = make_geom(s, clip, tx, ty);
-    const int cells = (tx + 1) * (ty + 1);
-    int nchunk = cdiv(25920, cells * s.B);
-    nchunk = std::max(1, std::min(nchunk, std::max(1, g.th / 16)));
+    const ClaheLaunch L = plan_clahe(s, clip, tx, ty, false);
+    const ClaheGeom &g = L.g;
+    const int cells = L.cells, nchunk = L.nchunk;
     const auto k_clahe_apply_codes = k_clahe_apply_out<true, false>;
     UWIE_LAUNCH(k_clahe_apply_codes, dim3(cells * nchunk, s.B), dim3(256), 0, st, ctx->d_lab, d_lab, d_tile_lut, g, nchunk, 0, 1.0f,
                 d_fin_code, d_fin_val, d_out_u8, d_out_f32, d_codes_out, d_hist);
@@ -1532,7 +1584,7 @@ int launch_clahe_apply_codes(uwie_ctx *ctx, const uint8_t *d_lab, const uint8_t 
 int launch_codes_lab_lut(uwie_ctx *ctx, const uint8_t *d_in, const uint8_t *d_code_lut, Shape s, double clip, int tx, int ty,
                          uint8_t *d_lab, uint8_t *d_tile_lut, hipStream_t st)
 {
-    const ClaheGeom g = make_geom(s, clip, tx, ty);
+    const ClaheGeom g = plan_clahe(s, clip, tx, ty, false).g;
     RestoreSrc src{};
     src.in = d_in;
     UWIE_LAUNCH(k_stretch_lab_lut<2>, dim3(tx * ty, s.B), dim3(256), 0, st, ctx->d_lab, (const float *)nullptr, src,

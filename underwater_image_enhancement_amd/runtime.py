@@ -784,9 +784,13 @@ class Device(_ClosedOnDel):
         check(self.lib.uwie_gamma_f32(self._ctx, _ptr(img), _ptr(out), img.numel(), float(g), int(mode), self.stream()))
         return out
 
+    def _clahe_workspace(self, B, H, W, tiles):
+        """A workspace sized for the tile LUTs of this grid (the default parameter set answers for 8 x 8)."""
+        return self.workspace_for(B, H, W, self.params(_lib.SURFACE_SIX, 2, tiles_x=int(tiles[0]), tiles_y=int(tiles[1])))
+
     def clahe_f32(self, img, clip, tiles=(8, 8)):
         B, H, W = self._bhw(img)
-        ws = self.workspace_for(B, H, W)
+        ws = self._clahe_workspace(B, H, W, tiles)
         out = torch.empty_like(img)
         check(self.lib.uwie_clahe_f32(self._ctx, _ptr(img), _ptr(out), B, H, W, float(clip), int(tiles[0]),
                                       int(tiles[1]), _ptr(ws), ws.numel(), self.stream()))
@@ -809,7 +813,7 @@ class Device(_ClosedOnDel):
 
     def clahe_u8(self, planes, clip, tiles=(8, 8)):
         B, H, W = (int(v) for v in planes.shape)
-        ws = self.workspace_for(B, H, W)
+        ws = self._clahe_workspace(B, H, W, tiles)
         out = torch.empty_like(planes)
         check(self.lib.uwie_clahe_u8(self._ctx, _ptr(planes), _ptr(out), B, H, W, float(clip), int(tiles[0]),
                                      int(tiles[1]), _ptr(ws), ws.numel(), self.stream()))
