@@ -25,6 +25,10 @@ __device__ __forceinline__ float px_val(uint32_t u, bool attenuate)
     float x = (float)u / 255.0f;
     return attenuate ? x * 0.85f : x;
 }
+// Loads and stores at an address aligned only for bytes: gfx950 takes them as one dword / dwordx4 access
+typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
+typedef uint4 __attribute__((aligned(1))) u128_unaligned;
+
 // Four consecutive RGB pixels (12 bytes).  Frames whose pixel count is a multiple of 4 keep every 4-pixel group
 // 4-byte aligned (frame bases are multiples of 12 bytes from a 256-byte aligned allocation), so the group comes in
 // as three dwords; other frames fall back to byte loads.
@@ -55,8 +59,7 @@ __device__ __forceinline__ Px4 load_px4(const uint8_t *p, int n, bool aligned)
 // four pixels at any byte address (three unaligned dword loads)
 __device__ __forceinline__ Px4 load_px4_any(const uint8_t *p)
 {
-    typedef uint32_t __attribute__((aligned(1))) u32_a1;
-    const u32_a1 *w = reinterpret_cast<const u32_a1 *>(p);
+    const u32_unaligned *w = reinterpret_cast<const u32_unaligned *>(p);
     const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
     Px4 o;
     o.r[0] = w0 & 255; o.g[0] = (w0 >> 8) & 255; o.b[0] = (w0 >> 16) & 255;
@@ -172,7 +175,10 @@ __device__ __forceinline__ float pow_f32_fast(float x, float g)
 //   vgg_stretch        clamp((x - p_low) / (p_high - p_low + 1e-8), 0, 1) of one channel value
 //   vgg_after_stretch  [UWIE_DIFF_OMEGA] dehaze with A = 0.6 -> [UWIE_DIFF_GAMMA] pow(v + 1e-8, gamma) -> clamp(0, 1), in place.
 //                      fmaxf(NaN, 0) = 0: the final clamp leaves no NaN behind
+// np.clip(v, 0, 1): clamp01 (fmin / fmax) turns NaN into 0; clip01 (v_med3_f32: one instruction) is for values that are
+// not NaN.  They differ for NaN, so both stay.
 __device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
+__device__ __forceinline__ float clip01(float v) { return __builtin_amdgcn_fmed3f(v, 0.0f, 1.0f); }
 __device__ __forceinline__ float vgg_stretch(float x, float lo, float rng) { return clamp01((x - lo) / rng); }
 __device__ __forceinline__ void vgg_after_stretch(float (&v)[3], float omega, float gamma, int flags)
 {
@@ -265,6 +271,14 @@ __device__ __forceinline__ uint64_t f64_key(double v)
     return b ^ ((b >> 63) ? 0xffffffffffffffffull : 0x8000000000000000ull);
 }
 
+// cv::saturate_cast<uchar>(int)
+__device__ __forceinline__ uint8_t sat_u8(int v) { return (uint8_t)min(max(v, 0), 255); }
+// float32 power: evaluated in float64 and rounded once (agrees with a correctly rounded powf except on astronomically rare
+// double-rounding cases; the exponent is float32(g) like NumPy's weak Python scalar).  pow_f32_fast is the per-pixel form.
+__device__ __forceinline__ float pow_f32(float x, float g) { return (float)pow((double)x, (double)g); }
+__device__ __forceinline__ float relu_f(float v) { return v <= 0.0f ? 0.0f : v; }  // NaN stays NaN, as torch's relu
+__device__ __forceinline__ float sigmoid_f(float v) { return 1.0f / (1.0f + expf(-v)); }
+
 // cv::borderInterpolate(p, len, BORDER_REFLECT_101)
 __device__ __forceinline__ int reflect101(int p, int len)
 {
@@ -335,6 +349,32 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v)
         if (lane >= o) v += t;
     }
     return v;
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __longlong_as_double((long long)shfl_xor_u64((uint64_t)__double_as_longlong(v), o));
+    return v;
+}
+// inclusive scan over a block of 256 threads; wsum: four words of LDS
+__device__ __forceinline__ uint32_t block_incl_scan_256(uint32_t v, uint32_t *wsum)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t incl = wave_incl_scan_u32(v);
+    __syncthreads();
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    for (int i = 0; i < w; ++i) incl += wsum[i];
+    return incl;
+}
+// Orders one wavefront's LDS accesses (a tile or queue that no other wavefront touches): LDS executes a wavefront's
+// instructions in order, so a compiler fence is all it takes -- no s_barrier
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // 16-byte accesses at an address aligned only for its element type: the copy through a local lets the compiler emit one

@@ -11,20 +11,15 @@
 // enumerates the recursion's leaves first and combines them in post-order.
 #include "common.h"
 #include "devutil.h"
+#include "lane_hist.h"
 #include "pairwise_tree.h"
+#include "quadtree.h"
 
 #include <cstdlib>
 
 namespace uwie {
 
 namespace {
-
-constexpr int kMaxLevels = 32;
-
-struct TraceRec {  // matches the layout documented in uwie.h
-    int32_t y0, x0, rows, cols;
-    double score[4];
-};
 
 struct LevelBufs {
     Region *blk;       // [B] current block
@@ -56,12 +51,8 @@ __global__ void __launch_bounds__(256) k_q_setup(Region *__restrict__ blk, Regio
     for (int b = i; b < B; b += n) {
         const Region k{b, 0, 0, H, W};
         blk[b] = k;
-        const bool leaf = k.rows <= min_size || k.cols <= min_size;  // six_stadigy.py:76
-        const int mr = k.rows / 2, mc = k.cols / 2;                 // six_stadigy.py:85-86
-        Region q[4] = {{b, 0, 0, mr, mc}, {b, 0, mc, mr, W - mc}, {b, mr, 0, H - mr, mc}, {b, mr, mc, H - mr, W - mc}};
+        quad_split(regs, b, k, min_size);
         for (int j = 0; j < 4; ++j) {
-            if (leaf) q[j].rows = q[j].cols = 0;
-            regs[b * 4 + j] = q[j];
             edges[b * 4 + j] = 0;
             strong[b * 4 + j] = 0;
         }
@@ -74,22 +65,15 @@ __global__ void k_make_quadrants(const Region *__restrict__ blk, Region *__restr
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const Region k = blk[b];
-    const bool leaf = k.rows <= min_size || k.cols <= min_size;  // six_stadigy.py:76
-    const int mr = k.rows / 2, mc = k.cols / 2;                 // six_stadigy.py:85-86
-    Region q[4] = {{b, k.y0, k.x0, mr, mc},
-                   {b, k.y0, k.x0 + mc, mr, k.cols - mc},
-                   {b, k.y0 + mr, k.x0, k.rows - mr, mc},
-                   {b, k.y0 + mr, k.x0 + mc, k.rows - mr, k.cols - mc}};
-    for (int i = 0; i < 4; ++i) {
-        if (leaf) q[i].rows = q[i].cols = 0;
-        regs[b * 4 + i] = q[i];
-    }
+    quad_split(regs, b, blk[b], min_size);
 }
 
 // value of element `e` (raster index inside region r) for channel c: x or (x - mean)^2
 template <bool VAR>
 struct Elem {
+    using src_t = uint8_t;
+    using val_t = float;
+    static constexpr bool kVar = VAR;
     const uint8_t *img;
     int W;
     float att[3];  // color_correction's factor of the channel (six_stadigy.py:305-323): 0.85f or 1.0f (x * 1.0f == x)
@@ -112,93 +96,8 @@ struct Elem {
     }
 };
 
-// Level 0 only (GRAY): the sums pass visits every pixel of the frame exactly once with its normalised, colour-corrected
-// value in hand, so it also writes the 8-bit gray plane -- gray = cvtColor((x*255).astype(u8), RGB2GRAY), six_stadigy.py:149,177
-// -- instead of a separate sweep over the frame (k_quant_gray: 1.6 GB read again at 4K x 64).
-struct GrayOut {
-    uint8_t *plane;  // gray plane of the image (nullptr: none)
-    int shift;       // RGB2GRAY fixed point (15 or 14)
-};
-__device__ __forceinline__ uint32_t gray_of(float v0, float v1, float v2, int shift)
-{
-    return gray_fixed(quant_u8(v0), quant_u8(v1), quant_u8(v2), shift);
-}
-
-// NumPy's pairwise_sum on a block of n <= 128 elements starting at raster element e0, three channels at once.
-template <bool VAR, bool GRAY = false>
-__device__ void leaf_sum3(const Elem<VAR> &el, const Region &r, int e0, int n, float out[3], GrayOut go = GrayOut{nullptr, 15})
-{
-    static_assert(!(VAR && GRAY), "the gray plane rides with the plain sums");
-    int ly = e0 / r.cols, lx = e0 % r.cols;
-    const uint8_t *p = el.img + ((size_t)(r.y0 + ly) * el.W + r.x0 + lx) * 3;
-    uint8_t *gp = GRAY ? go.plane + (size_t)(r.y0 + ly) * el.W + r.x0 + lx : nullptr;
-    auto step = [&]() {
-        ++lx;
-        p += 3;
-        if (GRAY) ++gp;
-        if (lx == r.cols) {
-            lx = 0;
-            p += (size_t)(el.W - r.cols) * 3;
-            if (GRAY) gp += el.W - r.cols;
-        }
-    };
-    // the three values of the pixel at p (and its gray byte on the way)
-    auto px3 = [&](float &v0, float &v1, float &v2) {
-        v0 = el.get(p, 0);
-        v1 = el.get(p, 1);
-        v2 = el.get(p, 2);
-        if constexpr (GRAY) *gp = (uint8_t)gray_of(v0, v1, v2, go.shift);
-    };
-    if (n < 8) {
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-        for (int i = 0; i < n; ++i) {
-            float v0, v1, v2;
-            px3(v0, v1, v2);
-            a0 += v0;
-            a1 += v1;
-            a2 += v2;
-            step();
-        }
-        out[0] = a0; out[1] = a1; out[2] = a2;
-        return;
-    }
-    float acc[3][8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        px3(acc[0][j], acc[1][j], acc[2][j]);
-        step();
-    }
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float v0, v1, v2;
-            px3(v0, v1, v2);
-            acc[0][j] += v0;
-            acc[1][j] += v1;
-            acc[2][j] += v2;
-            step();
-        }
-    }
-    float res[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) res[c] = tree8(acc[c]);
-    for (; i < n; ++i) {
-        float v0, v1, v2;
-        px3(v0, v1, v2);
-        res[0] += v0;
-        res[1] += v1;
-        res[2] += v2;
-        step();
-    }
-    out[0] = res[0]; out[1] = res[1]; out[2] = res[2];
-}
-
-// The same for a full 128-element leaf, eight pixels per step: when the eight pixels lie in one row of the region
+// leaf_sum3 (quadtree.h) for a full 128-element leaf of bytes, eight pixels per step: when the eight pixels lie in one row of the region
 // their 24 bytes come in as six (unaligned) dword loads instead of 24 byte loads.
-typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
-typedef uint4 __attribute__((aligned(1))) u128_unaligned;
-
 typedef uint2 __attribute__((aligned(1))) u64x_unaligned;
 
 template <bool VAR, bool GRAY = false>
@@ -380,7 +279,7 @@ __global__ void __launch_bounds__(64) k_q_chunk_sums(const uint8_t *__restrict__
     }
     // ragged chunk: the recursion tree of NumPy's pairwise sum for this length (pairwise_tree.h)
     float res[3];
-    pairwise_ragged(len, lane, tree, [&](int off, int l, float *s3) { leaf_sum3<VAR, GRAY>(el, r, c0 + off, l, s3, go); }, res);
+    pairwise_ragged(len, lane, tree, [&](int off, int l, float *s3) { leaf_sum3<Elem<VAR>, GRAY>(el, r, c0 + off, l, s3, go); }, res);
     if (lane == 0) { out[0] = res[0]; out[1] = res[1]; out[2] = res[2]; }
 }
 
@@ -403,30 +302,11 @@ __global__ void __launch_bounds__(64) k_q_combine(const Region *__restrict__ reg
     if (!VAR) mean[reg * 3 + lane] = (float)((double)acc / (double)n);
 }
 
-// The greedy step (six_stadigy.py:100-111): quadrant `arg` becomes the block, its quadrants the next level's regions
-// (what k_make_quadrants would write) with zeroed edge counters.  One lane.
-__device__ void q_descend(Region *__restrict__ blk, Region *__restrict__ regs, uint32_t *__restrict__ edges, int b, int arg, int min_size)
-{
-    const Region k = regs[b * 4 + arg];
-    blk[b] = k;
-    const bool leaf = k.rows <= min_size || k.cols <= min_size;  // six_stadigy.py:76
-    const int mr = k.rows / 2, mc = k.cols / 2;                 // six_stadigy.py:85-86
-    Region q[4] = {{b, k.y0, k.x0, mr, mc},
-                   {b, k.y0, k.x0 + mc, mr, k.cols - mc},
-                   {b, k.y0 + mr, k.x0, k.rows - mr, mc},
-                   {b, k.y0 + mr, k.x0 + mc, k.rows - mr, k.cols - mc}};
-    for (int i = 0; i < 4; ++i) {
-        if (leaf) q[i].rows = q[i].cols = 0;
-        regs[b * 4 + i] = q[i];
-        edges[b * 4 + i] = 0;
-    }
-}
-
 // ---- a level decided from byte histograms (round 3) ------------------------------------------------------------------
 // compute_Q's score of a quadrant is a function of sums over its pixels, and a pixel's contribution only depends on its
 // byte: the EXACT sums (sum x, sum (x - m)^2 per channel) follow from a 3 x 256 histogram of the quadrant -- one pass over
-// the RGB bytes where NumPy's order needs two, and a streaming one (k_q_hist: the lane-column histogram words of
-// k_chunk_hist; on level 0 it writes the gray plane on the way).  The reference's float32 pairwise sums differ from the
+// the RGB bytes where NumPy's order needs two, and a streaming one (k_q_hist: the lane-column histogram of
+// lane_hist.h; on level 0 it writes the gray plane on the way).  The reference's float32 pairwise sums differ from the
 // exact ones by a bounded amount, so k_q_decide evaluates each quadrant's score as an INTERVAL that contains the
 // reference's value; when the best quadrant's interval lies above the other three the argmax is known and the level is
 // decided (results identical by construction), otherwise -- near ties, or when the caller wants the scores themselves
@@ -435,8 +315,8 @@ __device__ void q_descend(Region *__restrict__ blk, Region *__restrict__ regs, u
 // accumulator, 3 + 7 tree levels up to the 8192-element buffer, the unrolled tail), the sequential total over nch chunks
 // adds (nch - 1) u, u = 2^-24; the squared deviations add 3 u per element and n (m~ - m)^2 from the rounded mean; every
 // float32 operation of the score adds u.  All of them are taken 1.25 x.
-constexpr int kQHistCols = 32, kQHistFold = 31;  // fold the 10-bit fields after 31 steps: 31 * 4 pixels * 8 threads per column
-static_assert(kQHistFold * 4 * (256 / kQHistCols) < 1024, "10-bit fields");
+constexpr int kQHistFold = 31;  // fold the 10-bit fields after 31 steps: 31 * 4 pixels * 8 threads per column
+static_assert(kQHistFold * 4 * (256 / kLaneHistCols) <= kLaneHistField, "10-bit fields");
 
 // NARROW (chosen by the host from the level's largest quadrant): rows of fewer than 256 groups share a step
 template <bool GRAY, bool NARROW>
@@ -444,7 +324,7 @@ __global__ void __launch_bounds__(256) k_q_hist(const uint8_t *__restrict__ in, 
                                                 const Region *__restrict__ regs, int H, int W, uint32_t *__restrict__ hist,
                                                 uint8_t *__restrict__ gray_out, int gray_shift)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t h[256 * kQHistCols];
+    __shared__ __attribute__((aligned(16))) uint32_t h[kLaneHistWords];
     __shared__ uint32_t cnt[768];
     const int reg = blockIdx.y, tid = threadIdx.x;
     const Region r = regs[reg];
@@ -452,22 +332,20 @@ __global__ void __launch_bounds__(256) k_q_hist(const uint8_t *__restrict__ in, 
     const int rpb = (r.rows + (int)gridDim.x - 1) / (int)gridDim.x;
     const int y_lo = blockIdx.x * rpb, y_hi = min(r.rows, y_lo + rpb);
     if (y_lo >= y_hi) return;
-    for (int i = tid; i < 256 * kQHistCols / 4; i += 256) reinterpret_cast<uint4 *>(h)[i] = make_uint4(0, 0, 0, 0);
+    LaneHist::zero(h, tid);
     for (int i = tid; i < 768; i += 256) cnt[i] = 0;
     __syncthreads();
     const int knd = kind ? kind[r.img] : 0;
     const uint8_t *img = in + (size_t)r.img * H * W * 3;
     uint8_t *gray = GRAY ? gray_out + (size_t)r.img * H * W : nullptr;
-    const uint32_t colb = (uint32_t)(tid & (kQHistCols - 1)) * 4u;
-    char *hb = reinterpret_cast<char *>(h);
-    auto bump = [&](uint32_t moved, uint32_t inc) { atomicAdd(reinterpret_cast<uint32_t *>(hb + ((moved & 0x7f80u) | colb)), inc); };
-    constexpr uint32_t kR = 1u, kG = 1u << 10, kB = 1u << 20;
+    const LaneHist lh(h, tid);
+    // This kernel's own fold: one column per LDS instruction like LaneHist::fold_b32, but clearing for the next batch
     auto fold = [&]() {  // all threads; thread v folds the 32 columns of value v into the 32-bit totals and clears them
         __syncthreads();
         uint32_t cr = 0, cg = 0, cb = 0;
 #pragma unroll 8
-        for (int k = 0; k < kQHistCols; ++k) {
-            uint32_t &w = h[tid * kQHistCols + ((tid + k) & (kQHistCols - 1))];
+        for (int k = 0; k < kLaneHistCols; ++k) {
+            uint32_t &w = h[tid * kLaneHistCols + ((tid + k) & (kLaneHistCols - 1))];
             cr += w & 1023u;
             cg += (w >> 10) & 1023u;
             cb += w >> 20;
@@ -509,12 +387,8 @@ __global__ void __launch_bounds__(256) k_q_hist(const uint8_t *__restrict__ in, 
         const int x = 4 * (c.t * 256 + gx0), yy = NARROW ? c.y + ry : c.y, n = (!NARROW || (lane_on && yy < y_hi)) ? min(4, r.cols - x) : 0;
         if (n == 4) {
             const uint32_t c0 = d[0], c1 = d[1], c2 = d[2];
-            // R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
-            bump(c0 << 7, kR); bump(c0 >> 1, kG); bump(c0 >> 9, kB);
-            bump(c0 >> 17, kR); bump(c1 << 7, kG); bump(c1 >> 1, kB);
-            bump(c1 >> 9, kR); bump(c1 >> 17, kG); bump(c2 << 7, kB);
-            bump(c2 >> 1, kR); bump(c2 >> 9, kG); bump(c2 >> 17, kB);
-            if constexpr (GRAY) {
+            lh.add4(c0, c1, c2);
+            if constexpr (GRAY) {  // R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
                 const uint32_t g4 = gray4(c0 & 255, (c0 >> 8) & 255, (c0 >> 16) & 255) |
                                     gray4(c0 >> 24, c1 & 255, (c1 >> 8) & 255) << 8 |
                                     gray4((c1 >> 16) & 255, c1 >> 24, c2 & 255) << 16 |
@@ -525,7 +399,7 @@ __global__ void __launch_bounds__(256) k_q_hist(const uint8_t *__restrict__ in, 
             const uint8_t *row = img + ((size_t)(r.y0 + yy) * W + r.x0) * 3;
             for (int j = 0; j < n; ++j) {
                 const uint8_t *p = row + (size_t)(x + j) * 3;
-                bump((uint32_t)p[0] << 7, kR); bump((uint32_t)p[1] << 7, kG); bump((uint32_t)p[2] << 7, kB);
+                lh.add1(p);
                 if constexpr (GRAY) gray[(size_t)(r.y0 + yy) * W + r.x0 + x + j] = (uint8_t)gray4(p[0], p[1], p[2]);
             }
         }
@@ -569,6 +443,7 @@ __global__ void __launch_bounds__(256) k_q_hist(const uint8_t *__restrict__ in, 
         }
     }
     fold();
+    // (written out, not LaneHist::flush: the call changed this kernel's scalar allocation through the streaming loop)
     for (int i = tid; i < 768; i += 256)
         if (cnt[i]) atomicAdd(&hist[(size_t)reg * 768 + i], cnt[i]);
 }
@@ -726,28 +601,13 @@ __global__ void __launch_bounds__(64) k_q_select(Region *__restrict__ blk, Regio
 #pragma unroll
     for (int i = 0; i < 24; ++i) tots[i] = __shfl(acc, i);
     if (lane != 0) return;
-    double best = 0.0;
-    int arg = 0;
     double score[4];
     for (int q = 0; q < 4; ++q) {
         const Region r = regs[b * 4 + q];
-        const long long n = (long long)r.rows * r.cols;
-        const float *S = tots + q * 6, *V = tots + q * 6 + 3;
-        const float t1 = ((S[0] + S[1]) + S[2]) / (float)(3 * n);
-        const float t2 = ((S[2] + S[1]) - 2.0f * S[0]) / (float)n;
-        const float v0 = V[0] / (float)n, v1 = V[1] / (float)n, v2 = V[2] / (float)n;
-        const float t3 = ((v0 + v1) + v2) / 3.0f;
-        const double t4 = (double)edges[b * 4 + q] / (double)n;  // int64 / int -> float64
-        const double Q = (double)((t1 + t2) - t3) - t4;
-        score[q] = Q;
-        if (q == 0 || Q > best) { best = Q; arg = q; }  // np.argmax: first maximum
+        score[q] = quad_score<float>(tots + q * 6, tots + q * 6 + 3, (long long)r.rows * r.cols, edges[b * 4 + q]);
     }
-    if (trace) {
-        TraceRec &t = trace[b * kMaxLevels + level];
-        const Region k = blk[b];
-        t.y0 = k.y0; t.x0 = k.x0; t.rows = k.rows; t.cols = k.cols;
-        for (int q = 0; q < 4; ++q) t.score[q] = score[q];
-    }
+    const int arg = quad_argmax(score);
+    if (trace) trace_store(trace, b, level, blk[b], score);
     if (chk && status) {
         // tuning q_hist = 3: the reference-order score of every quadrant has to lie inside the interval k_q_decide
         // derived from the byte histograms, and a decision it would have taken has to be this argmax
@@ -781,13 +641,6 @@ constexpr int kTailSub = 4;                                    // wavefronts per
 constexpr int kTailPixBytes = 3 * kNpChunk;                    // RGB of a quadrant; later its gray bytes + 16-bit words
 constexpr int kTailTreeBytes = (int)((sizeof(TailTree) + 15) & ~size_t(15));
 constexpr int kTailQuadBytes = kTailPixBytes + kTailTreeBytes;
-
-__device__ __forceinline__ void tail_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // rows x rowbytes bytes (global, row pitch `pitch`) -> dense LDS, by the `nl` lanes of a quadrant (this one is `ql`):
 // dword loads; (row, dword) advance without a division per element.
@@ -994,7 +847,7 @@ __device__ uint32_t tail_hysteresis(uint16_t *st, int rows, int cols, int lane)
                 st[e] = (uint16_t)((st[e] & 0x1fff) | (2 << 13));
                 changed = true;
             }
-            tail_wave_sync();
+            wave_lds_sync();
         }
         if (!__any(changed)) break;
     }
@@ -1035,12 +888,8 @@ __global__ void __launch_bounds__(256 * kTailSub) k_q_tail(const uint8_t *__rest
     const uint8_t *img = in + (size_t)b * H * W * 3;
     const uint8_t *g = gray + (size_t)b * H * W;
     for (int level = level0; level < kMaxLevels; ++level) {
-        if (k.rows <= min_size || k.cols <= min_size) break;  // six_stadigy.py:76
-        const int mr = k.rows / 2, mc = k.cols / 2;           // six_stadigy.py:85-86
-        const Region r = qd == 0   ? Region{b, k.y0, k.x0, mr, mc}
-                         : qd == 1 ? Region{b, k.y0, k.x0 + mc, mr, k.cols - mc}
-                         : qd == 2 ? Region{b, k.y0 + mr, k.x0, k.rows - mr, mc}
-                                   : Region{b, k.y0 + mr, k.x0 + mc, k.rows - mr, k.cols - mc};
+        if (quad_is_leaf(k, min_size)) break;
+        const Region r = quad_region(b, k, qd);
         const int n = r.rows * r.cols;
 #ifdef UWIE_TAIL_PROF
         const uint64_t c0 = wall_clock64();
@@ -1150,9 +999,9 @@ __global__ void __launch_bounds__(256 * kTailSub) k_q_tail(const uint8_t *__rest
         if (hist_mode) {
             if (threadIdx.x == 0) {  // one thread decides (its doubles would cost every lane registers), everybody reads
                 double lo[4], hi[4];
-                const int rows4[4] = {mr, mr, k.rows - mr, k.rows - mr}, cols4[4] = {mc, k.cols - mc, mc, k.cols - mc};
                 for (int q = 0; q < 4; ++q) {
-                    const double t4 = (double)s_edges[q] / ((double)rows4[q] * (double)cols4[q]);
+                    const Region rq = quad_region(b, k, q);
+                    const double t4 = (double)s_edges[q] / ((double)rq.rows * (double)rq.cols);
                     lo[q] = s_ilo[q] - t4;
                     hi[q] = s_ihi[q] - t4;
                     s_clo[q] = lo[q];
@@ -1205,32 +1054,19 @@ __global__ void __launch_bounds__(256 * kTailSub) k_q_tail(const uint8_t *__rest
             __syncthreads();
             if (sw == 0) {
                 pairwise_combine<float, 128, 8, true>(nlev, lane, tree, V);
-                if (lane == 0) {
-                    const float t1 = ((S[0] + S[1]) + S[2]) / (float)(3 * (long long)n);
-                    const float t2 = ((S[2] + S[1]) - 2.0f * S[0]) / (float)n;
-                    const float v0 = V[0] / (float)n, v1 = V[1] / (float)n, v2 = V[2] / (float)n;
-                    const float t3 = ((v0 + v1) + v2) / 3.0f;
-                    const double t4 = (double)s_edges[qd] / (double)n;  // int64 / int -> float64
-                    s_q[qd] = (double)((t1 + t2) - t3) - t4;
-                }
+                if (lane == 0) s_q[qd] = quad_score<float>(S, V, (long long)n, s_edges[qd]);
             }
             __syncthreads();
             double score[4];
             for (int q = 0; q < 4; ++q) score[q] = s_q[q];
-            arg = 0;
-            for (int q = 1; q < 4; ++q)
-                if (score[q] > score[arg]) arg = q;  // np.argmax: first maximum
+            arg = quad_argmax(score);
             if (check_mode && threadIdx.x == 0 && status) {  // (see k_q_select)
                 bool bad = false;
                 for (int q = 0; q < 4; ++q) bad = bad || !(score[q] >= s_clo[q] && score[q] <= s_chi[q]);
                 if ((s_dec >> 8) != 0 && (s_dec & 255) != arg) bad = true;
                 if (bad) atomicOr(status, (uint32_t)UWIE_STATUS_QTREE_BOUNDS);
             }
-            if (trace && threadIdx.x == 0) {
-                TraceRec &t = trace[b * kMaxLevels + level];
-                t.y0 = k.y0; t.x0 = k.x0; t.rows = k.rows; t.cols = k.cols;
-                for (int q = 0; q < 4; ++q) t.score[q] = score[q];
-            }
+            if (trace && threadIdx.x == 0) trace_store(trace, b, level, k, score);
         }
 #ifdef UWIE_TAIL_PROF
         if (trace && threadIdx.x == 0) {  // 100 MHz ticks: staging + histogram, gray load, Canny + decision
@@ -1240,10 +1076,7 @@ __global__ void __launch_bounds__(256 * kTailSub) k_q_tail(const uint8_t *__rest
             t.score[3] = (double)(clock64() - k0) / (double)(c3 - c0);
         }
 #endif
-        k = arg == 0   ? Region{b, k.y0, k.x0, mr, mc}
-            : arg == 1 ? Region{b, k.y0, k.x0 + mc, mr, k.cols - mc}
-            : arg == 2 ? Region{b, k.y0 + mr, k.x0, k.rows - mr, mc}
-                       : Region{b, k.y0 + mr, k.x0 + mc, k.rows - mr, k.cols - mc};
+        k = quad_region(b, k, arg);
         __syncthreads();  // s_q and the slices are rewritten by the next level
     }
     if (wid != 0) return;
@@ -1270,8 +1103,6 @@ __global__ void __launch_bounds__(256 * kTailSub) k_q_tail(const uint8_t *__rest
         A[b * 3 + 2] = px_val(p[2], px_atten(knd, 2));
     }
 }
-
-int max_chunks(Shape s) { return cdiv((long long)((s.H + 1) / 2) * ((s.W + 1) / 2), kNpChunk); }
 
 LevelBufs carve_level(Carver &c, Shape s)
 {

@@ -32,6 +32,7 @@
 // every candidate is strong) that removes almost all labelling work; the standalone edge map keeps every candidate.
 #include "common.h"
 #include "devutil.h"
+#include "lane_hist.h"
 
 #include <cstdlib>
 
@@ -57,7 +58,6 @@ struct CannyBufs {
 };
 
 typedef short v2s __attribute__((ext_vector_type(2)));
-typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
 
 constexpr int kCT_H = 32, kCT_W = 64;      // output tile
 constexpr int kSG_H = kCT_H + 4, kSG_W = 72;  // gray tile: 2-pixel halo, rows padded to a multiple of 8 bytes
@@ -268,15 +268,15 @@ __global__ void __launch_bounds__(256) k_gray_strong(const uint8_t *__restrict__
 // ---- levels >= 1 of the quadtree (round 4): the quadrants' byte histograms AND the pre-pass in one sweep ---------------
 // k_q_hist (k_airlight.hip) and k_canny_strong stream over the same four quadrants of the chosen block, one after the
 // other: the first is bound by its LDS atomics, the second by its packed arithmetic.  Here one wavefront does both for its
-// strip and band -- per row three dwords of RGB for the histogram (the lane-column words of k_chunk_hist: the bank of an
+// strip and band -- per row three dwords of RGB for the histogram (the lane-column histogram of lane_hist.h: the bank of an
 // atomic is the lane's column) next to the 8 gray bytes of the Sobel window -- so the two instruction streams share the
 // wavefront's issue slots and a level costs one launch less.  Requires quadrant widths and origins that are multiples of
 // four (the host checks (W >> level) % 8 == 0).  A block = four bands of one strip; its histogram is folded after 16 rows
 // (10-bit fields: a column takes 2 lanes x 4 wavefronts x 4 pixels per row) and at the end, then added to the region's.
 template <bool EDGE>
 __device__ void hs_body(const uint8_t *__restrict__ g, const uint8_t *__restrict__ rgb, int W, const Region &r, int x0, int y0,
-                        int lane, int tid, int high, uint32_t *__restrict__ strong_flag, uint32_t *__restrict__ hist_reg, uint32_t *h,
-                        uint32_t *cnt)
+                        int lane, int tid, int high, uint32_t *__restrict__ strong_flag, uint32_t *__restrict__ hist_reg, uint32_t (&h)[kLaneHistWords],
+                        uint32_t (&cnt)[768])
 {
     const int x = x0 + 4 * lane;
     const bool rows_on = y0 < r.rows, counted = x + 4 <= r.cols;
@@ -292,25 +292,9 @@ __device__ void hs_body(const uint8_t *__restrict__ g, const uint8_t *__restrict
     auto gload = [&](int y) -> uint64_t {
         return *reinterpret_cast<const u64_unaligned *>(gbase + (size_t)min(max(y, 0), r.rows - 1) * W);
     };
-    const uint32_t colb = (uint32_t)(tid & 31) * 4u;
-    char *hb = reinterpret_cast<char *>(h);
-    auto bump = [&](uint32_t moved, uint32_t inc) { atomicAdd(reinterpret_cast<uint32_t *>(hb + ((moved & 0x7f80u) | colb)), inc); };
-    constexpr uint32_t kR = 1u, kG = 1u << 10, kB = 1u << 20;
-    auto fold = [&]() {  // all threads; thread v folds the 32 columns of value v into the 32-bit totals and clears them
-        __syncthreads();
-        uint32_t cr = 0, cg = 0, cb = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            uint4 *wq = reinterpret_cast<uint4 *>(&h[tid * 32 + 4 * ((tid + k) & 7)]);
-            const uint4 w = *wq;
-            *wq = make_uint4(0, 0, 0, 0);
-            cr += (w.x & 1023u) + (w.y & 1023u) + (w.z & 1023u) + (w.w & 1023u);
-            cg += ((w.x >> 10) & 1023u) + ((w.y >> 10) & 1023u) + ((w.z >> 10) & 1023u) + ((w.w >> 10) & 1023u);
-            cb += (w.x >> 20) + (w.y >> 20) + (w.z >> 20) + (w.w >> 20);
-        }
-        cnt[tid] += cr; cnt[256 + tid] += cg; cnt[512 + tid] += cb;
-        __syncthreads();
-    };
+    const LaneHist lh(h, tid);
+    constexpr int kFoldRows = 16;  // rows of a band between two folds: eight threads of a column x 4 pixels per row
+    static_assert(kPreRows == 2 * kFoldRows && kFoldRows * (256 / kLaneHistCols) * 4 <= kLaneHistField, "10-bit fields");
     bool sobel = rows_on && !narrow && !__hip_atomic_load(strong_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (wavefront-uniform)
     PreRow a{}, b{};
     if (sobel) {
@@ -334,14 +318,7 @@ __device__ void hs_body(const uint8_t *__restrict__ g, const uint8_t *__restrict
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 if (yb + i < y1) {
-                    if (counted) {
-                        const uint32_t c0 = c[i][0], c1 = c[i][1], c2 = c[i][2];
-                        // R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
-                        bump(c0 << 7, kR); bump(c0 >> 1, kG); bump(c0 >> 9, kB);
-                        bump(c0 >> 17, kR); bump(c1 << 7, kG); bump(c1 >> 1, kB);
-                        bump(c1 >> 9, kR); bump(c1 >> 17, kG); bump(c2 << 7, kB);
-                        bump(c2 >> 1, kR); bump(c2 >> 9, kG); bump(c2 >> 17, kB);
-                    }
+                    if (counted) lh.add4(c[i][0], c[i][1], c[i][2]);
                     if (sobel) {
                         const PreRow cc = pre_row<EDGE>(w[i], sh);
                         const v2s dx0 = a.hd0 + b.hd0 + b.hd0 + cc.hd0, dx1 = a.hd1 + b.hd1 + b.hd1 + cc.hd1;
@@ -354,11 +331,10 @@ __device__ void hs_body(const uint8_t *__restrict__ g, const uint8_t *__restrict
                 }
             }
         }
-        if (blk == 1) fold();
+        if (blk == kFoldRows / 8 - 1) LaneHist::fold_totals(h, tid, cnt);
     }
-    fold();
-    for (int i = tid; i < 768; i += 256)
-        if (cnt[i]) atomicAdd(&hist_reg[i], cnt[i]);
+    LaneHist::fold_totals(h, tid, cnt);
+    LaneHist::flush(tid, cnt, hist_reg, 0);
     if (rows_on && narrow) {
         if (lane == 0) *strong_flag = 1;
         return;
@@ -376,14 +352,14 @@ __global__ void __launch_bounds__(256) k_hist_strong(const uint8_t *__restrict__
                                                      const Region *__restrict__ regs, int H, int W, int strips, int high,
                                                      uint32_t *__restrict__ strong, uint32_t *__restrict__ hist)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t h[256 * 32];
+    __shared__ __attribute__((aligned(16))) uint32_t h[kLaneHistWords];
     __shared__ uint32_t cnt[768];
     const Region r = regs[blockIdx.y];
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int strip = blockIdx.x % strips, band = (blockIdx.x / strips) * 4 + wv;
     const int x0 = strip * kPreCols, y0 = band * kPreRows;
     if (r.rows <= 0 || r.cols < 4 || x0 >= r.cols || (int)(blockIdx.x / strips) * 4 * kPreRows >= r.rows) return;  // (block-uniform)
-    for (int i = tid; i < 256 * 32 / 4; i += 256) reinterpret_cast<uint4 *>(h)[i] = make_uint4(0, 0, 0, 0);
+    LaneHist::zero(h, tid);
     for (int i = tid; i < 768; i += 256) cnt[i] = 0;
     // (the first fold's barrier orders the clears before the first atomics of the OTHER wavefronts; this one for its own)
     __syncthreads();

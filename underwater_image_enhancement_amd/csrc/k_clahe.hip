@@ -12,7 +12,6 @@ namespace uwie {
 
 namespace {
 
-__device__ __forceinline__ uint8_t sat_u8(int v) { return (uint8_t)min(max(v, 0), 255); }
 #define UWIE_DESCALE(x, n) (((x) + (1 << ((n)-1))) >> (n))
 
 __device__ __forceinline__ void rgb2lab_px(const LabTables *__restrict__ T, uint32_t r8, uint32_t g8, uint32_t b8,
@@ -102,18 +101,6 @@ struct ClaheGeom {
     int clip;                  // integer clip limit, 0 = no clipping
     float lutScale;            // 255 / tile area
 };
-
-// block-wide exclusive/inclusive helpers over 256 threads
-__device__ __forceinline__ uint32_t block_incl_scan_256(uint32_t v, uint32_t *wsum)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t incl = wave_incl_scan_u32(v);
-    __syncthreads();
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    for (int i = 0; i < w; ++i) incl += wsum[i];
-    return incl;
-}
 
 // grid (tx*ty, B), block 256.  src: u8 plane with pixel stride `ps` bytes.
 __global__ void __launch_bounds__(256) k_clahe_lut(const uint8_t *__restrict__ src, int ps, ClaheGeom g,

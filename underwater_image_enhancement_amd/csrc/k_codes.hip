@@ -17,7 +17,6 @@ namespace uwie {
 
 namespace {
 
-__device__ __forceinline__ uint8_t sat_u8(int v) { return (uint8_t)min(max(v, 0), 255); }
 #define UWIE_DESCALE(x, n) (((x) + (1 << ((n)-1))) >> (n))
 
 // ------------------------------------------------------------------ histograms of u8 HWC frames
@@ -69,17 +68,6 @@ __device__ __forceinline__ T np_lerp_t(T a, T b, T t)
     T r = a + diff * t;
     if (t >= (T)0.5) r = b - diff * ((T)1 - t);
     return r;
-}
-
-__device__ __forceinline__ uint32_t block_incl_scan_256(uint32_t v, uint32_t *wsum)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t incl = wave_incl_scan_u32(v);
-    __syncthreads();
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    for (int i = 0; i < w; ++i) incl += wsum[i];
-    return incl;
 }
 
 // grid (3, B), block 256: thread u evaluates the chain for input code u of channel blockIdx.x

@@ -16,6 +16,7 @@
 //     plain sequential float adds only for the 16 pixels around the event (and for the frame's first 1024 pixels).
 #include "common.h"
 #include "devutil.h"
+#include "lane_hist.h"
 
 namespace uwie {
 
@@ -26,38 +27,57 @@ constexpr int kChunkPx = 16384;  // pixels per histogram chunk
 // then depends on the parity of the running sum and the chunk has to be walked).
 constexpr uint64_t kTieBit = 1ull << 63;
 
-// Round 3 layout of the chunk histogram: one 32-bit word per (byte value, lane column), the three channels' counters in
-// 10-bit fields of that word.  The LDS bank of an atomic is then the lane's column (lane & 31 -- `ds_add_u32` is serviced in
-// the two 32-lane halves, banks (a/4) mod 32), never the pixel's value: no bank conflicts whatever the picture, where the
-// value-indexed copies of rounds 1-2 spent 72 % of their LDS cycles on conflicts (neighbouring pixels share their values).
-// A column receives 16384 / 32 = 512 pixels of a chunk (+1 for a ragged tail), so a field cannot overflow.
+// The chunk histogram is a lane-column histogram (lane_hist.h).  A column receives 16384 / 32 = 512 pixels of a chunk (+1 for
+// a ragged tail), so a field cannot overflow.
 // Output per chunk: the 768 counts as 16-bit pairs (values 2j and 2j+1 of a channel in one word: the operand layout of
 // v_dot2_u32_u16 in k_chunk_ulps), and one byte per (channel, binade) telling whether a present value ties there (a byte
 // value ties in exactly one binade, CastTables::tiebin).
-constexpr int kHistCols = 32;
 constexpr int kPairs = 3 * kCastBinades;
-static_assert(kChunkPx / kHistCols + 3 < 1024, "10-bit fields");
+static_assert(kChunkPx / kLaneHistCols + 3 <= kLaneHistField, "10-bit fields");
 static_assert(kChunkPx < 65536, "16-bit counts");
+
+// What k_chunk_hist and k_chunk_hist_quad share.  Set-up: cleared histogram words and tie flags.
+__device__ __forceinline__ void chunk_setup(uint32_t (&h)[kLaneHistWords], uint32_t *s_tie, int tid)
+{
+    LaneHist::zero(h, tid);
+    if (tid < kPairs) s_tie[tid] = 0;
+    __syncthreads();
+}
+// thread v's three counts of byte value v as 16-bit pairs: out384[channel * 128 + v / 2]
+__device__ __forceinline__ void store_pairs(uint32_t *out384, int tid, uint32_t r, uint32_t g, uint32_t bl)
+{
+    const uint32_t r2 = r | (__shfl_down(r, 1) << 16), g2 = g | (__shfl_down(g, 1) << 16), b2 = bl | (__shfl_down(bl, 1) << 16);
+    if (!(tid & 1)) {
+        uint32_t *out = out384 + (tid >> 1);
+        out[0] = r2; out[128] = g2; out[256] = b2;
+    }
+}
+// Epilogue: the chunk's counts (r, g, bl of byte value tid; tb = that value's tie binade) -> pairs and tie flags
+__device__ __forceinline__ void chunk_epilogue(uint32_t tb, uint32_t r, uint32_t g, uint32_t bl, uint32_t *s_tie,
+                                               uint32_t *__restrict__ hist2, uint8_t *__restrict__ ties, size_t chunk, int tid)
+{
+    if (tb < (uint32_t)kCastBinades) {  // same-value stores: no atomics needed
+        if (r) s_tie[tb] = 1;
+        if (g) s_tie[kCastBinades + tb] = 1;
+        if (bl) s_tie[2 * kCastBinades + tb] = 1;
+    }
+    store_pairs(hist2 + chunk * 384, tid, r, g, bl);
+    __syncthreads();
+    if (tid < kPairs) ties[chunk * kPairs + tid] = (uint8_t)s_tie[tid];
+}
 
 __global__ void __launch_bounds__(256) k_chunk_hist(const uint8_t *__restrict__ in, const CastTables *__restrict__ tab,
                                                     uint32_t *__restrict__ hist2, uint8_t *__restrict__ ties, int npx,
                                                     int nchunk)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t h[256 * kHistCols];
+    __shared__ __attribute__((aligned(16))) uint32_t h[kLaneHistWords];
     __shared__ uint32_t s_tie[kPairs];
     const int b = blockIdx.y, c = blockIdx.x, tid = threadIdx.x;
     const uint32_t tb = tab->tiebin[tid];
-    for (int i = tid; i < 256 * kHistCols / 4; i += 256) reinterpret_cast<uint4 *>(h)[i] = make_uint4(0, 0, 0, 0);
-    if (tid < kPairs) s_tie[tid] = 0;
-    __syncthreads();
+    chunk_setup(h, s_tie, tid);
     const uint8_t *img = in + (size_t)b * npx * 3;
     const int p0 = c * kChunkPx, p1 = min(npx, p0 + kChunkPx);
-    const uint32_t colb = (uint32_t)(tid & (kHistCols - 1)) * 4u;
-    char *hb = reinterpret_cast<char *>(h);
-    typedef uint32_t __attribute__((aligned(1))) u32_any;
-    // byte address of (value, column): value * 128 + column * 4; the caller shifts the value's byte to bit 7 of the word
-    auto bump = [&](uint32_t moved, uint32_t inc) { atomicAdd(reinterpret_cast<uint32_t *>(hb + ((moved & 0x7f80u) | colb)), inc); };
-    constexpr uint32_t kR = 1u, kG = 1u << 10, kB = 1u << 20;
+    const LaneHist lh(h, tid);
     // whole groups of four pixels (12 bytes, any alignment: three dword loads); a thread's next kAhead groups are loaded
     // (unconditionally, index clamped: no branch for the compiler to park a vmcnt(0) in) before the atomics of this batch
     const int nfull = (p1 - p0) >> 2;
@@ -68,21 +88,14 @@ __global__ void __launch_bounds__(256) k_chunk_hist(const uint8_t *__restrict__ 
 #pragma unroll
             for (int i = 0; i < kAhead; ++i) {
                 const int g = min(base + i * 256, nfull - 1);
-                const u32_any *q = reinterpret_cast<const u32_any *>(img + (size_t)(p0 + 4 * g) * 3);
+                const u32_unaligned *q = reinterpret_cast<const u32_unaligned *>(img + (size_t)(p0 + 4 * g) * 3);
                 d[i][0] = q[0]; d[i][1] = q[1]; d[i][2] = q[2];
             }
         };
         auto consume = [&](int base, const uint32_t (&d)[kAhead][3]) {
 #pragma unroll
             for (int i = 0; i < kAhead; ++i) {
-                if (base + i * 256 < nfull) {
-                    const uint32_t c0 = d[i][0], c1 = d[i][1], c2 = d[i][2];
-                    // R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
-                    bump(c0 << 7, kR); bump(c0 >> 1, kG); bump(c0 >> 9, kB);
-                    bump(c0 >> 17, kR); bump(c1 << 7, kG); bump(c1 >> 1, kB);
-                    bump(c1 >> 9, kR); bump(c1 >> 17, kG); bump(c2 << 7, kB);
-                    bump(c2 >> 1, kR); bump(c2 >> 9, kG); bump(c2 >> 17, kB);
-                }
+                if (base + i * 256 < nfull) lh.add4(d[i][0], d[i][1], d[i][2]);
             }
         };
         // two buffers taking turns (a register copy at the end of a trip would wait for the loads it copies)
@@ -96,34 +109,10 @@ __global__ void __launch_bounds__(256) k_chunk_hist(const uint8_t *__restrict__ 
         }
     }
     // the chunk's last one to three pixels (frames whose pixel count is no multiple of four)
-    for (int p = p0 + 4 * nfull + tid; p < p1; p += 256) {
-        bump((uint32_t)img[(size_t)p * 3] << 7, kR);
-        bump((uint32_t)img[(size_t)p * 3 + 1] << 7, kG);
-        bump((uint32_t)img[(size_t)p * 3 + 2] << 7, kB);
-    }
+    for (int p = p0 + 4 * nfull + tid; p < p1; p += 256) lh.add1(img + (size_t)p * 3);
     __syncthreads();
-    // thread v folds the 32 columns of value v (rotated start: lane l reads bank l + k)
-    uint32_t r = 0, g = 0, bl = 0;
-#pragma unroll 8
-    for (int k = 0; k < kHistCols; ++k) {
-        const uint32_t w = h[tid * kHistCols + ((tid + k) & (kHistCols - 1))];
-        r += w & 1023u;
-        g += (w >> 10) & 1023u;
-        bl += w >> 20;
-    }
-    if (tb < (uint32_t)kCastBinades) {  // same-value stores: no atomics needed
-        if (r) s_tie[tb] = 1;
-        if (g) s_tie[kCastBinades + tb] = 1;
-        if (bl) s_tie[2 * kCastBinades + tb] = 1;
-    }
-    const uint32_t r2 = r | (__shfl_down(r, 1) << 16), g2 = g | (__shfl_down(g, 1) << 16), b2 = bl | (__shfl_down(bl, 1) << 16);
-    const size_t chunk = (size_t)b * nchunk + c;
-    if (!(tid & 1)) {
-        uint32_t *out = hist2 + chunk * 384 + (tid >> 1);
-        out[0] = r2; out[128] = g2; out[256] = b2;
-    }
-    __syncthreads();
-    if (tid < kPairs) ties[chunk * kPairs + tid] = (uint8_t)s_tie[tid];
+    const uint3 f = LaneHist::fold_b32(h, tid);
+    chunk_epilogue(tb, f.x, f.y, f.z, s_tie, hist2, ties, (size_t)b * nchunk + c, tid);
 }
 
 // ---- round 4 (tuning entry_fuse): the level-0 quadrant histograms of the quadtree out of the same pass ----------------
@@ -160,10 +149,8 @@ __device__ __forceinline__ bool quad_phase(int p0, int p1, int H, int W, int q, 
 // 0 none -- launch_cast_classify repairs the frames whose guess turns out wrong).  gside: the gray plane at the side's column.
 template <int ATT>
 __device__ __forceinline__ void chunk_phase(const uint8_t *__restrict__ side, uint8_t *__restrict__ gside, int W, int Gh, int ra, int ga,
-                                            int n, int tid, char *hb, uint32_t colb, float cr, float cg, float cb)
+                                            int n, int tid, const LaneHist lh, float cr, float cg, float cb)
 {
-    auto bump = [&](uint32_t moved, uint32_t inc) { atomicAdd(reinterpret_cast<uint32_t *>(hb + ((moved & 0x7f80u) | colb)), inc); };
-    constexpr uint32_t kR = 1u, kG = 1u << 10, kB = 1u << 20;
     constexpr int kAhead = 4, kStep = kAhead * 256, kWords = ATT >= 0 ? 4 : 3;
     const int dr = 256 / Gh, dg = 256 - dr * Gh;  // a step of 256 groups in (row, group) terms
     const uint32_t px_safe = (uint32_t)(ra * W + 4 * ga);
@@ -187,10 +174,7 @@ __device__ __forceinline__ void chunk_phase(const uint8_t *__restrict__ side, ui
         for (int i = 0; i < kAhead; ++i) {
             if (j0 + i * 256 < n) {
                 const uint32_t c0 = d[i][0], c1 = d[i][1], c2 = d[i][2];
-                bump(c0 << 7, kR); bump(c0 >> 1, kG); bump(c0 >> 9, kB);
-                bump(c0 >> 17, kR); bump(c1 << 7, kG); bump(c1 >> 1, kB);
-                bump(c1 >> 9, kR); bump(c1 >> 17, kG); bump(c2 << 7, kB);
-                bump(c2 >> 1, kR); bump(c2 >> 9, kG); bump(c2 >> 17, kB);
+                lh.add4(c0, c1, c2);
                 if constexpr (ATT >= 0) {
                     const uint32_t w3[3] = {c0, c1, c2};
                     *reinterpret_cast<uint32_t *>(gside + d[i][3]) = gray4_f32<ATT>(w3, cr, cg, cb);
@@ -215,19 +199,16 @@ __global__ void __launch_bounds__(256) k_chunk_hist_quad(const uint8_t *__restri
                                                          uint8_t *__restrict__ gray_out, const int32_t *__restrict__ guess, float cr,
                                                          float cg, float cb)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t h[256 * kHistCols];
+    __shared__ __attribute__((aligned(16))) uint32_t h[kLaneHistWords];
     __shared__ uint32_t s_tie[kPairs];
     const int b = blockIdx.y, c = blockIdx.x, tid = threadIdx.x;
     const uint32_t tb = tab->tiebin[tid];
-    for (int i = tid; i < 256 * kHistCols / 4; i += 256) reinterpret_cast<uint4 *>(h)[i] = make_uint4(0, 0, 0, 0);
-    if (tid < kPairs) s_tie[tid] = 0;
-    __syncthreads();
+    chunk_setup(h, s_tie, tid);
     const uint8_t *img = in + (size_t)b * npx * 3;
     uint8_t *gimg = gray_out ? gray_out + (size_t)b * npx : nullptr;
     const int att = gray_out ? guess[b] : -1;  // (block-uniform)
     const int p0 = c * kChunkPx, p1 = min(npx, p0 + kChunkPx);
-    const uint32_t colb = (uint32_t)(tid & (kHistCols - 1)) * 4u;
-    char *hb = reinterpret_cast<char *>(h);
+    const LaneHist lh(h, tid);
     const int Gh = W >> 3;
     uint32_t tr = 0, tg = 0, tbl = 0;  // the chunk's counts of byte value `tid`
     for (int q = 0; q < 4; ++q) {
@@ -236,25 +217,16 @@ __global__ void __launch_bounds__(256) k_chunk_hist_quad(const uint8_t *__restri
         const int xs = (q & 1) ? (W >> 1) : 0;
         const uint8_t *side = img + (size_t)xs * 3;
         uint8_t *gside = gimg + xs;
-        if (att < 0) chunk_phase<-1>(side, gside, W, Gh, ra, ga, n, tid, hb, colb, cr, cg, cb);
-        else if (att == 1) chunk_phase<1>(side, gside, W, Gh, ra, ga, n, tid, hb, colb, cr, cg, cb);
-        else if (att == 2) chunk_phase<2>(side, gside, W, Gh, ra, ga, n, tid, hb, colb, cr, cg, cb);
-        else chunk_phase<0>(side, gside, W, Gh, ra, ga, n, tid, hb, colb, cr, cg, cb);
+        if (att < 0) chunk_phase<-1>(side, gside, W, Gh, ra, ga, n, tid, lh, cr, cg, cb);
+        else if (att == 1) chunk_phase<1>(side, gside, W, Gh, ra, ga, n, tid, lh, cr, cg, cb);
+        else if (att == 2) chunk_phase<2>(side, gside, W, Gh, ra, ga, n, tid, lh, cr, cg, cb);
+        else chunk_phase<0>(side, gside, W, Gh, ra, ga, n, tid, lh, cr, cg, cb);
         __syncthreads();
-        // thread v folds (and clears) the 32 columns of value v: this quadrant's share of the chunk.  Four columns per LDS
-        // instruction, the quads taken in a rotated order (eight neighbouring lanes cover the 32 banks): the fold is a quarter
-        // of the LDS instructions of the b32 version, which made the two folds of a chunk cost as much as a third of its atomics
-        uint32_t r = 0, g = 0, bl = 0;
-#pragma unroll
-        for (int k = 0; k < kHistCols / 4; ++k) {
-            uint4 *wq = reinterpret_cast<uint4 *>(&h[tid * kHistCols + 4 * ((tid + k) & (kHistCols / 4 - 1))]);
-            const uint4 w = *wq;
-            *wq = make_uint4(0, 0, 0, 0);
-            r += (w.x & 1023u) + (w.y & 1023u) + (w.z & 1023u) + (w.w & 1023u);
-            g += ((w.x >> 10) & 1023u) + ((w.y >> 10) & 1023u) + ((w.z >> 10) & 1023u) + ((w.w >> 10) & 1023u);
-            bl += (w.x >> 20) + (w.y >> 20) + (w.z >> 20) + (w.w >> 20);
-        }
+        // this quadrant's share of the chunk (folded and cleared)
+        const uint3 f = LaneHist::fold_b128(h, tid);
+        const uint32_t r = f.x, g = f.y, bl = f.z;
         tr += r; tg += g; tbl += bl;
+        // (written out, not store_pairs: the call moved its address arithmetic in front of the phases' loops)
         const uint32_t r2 = r | (__shfl_down(r, 1) << 16), g2 = g | (__shfl_down(g, 1) << 16), b2 = bl | (__shfl_down(bl, 1) << 16);
         if (!(tid & 1)) {
             uint32_t *out = qpart + (((size_t)b * nchunk + c) * 4 + q) * 384 + (tid >> 1);
@@ -262,19 +234,7 @@ __global__ void __launch_bounds__(256) k_chunk_hist_quad(const uint8_t *__restri
         }
         __syncthreads();
     }
-    if (tb < (uint32_t)kCastBinades) {  // same-value stores: no atomics needed
-        if (tr) s_tie[tb] = 1;
-        if (tg) s_tie[kCastBinades + tb] = 1;
-        if (tbl) s_tie[2 * kCastBinades + tb] = 1;
-    }
-    const uint32_t r2 = tr | (__shfl_down(tr, 1) << 16), g2 = tg | (__shfl_down(tg, 1) << 16), b2 = tbl | (__shfl_down(tbl, 1) << 16);
-    const size_t chunk = (size_t)b * nchunk + c;
-    if (!(tid & 1)) {
-        uint32_t *out = hist2 + chunk * 384 + (tid >> 1);
-        out[0] = r2; out[128] = g2; out[256] = b2;
-    }
-    __syncthreads();
-    if (tid < kPairs) ties[chunk * kPairs + tid] = (uint8_t)s_tie[tid];
+    chunk_epilogue(tb, tr, tg, tbl, s_tie, hist2, ties, (size_t)b * nchunk + c, tid);
 }
 
 // The cast kind of a frame guessed from a strided sample of its pixels (exact integer means of the sample, the reference's
@@ -291,7 +251,6 @@ __global__ void __launch_bounds__(kGuessThreads) k_kind_guess(const uint8_t *__r
     const uint8_t *img = in + (size_t)b * npx * 3;
     const int n = min(npx, kGuessPx);
     const uint32_t stride = (uint32_t)(npx / n);
-    typedef uint32_t __attribute__((aligned(1))) u32_any;
     uint32_t w[kGuessPer];
     // a pixel = the low three bytes of one (unaligned) dword; all of a thread's loads in flight.  The last pixel of the last
     // frame is read as the dword that ENDS at its last byte.
@@ -300,7 +259,7 @@ __global__ void __launch_bounds__(kGuessThreads) k_kind_guess(const uint8_t *__r
         const int i = min(tid + k * kGuessThreads, n - 1);
         const size_t px = (size_t)i * stride;
         const bool tail = px + 1 >= (size_t)npx;
-        const uint32_t v = *reinterpret_cast<const u32_any *>(img + px * 3 - (tail ? 1 : 0));
+        const uint32_t v = *reinterpret_cast<const u32_unaligned *>(img + px * 3 - (tail ? 1 : 0));
         w[k] = tail ? v >> 8 : v;
     }
     uint32_t r = 0, g = 0, bl = 0;
@@ -433,8 +392,6 @@ __device__ __forceinline__ float from_mantissa(uint32_t S, int e)
 {
     return __uint_as_float(((uint32_t)(e + 127) << 23) | (S & 0x7fffffu));
 }
-
-typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
 
 // ---- k_cast_resolve: one block of 16 wavefronts per (image, channel).
 // Wavefront 0 walks the chunks 64 at a time: lane j holds the ulp count of chunk c+j for the current binade, a prefix scan

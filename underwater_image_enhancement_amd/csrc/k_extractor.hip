@@ -29,15 +29,7 @@ constexpr size_t kFxGlcmLds = 256 * 256 * 2 + 256 * 4;  // u16 counts + |i - j| 
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ uint8_t sat_u8(int v) { return (uint8_t)min(max(v, 0), 255); }
 #define UWIE_DESCALE(x, n) (((x) + (1 << ((n)-1))) >> (n))
-
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __longlong_as_double((long long)shfl_xor_u64((uint64_t)__double_as_longlong(v), o));
-    return v;
-}
 
 __device__ __forceinline__ float key_f32(uint32_t k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
 

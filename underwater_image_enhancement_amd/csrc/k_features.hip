@@ -15,7 +15,6 @@ namespace uwie {
 namespace {
 
 constexpr int kNFeat = 79;
-typedef uint4 __attribute__((aligned(1))) u128_unaligned;
 
 // MODE 0: {x, x*x, 0}   MODE 1: {(x - mean)^2, 0, 0}
 template <int MODE>

@@ -7,20 +7,19 @@
 // parity, not speed: nothing here is fused.
 //   k_f_prepare      [color_correction (S6:305-323)] and (x * 255).astype(uint8) (S6:149,177,204, ES:180,228,299,339)
 //   k_f_mean_seq     img.mean(axis=(0,1)): sequential accumulation per channel in the image's dtype (S6:294)
-//   k_fq_chunk_sums  compute_Q's np.sum / np.mean / squared deviations in NumPy's pairwise order (S6:134-147)
-//   k_fq_select      compute_Q's score and the greedy step (S6:100-111,152-155)
+//   k_fq_chunk_sums  compute_Q's np.sum / np.mean / squared deviations in NumPy's pairwise order (S6:134-147): quadtree.h's leaf sums
+//   k_fq_select      compute_Q's score and the greedy step (S6:100-111,152-155): quadtree.h's score, argmax and descent
 //   k_f_brightest    get_brightest_pixel (S6:160-165)
 //   k_f_trans_init   1 - omega * min_c(img / (A + eps)) [clip] (S6:170-174, ES:221-225)
 //   k_f_restore      restore_image (S6:183-188) / recover_image (ES:237-249)
 #include "common.h"
 #include "devutil.h"
 #include "pairwise_tree.h"
+#include "quadtree.h"
 
 namespace uwie {
 
 namespace {
-
-constexpr int kMaxLevelsF = 32;
 
 template <class T>
 __global__ void k_f_prepare(const T *__restrict__ x, const int32_t *__restrict__ kind, T *__restrict__ xc, uint8_t *__restrict__ q,
@@ -72,6 +71,9 @@ __global__ void k_f_mean_seq(const T *__restrict__ x, size_t npx, int B, float *
 // ---- quadtree statistics on a float image
 template <class T, bool VAR>
 struct ElemF {
+    using src_t = T;
+    using val_t = T;
+    static constexpr bool kVar = VAR;
     const T *img;  // one image, HWC
     int W;
     T mean[3];
@@ -85,58 +87,6 @@ struct ElemF {
         return v;
     }
 };
-
-// NumPy's pairwise_sum on a block of n <= 128 elements starting at raster element e0 of region r, three channels at once
-template <class T, bool VAR>
-__device__ void leaf_sum3f(const ElemF<T, VAR> &el, const Region &r, int e0, int n, T out[3])
-{
-    int ly = e0 / r.cols, lx = e0 % r.cols;
-    const T *p = el.img + ((size_t)(r.y0 + ly) * el.W + r.x0 + lx) * 3;
-    auto step = [&]() {
-        ++lx;
-        p += 3;
-        if (lx == r.cols) {
-            lx = 0;
-            p += (size_t)(el.W - r.cols) * 3;
-        }
-    };
-    if (n < 8) {
-        T a0 = 0, a1 = 0, a2 = 0;
-        for (int i = 0; i < n; ++i) {
-            a0 += el.get(p, 0);
-            a1 += el.get(p, 1);
-            a2 += el.get(p, 2);
-            step();
-        }
-        out[0] = a0; out[1] = a1; out[2] = a2;
-        return;
-    }
-    T acc[3][8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c][j] = el.get(p, c);
-        step();
-    }
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) acc[c][j] += el.get(p, c);
-            step();
-        }
-    }
-    T res[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) res[c] = tree8<T>(acc[c]);
-    for (; i < n; ++i) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) res[c] += el.get(p, c);
-        step();
-    }
-    out[0] = res[0]; out[1] = res[1]; out[2] = res[2];
-}
 
 // one wavefront per (chunk, region); VAR: the means are derived from the sums pass's chunk sums (csum_in)
 template <class T, bool VAR>
@@ -168,7 +118,7 @@ __global__ void __launch_bounds__(64) k_fq_chunk_sums(const T *__restrict__ in, 
     T *out = csum + ((size_t)reg * maxChunks + ci) * 3;
     T res[3];
     if (len == kNpChunk) {
-        leaf_sum3f<T, VAR>(el, r, c0 + lane * 128, 128, res);
+        leaf_sum3(el, r, c0 + lane * 128, 128, res);
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
 #pragma unroll
@@ -178,20 +128,15 @@ __global__ void __launch_bounds__(64) k_fq_chunk_sums(const T *__restrict__ in, 
             }
         }
     } else {
-        pairwise_ragged<T>(len, lane, tree, [&](int off, int l, T *s3) { leaf_sum3f<T, VAR>(el, r, c0 + off, l, s3); }, res);
+        pairwise_ragged<T>(len, lane, tree, [&](int off, int l, T *s3) { leaf_sum3(el, r, c0 + off, l, s3); }, res);
     }
     if (lane == 0) { out[0] = res[0]; out[1] = res[1]; out[2] = res[2]; }
 }
 
-struct TraceRecF {
-    int32_t y0, x0, rows, cols;
-    double score[4];
-};
-
 template <class T>
 __global__ void __launch_bounds__(64) k_fq_select(Region *__restrict__ blk, Region *__restrict__ regs, const T *__restrict__ csum,
                                                   const T *__restrict__ csum_var, int maxChunks, uint32_t *__restrict__ edges,
-                                                  int level, int min_size, TraceRecF *__restrict__ trace)
+                                                  int level, int min_size, TraceRec *__restrict__ trace)
 {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (regs[b * 4].rows == 0) return;  // leaf reached earlier
@@ -207,41 +152,13 @@ __global__ void __launch_bounds__(64) k_fq_select(Region *__restrict__ blk, Regi
     if (lane < 24) tots[lane] = acc;
     __syncthreads();
     if (lane != 0) return;
-    double best = 0.0;
-    int arg = 0;
     double score[4];
     for (int q = 0; q < 4; ++q) {
         const Region r = regs[b * 4 + q];
-        const long long n = (long long)r.rows * r.cols;
-        const T *S = tots + q * 6, *V = tots + q * 6 + 3;
-        const T t1 = ((S[0] + S[1]) + S[2]) / (T)(3 * n);
-        const T t2 = ((S[2] + S[1]) - (T)2 * S[0]) / (T)n;
-        const T v0 = V[0] / (T)n, v1 = V[1] / (T)n, v2 = V[2] / (T)n;
-        const T t3 = ((v0 + v1) + v2) / (T)3;
-        const double t4 = (double)edges[b * 4 + q] / (double)n;
-        const double Q = (double)((t1 + t2) - t3) - t4;
-        score[q] = Q;
-        if (q == 0 || Q > best) { best = Q; arg = q; }
+        score[q] = quad_score<T>(tots + q * 6, tots + q * 6 + 3, (long long)r.rows * r.cols, edges[b * 4 + q]);
     }
-    if (trace) {
-        TraceRecF &t = trace[b * kMaxLevelsF + level];
-        const Region k = blk[b];
-        t.y0 = k.y0; t.x0 = k.x0; t.rows = k.rows; t.cols = k.cols;
-        for (int q = 0; q < 4; ++q) t.score[q] = score[q];
-    }
-    const Region k = regs[b * 4 + arg];
-    blk[b] = k;
-    const bool leaf = k.rows <= min_size || k.cols <= min_size;
-    const int mr = k.rows / 2, mc = k.cols / 2;
-    Region q[4] = {{b, k.y0, k.x0, mr, mc},
-                   {b, k.y0, k.x0 + mc, mr, k.cols - mc},
-                   {b, k.y0 + mr, k.x0, k.rows - mr, mc},
-                   {b, k.y0 + mr, k.x0 + mc, k.rows - mr, k.cols - mc}};
-    for (int i = 0; i < 4; ++i) {
-        if (leaf) q[i].rows = q[i].cols = 0;
-        regs[b * 4 + i] = q[i];
-        edges[b * 4 + i] = 0;
-    }
+    if (trace) trace_store(trace, b, level, blk[b], score);
+    q_descend(blk, regs, edges, b, quad_argmax(score), min_size);
 }
 
 __global__ void k_f_init_blocks(Region *blk, Region *regs, uint32_t *edges, int B, int H, int W, int min_size)
@@ -250,17 +167,8 @@ __global__ void k_f_init_blocks(Region *blk, Region *regs, uint32_t *edges, int 
     if (b >= B) return;
     const Region k{b, 0, 0, H, W};
     blk[b] = k;
-    const bool leaf = k.rows <= min_size || k.cols <= min_size;
-    const int mr = k.rows / 2, mc = k.cols / 2;
-    Region q[4] = {{b, k.y0, k.x0, mr, mc},
-                   {b, k.y0, k.x0 + mc, mr, k.cols - mc},
-                   {b, k.y0 + mr, k.x0, k.rows - mr, mc},
-                   {b, k.y0 + mr, k.x0 + mc, k.rows - mr, k.cols - mc}};
-    for (int i = 0; i < 4; ++i) {
-        if (leaf) q[i].rows = q[i].cols = 0;
-        regs[b * 4 + i] = q[i];
-        edges[b * 4 + i] = 0;
-    }
+    quad_split(regs, b, k, min_size);
+    for (int j = 0; j < 4; ++j) edges[b * 4 + j] = 0;
 }
 
 // argmax of (r+g)+b over the leaf (np.sum(block, axis=2) in the image's dtype), first maximum in raster order
@@ -344,8 +252,6 @@ struct FloatLevel {
     uint32_t *edges;
 };
 
-int max_chunks_f(Shape s) { return cdiv((long long)((s.H + 1) / 2) * ((s.W + 1) / 2), kNpChunk); }
-
 template <class T>
 FloatLevel<T> carve_float_level(Carver &c, Shape s)
 {
@@ -353,8 +259,8 @@ FloatLevel<T> carve_float_level(Carver &c, Shape s)
     const size_t nreg = (size_t)s.B * 4;
     L.blk = c.take<Region>(s.B);
     L.regs = c.take<Region>(nreg);
-    L.csum = c.take<T>(nreg * max_chunks_f(s) * 3);
-    L.csum_var = c.take<T>(nreg * max_chunks_f(s) * 3);
+    L.csum = c.take<T>(nreg * max_chunks(s) * 3);
+    L.csum_var = c.take<T>(nreg * max_chunks(s) * 3);
     L.edges = c.take<uint32_t>(nreg);
     return L;
 }
@@ -398,9 +304,9 @@ int launch_float_airlight(const T *d_x, const uint8_t *d_gray, Shape s, int min_
     const int B = s.B, nreg = 4 * B;
     UWIE_LAUNCH(k_f_init_blocks, dim3(cdiv(B, 64)), dim3(64), 0, st, L.blk, L.regs, L.edges, B, s.H, s.W, min_size);
     UWIE_LAUNCH_CHECK();
-    const int maxChunks = max_chunks_f(s);
+    const int maxChunks = max_chunks(s);
     int rmax = s.H, cmax = s.W;
-    for (int level = 0; level < kMaxLevelsF && rmax > min_size && cmax > min_size; ++level) {
+    for (int level = 0; level < kMaxLevels && rmax > min_size && cmax > min_size; ++level) {
         const int qr = (rmax + 1) / 2, qc = (cmax + 1) / 2;
         const int nch = cdiv((long long)qr * qc, kNpChunk);
         UWIE_LAUNCH((k_fq_chunk_sums<T, false>), dim3(nch, nreg), dim3(64), 0, st, d_x, L.regs, s.H, s.W, maxChunks, L.csum,
@@ -412,7 +318,7 @@ int launch_float_airlight(const T *d_x, const uint8_t *d_gray, Shape s, int min_
         const int rc = launch_canny(d_gray, s, L.regs, nreg, qr, qc, 50, 150, L.edges, nullptr, canny_ws, st, true);
         if (rc != UWIE_OK) return rc;
         UWIE_LAUNCH((k_fq_select<T>), dim3(B), dim3(64), 0, st, L.blk, L.regs, (const T *)L.csum, (const T *)L.csum_var, maxChunks,
-                    L.edges, level, min_size, (TraceRecF *)nullptr);
+                    L.edges, level, min_size, (TraceRec *)nullptr);
         UWIE_LAUNCH_CHECK();
         rmax = qr;
         cmax = qc;

@@ -18,11 +18,7 @@ namespace uwie {
 
 namespace {
 
-typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
-typedef uint4 __attribute__((aligned(1))) u128_unaligned;
 
-// np.clip(v, 0, 1) for a value that is not NaN: one instruction (the clamp output modifier)
-__device__ __forceinline__ float clip01(float v) { return __builtin_amdgcn_fmed3f(v, 0.0f, 1.0f); }
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 #ifndef UWIE_CLAHE_PREFETCH
 #define UWIE_CLAHE_PREFETCH 0
@@ -30,7 +26,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #ifndef UWIE_STRETCH_WAVES
 #define UWIE_STRETCH_WAVES 5
 #endif
-__device__ __forceinline__ uint8_t sat_u8(int v) { return (uint8_t)min(max(v, 0), 255); }
 #define UWIE_DESCALE(x, n) (((x) + (1 << ((n)-1))) >> (n))
 
 // grid (nblk, B), block 256.  LIN: the histogram is over lin_digit() (select_lin_*), else over the top 11 key bits.
@@ -335,13 +330,6 @@ constexpr int kRankNW = 2, kRankNS = 3 * kRankNW;
 constexpr int kRankQW = 64 + 64 * 12;  // queue entries per wavefront: fewer than 64 left over + at most 12 per lane and trip
 constexpr int kRankSW = 128;           // stage entries per wavefront and (channel, window): flushed when 64 are there
 
-__device__ __forceinline__ void wave_lds_sync()  // LDS executes a wavefront's instructions in order: a compiler fence is all
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // (free functions with everything passed explicitly: as lambdas, the closure of a closure stayed in scratch memory)
 struct RankWave {  // what one wavefront's exact stage works with
     const uint8_t *img;
@@ -469,10 +457,9 @@ __global__ void __launch_bounds__(256) k_restore_rank(RestoreSrc S, int npx, Lin
                      lists + (size_t)(3 * b) * (kLinLists / kRankCapMul) * cap, cap, lane};
 
     const int step = gridDim.x * 1024, iters = (npx + step - 1) / step;  // block-uniform trip count
-    typedef uint32_t __attribute__((aligned(1))) u32_a1;
 #define UWIE_RANK_LOAD4(p_, w_, tv_)                                                                                   \
     do {                                                                                                                \
-        const u32_a1 *q_ = reinterpret_cast<const u32_a1 *>(img + (size_t)(p_) * 3);                                    \
+        const u32_unaligned *q_ = reinterpret_cast<const u32_unaligned *>(img + (size_t)(p_) * 3);                      \
         (w_)[0] = q_[0]; (w_)[1] = q_[1]; (w_)[2] = q_[2];                                                              \
         const double2_a8 ta_ = *reinterpret_cast<const double2_a8 *>(tpl + (p_)),                                       \
                          tb_ = *reinterpret_cast<const double2_a8 *>(tpl + (p_) + 2);                                   \
@@ -634,17 +621,6 @@ struct ClaheGeom {
     int H, W, tx, ty, tw, th, clip;
     float lutScale;
 };
-
-__device__ __forceinline__ uint32_t block_incl_scan_256(uint32_t v, uint32_t *wsum)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t incl = wave_incl_scan_u32(v);
-    __syncthreads();
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    for (int i = 0; i < w; ++i) incl += wsum[i];
-    return incl;
-}
 
 // grid (tx*ty, B), block 256.  SRC 0: stored planes; 1: the restored image is recomputed from src (restore.h); 2: the
 // code-domain strategies (k_codes.hip): the u8 frame src.in goes through a per-(image, channel) code LUT (codes) and the
@@ -896,7 +872,6 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(BS == 2
     lut[((size_t)b * g.tx * g.ty + tile) * 256 + tid] = sat_u8(__float2int_rn((float)sum * g.lutScale));
 }
 
-__device__ __forceinline__ float pow_f32(float x, float e) { return (float)pow((double)x, (double)e); }
 
 // value of the float image for an 8-bit code v after LAB2RGB: v/255 [-> gamma]; and its output quantisation
 __device__ __forceinline__ float final_value(int v, int gamma_mode, float gexp)

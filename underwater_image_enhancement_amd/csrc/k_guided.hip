@@ -18,7 +18,6 @@ namespace {
 // ---- sources for the row pass.  Raw = what a lane holds per pixel; plane(raw, w) = the value of plane w.
 typedef double2 __attribute__((aligned(8))) gdouble2_a8;
 typedef float4 __attribute__((aligned(4))) gfloat4_a4;
-typedef uint32_t __attribute__((aligned(1))) gu32_a1;
 typedef double gd2v __attribute__((ext_vector_type(2), aligned(8)));
 // The float64 planes are written once and read once, tens of GB behind: nontemporal stores everywhere and nontemporal loads
 // in the column pass (a lane's loads there are whole 512-byte runs of a row) took the four passes from 16.9 to 16.25 ms at
@@ -106,7 +105,7 @@ struct SrcGuideT {
         const size_t i0 = ((size_t)b * H + y) * W + x;
 #pragma unroll
         for (int i = 0; i < N; i += 4) {
-            const uint32_t g4 = *reinterpret_cast<const gu32_a1 *>(gray + i0 + i);
+            const uint32_t g4 = *reinterpret_cast<const u32_unaligned *>(gray + i0 + i);
             r[i].g = g4 & 255u; r[i + 1].g = (g4 >> 8) & 255u; r[i + 2].g = (g4 >> 16) & 255u; r[i + 3].g = g4 >> 24;
             if constexpr (sizeof(TP) == 4) {
                 const gfloat4_a4 v = *reinterpret_cast<const gfloat4_a4 *>(t0 + i0 + i);
@@ -131,12 +130,6 @@ using SrcGuide = SrcGuideT<float>;
 // and hands the trip's NP x 64 x 16 results through an 8.5 KB LDS tile so that they leave as whole 128-byte lines (eight rows
 // per store instruction; stored lane by lane they were 64 partial lines per instruction and the pass ran at 1.7 TB/s).  The
 // tile is wavefront-private: no barrier anywhere.  grid (ceil(H / 64), B), block 64; trips are aligned to 16 columns.
-__device__ __forceinline__ void gwave_lds_sync()  // LDS executes one wavefront's instructions in order: a compiler fence is all
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 constexpr int kLaneOT = 17;  // tile row stride in doubles: lane = row writes hit 64 different bank pairs
 
@@ -245,7 +238,7 @@ __global__ void __launch_bounds__(64) k_box_rows_lane(Src src, double *__restric
             for (int i = 0; i < D * CH; ++i) hist[i] = hist[i + CH];
         }
         if (BOUND) continue;
-        gwave_lds_sync();
+        wave_lds_sync();
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             double *op = out + (size_t)p * plane_stride + ((size_t)b * H + y0) * W + col0 + t_col;
@@ -256,7 +249,7 @@ __global__ void __launch_bounds__(64) k_box_rows_lane(Src src, double *__restric
                 if (y0 + row < H) st_d2(op + (size_t)row * W, v0, v1);
             }
         }
-        gwave_lds_sync();
+        wave_lds_sync();
     }
 }
 
@@ -335,7 +328,7 @@ __global__ void __launch_bounds__(64) k_box_rows_ring(const double *__restrict__
         }
         if (!have_nx) load_run(col0 + xe0, nx);
         put_run(slot, nx);
-        gwave_lds_sync();
+        wave_lds_sync();
         have_nx = interior(col0 + CH);
         if (have_nx) load_run(col0 + CH + xe0, nx);
         const double *rrow = ring + lane * kRingS;
@@ -345,7 +338,7 @@ __global__ void __launch_bounds__(64) k_box_rows_ring(const double *__restrict__
             s += rrow[le0 + c] - rrow[(tr0 + c) & (kRingW - 1)];
             otile[lane * kLaneOT + c] = s;
         }
-        gwave_lds_sync();
+        wave_lds_sync();
         double *op = out + (size_t)y0 * W + col0 + t_col;
 #pragma unroll
         for (int i = 0; i < LPR; ++i) {
@@ -353,7 +346,7 @@ __global__ void __launch_bounds__(64) k_box_rows_ring(const double *__restrict__
             const double v0 = otile[row * kLaneOT + t_col], v1 = otile[row * kLaneOT + t_col + 1];
             if (y0 + row < H) st_d2(op + (size_t)row * W, v0, v1);
         }
-        gwave_lds_sync();
+        wave_lds_sync();
     }
 }
 
@@ -560,7 +553,7 @@ __global__ void __launch_bounds__(64) k_box_fused_ab(const uint8_t *__restrict__
         R.s0 = bnd[y];
         const int xs = x0 - 8 + 8 * pl;
         if (!edge) {
-            const gu32_a1 *gw = reinterpret_cast<const gu32_a1 *>(g + (size_t)y * W + xs);
+            const u32_unaligned *gw = reinterpret_cast<const u32_unaligned *>(g + (size_t)y * W + xs);
             R.g0 = gw[0];
             R.g1 = gw[1];
             const TP *tp = t + (size_t)y * W + xs;
@@ -652,7 +645,7 @@ __global__ void __launch_bounds__(64) k_box_fused_ab(const uint8_t *__restrict__
     auto block = [&](int r0, const RawRun &use, RawRun &fill) {
         put(use);
         const double s_in = use.s0;
-        gwave_lds_sync();
+        wave_lds_sync();
         if (r0 + 32 < H) fetch(r0 + 32, fill);
         // ---- rows: lane (row li, plane pl)
         if (r0 + li < H) {
@@ -665,7 +658,7 @@ __global__ void __launch_bounds__(64) k_box_fused_ab(const uint8_t *__restrict__
                 rrow[4 * c] = s;
             }
         }
-        gwave_lds_sync();
+        wave_lds_sync();
         // ---- columns: lane (column li, plane pl)
         const int r_last = min(r0 + 15, H - 1);
         if (r0 >= 16 && r0 + 15 < H) {  // whole block away from the top: the 32 ring reads first, then the chain
@@ -684,9 +677,9 @@ __global__ void __launch_bounds__(64) k_box_fused_ab(const uint8_t *__restrict__
         } else {
             col_steps(r0, r_last);
         }
-        gwave_lds_sync();
+        wave_lds_sync();
         epilogue(r0 - A, r_last - r0 + 1);
-        gwave_lds_sync();
+        wave_lds_sync();
     };
     RawRun b0, b1, b2;
     fetch(0, b0);
@@ -705,7 +698,7 @@ __global__ void __launch_bounds__(64) k_box_fused_ab(const uint8_t *__restrict__
             means[(y - y_first) * kFuseRS + lane] = s0 * scale;
             sum = s0 - l;
         }
-        gwave_lds_sync();
+        wave_lds_sync();
         epilogue(y_first, A);
     }
 }

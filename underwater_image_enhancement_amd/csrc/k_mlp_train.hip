@@ -25,6 +25,7 @@
 //   k_mt_clip_adam          every block re-reduces the partials in the same order, forms clip_grad_norm_'s coefficient in
 //                           float32 and applies the clip and torch's Adam update elementwise
 #include "common.h"
+#include "devutil.h"
 
 namespace uwie {
 
@@ -40,9 +41,6 @@ enum { MT_RELU_DROP = 0, MT_RES_DROP_RELU = 1, MT_RELU = 2, MT_HEADS = 3 };
 // ParameterPredictor's ranges (deep_learning_parameters.py:158-161) in the gated order: L_low, L_high, use_gamma, gamma
 __constant__ float kMtScale[4] = {15.0f, 13.0f, 1.0f, 0.5f};
 __constant__ float kMtMin[4] = {5.0f, 85.0f, 0.0f, 1.0f};
-
-__device__ __forceinline__ float relu_f(float v) { return v <= 0.0f ? 0.0f : v; }
-__device__ __forceinline__ float sigmoid_f(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 struct Drop {
     const uint8_t *given;  // [B][N] of this site, or nullptr: drawn

@@ -21,6 +21,7 @@
 // deep_learning_parameters.ParameterPredictor.forward in eval mode (:97-163) is five kinds of launch of
 // the same kernel (launch_mlp): input_proj, per residual block two layers, output_proj, and the four heads as one N = 4 layer.
 #include "common.h"
+#include "devutil.h"
 
 namespace uwie {
 
@@ -49,10 +50,6 @@ struct LinArgs {
     int B, K, N, ldx;
     int xstep;         // input offset per output neuron (the heads' last layers read their own 128 hidden values)
 };
-
-__device__ __forceinline__ float relu_f(float v) { return v <= 0.0f ? 0.0f : v; }  // NaN stays NaN, as torch's relu
-
-__device__ __forceinline__ float sigmoid_f(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 constexpr int kLdsRows = 8192;  // floats of batch rows staged in LDS per pass (32 KB)
 

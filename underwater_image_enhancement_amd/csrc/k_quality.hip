@@ -29,16 +29,6 @@ struct QaWeights {
     double w[8];
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t u = shfl_xor_u64((uint64_t)__double_as_longlong(v), o);
-        v += __longlong_as_double((long long)u);
-    }
-    return v;
-}
-
 // grid (nblk, B), block 256.  hist: [B][3][256] (gray, S, L).  The colourfulness sums (rg, yb, rg^2, yb^2) go to
 // cpart: [B][nblk][4] doubles, one row per block, when fimg is given; else to isum: [B][4] int64 of 255 * rg = r - g and
 // 510 * yb = r + g - 2b (|sum of squares| <= 510^2 * npx: 64 bits hold any frame the library takes).

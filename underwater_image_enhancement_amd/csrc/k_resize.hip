@@ -6,6 +6,7 @@
 // The frames come from a device table of uwie_frame_desc (pointer, H, W), so a packed upload and separate tensors need no
 // copy.  No float reductions and no atomics on results: an output element depends on its frame alone.
 #include "common.h"
+#include "devutil.h"
 
 namespace uwie {
 
@@ -22,7 +23,6 @@ struct RsNorm {
     float mean[3], stdv[3];
 };
 
-__device__ __forceinline__ uint8_t sat_u8(int v) { return (uint8_t)min(max(v, 0), 255); }
 
 // one coordinate's float32 source position (float)((d + 0.5) * scale - 0.5), scale = 1 / (dst / src) in double: the floor
 // and the fraction

@@ -44,10 +44,6 @@ __global__ void __launch_bounds__(256) k_stretch_apply(const float *__restrict__
     }
 }
 
-// float32 power: evaluated in float64 and rounded once (agrees with a correctly rounded powf except on
-// astronomically rare double-rounding cases; the exponent is float32(g) like NumPy's weak Python scalar).
-__device__ __forceinline__ float pow_f32(float x, float g) { return (float)pow((double)x, (double)g); }
-
 __global__ void __launch_bounds__(256) k_gamma(const float *__restrict__ img, float *__restrict__ out, size_t n, float g,
                                                int clip)
 {

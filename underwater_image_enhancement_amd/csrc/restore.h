@@ -8,7 +8,6 @@
 
 namespace uwie {
 
-typedef uint32_t __attribute__((aligned(1))) u32_any;
 typedef double2 __attribute__((aligned(8))) double2_a8;
 
 // TAB: the float32 differences I - A of the 3 x 256 possible bytes come from a table in LDS (3 KB, filled by the
@@ -148,7 +147,7 @@ struct RestoreImgT {  // per image, in registers
     }
     __device__ __forceinline__ void load_four(int p, uint32_t (&w)[3], double (&tv)[4]) const
     {
-        const u32_any *q = reinterpret_cast<const u32_any *>(img + (size_t)p * 3);
+        const u32_unaligned *q = reinterpret_cast<const u32_unaligned *>(img + (size_t)p * 3);
         w[0] = q[0]; w[1] = q[1]; w[2] = q[2];
         if constexpr (F32) {  // one 16-byte load; the four floats travel in the low words of tv (no conversion either way)
             typedef float4 __attribute__((aligned(4))) float4_a4;
@@ -176,7 +175,7 @@ struct RestoreImgT {  // per image, in registers
         Px4 v;
         double tv[4];
         if (n == 4) {
-            const u32_any *w = reinterpret_cast<const u32_any *>(img + (size_t)p * 3);
+            const u32_unaligned *w = reinterpret_cast<const u32_unaligned *>(img + (size_t)p * 3);
             const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
             v.r[0] = w0 & 255; v.g[0] = (w0 >> 8) & 255; v.b[0] = (w0 >> 16) & 255;
             v.r[1] = w0 >> 24; v.g[1] = w1 & 255; v.b[1] = (w1 >> 8) & 255;
