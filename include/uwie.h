@@ -99,6 +99,22 @@ typedef struct uwie_params {
                               than 10, PSNR >= 80 dB (tests/test_gpu_fuzz.py::test_f32t_transmission_stated_tolerance).  SIX
                               surface, strategies 1-3, windows 10 / 15 / 20 on frames the wavefront kernels take (even W,
                               H >= 4k, W >= 2k); everything else silently keeps float64.                         */
+    int32_t dark_patch;    /* side k of the square patch the dark channel is taken over (He et al.'s dark channel prior uses
+                              15).  1 (default; 0 means 1, so a zero-filled struct keeps it) is the reference: the minimum
+                              over the three channels of ONE pixel (S6:170-171, ES:221-222).  dark_patch > 1 HAS NO REFERENCE
+                              COUNTERPART; its contract is this definition.  For an H x W plane d, k >= 1 and the anchor
+                              a = k / 2 (integer division),
+                                erode(d)[y, x] = min{ d[v, u] : y - a <= v <= y + k - 1 - a,  x - a <= u <= x + k - 1 - a,
+                                                               (v, u) inside the image }
+                              which is cv2.erode with a k x k rectangle, its default centre anchor and its default border:
+                              pixels outside the frame never win.  Even k is allowed and asymmetric as written (k = 4 covers
+                              x - 2 .. x + 1).  The transmission is the surface's own arithmetic with erode between the channel
+                              minimum and 1 - omega * dark: float32, eps = 1e-6 and the clip to [0.1, 1] on the SIX surface
+                              (S6:170-174), eps = 1e-10 and no clip on the DICT surface (ES:221-225).  The guide image, the
+                              atmospheric light, the restore step and everything after them read the original frame.
+                              Valid: 0 .. 31.  u8 frames only: uwie_enhance_f32 / _f64 return UWIE_E_INVALID for > 1.
+                              A patched call writes the t0 plane first (k_trans_patch) and never takes the route that
+                              evaluates t0 inside the guided filter (tuning gf_fuse).                              */
 } uwie_params;
 
 #define UWIE_INTER_F64 0
@@ -705,9 +721,15 @@ int uwie_atmospheric_light(uwie_ctx *ctx, const uint8_t *d_in, const int32_t *d_
                            size_t workspace_bytes, void *stream);
 
 /* first half of estimate_transmission (S6:170-177 / ES:221-228): t0 = 1 - omega*min_c(x/(A+eps)) [clipped
- * on the SIX surface] as float32 [batch][H][W], and the 8-bit gray guide [batch][H][W]. */
+ * on the SIX surface] as float32 [batch][H][W], and the 8-bit gray guide [batch][H][W].  p->dark_patch > 1: the dark channel
+ * is eroded over the patch first (see uwie_params); the gray guide does not depend on it. */
 int uwie_transmission_init(uwie_ctx *ctx, const uint8_t *d_in, const int32_t *d_kind, const float *d_A, int batch,
                            int H, int W, const uwie_params *p, float *d_t0, uint8_t *d_gray, void *stream);
+
+/* The output tile (*tile_w x *tile_h pixels, anchored at the frame's top left corner) that one workgroup of the patched
+ * transmission kernel (k_trans_patch, dark_patch = k) covers on an H x W frame: the launcher runs on these numbers, so a test
+ * can aim at the seams between tiles.  No context: nothing here depends on a tuning. */
+int uwie_dark_patch_plan(int H, int W, int k, int *tile_w, int *tile_h);
 
 /* cv2.boxFilter(src, CV_64F, (k,k)) on float64 planes [batch][H][W] (S6:31-43). */
 int uwie_box_filter_f64(uwie_ctx *ctx, const double *d_src, double *d_dst, int batch, int H, int W, int ksize,

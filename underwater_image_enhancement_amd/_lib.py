@@ -57,6 +57,7 @@ class UwieParams(ctypes.Structure):
         ("apply_gamma", ctypes.c_int32),
         ("gf_exact", ctypes.c_int32),
         ("inter_dtype", ctypes.c_int32),
+        ("dark_patch", ctypes.c_int32),
     ]
 
 
@@ -89,6 +90,13 @@ def clahe_plan(batch, H, W, tiles=(8, 8), clip_limit=2.0, recomputed=False) -> U
     return out
 
 
+def dark_patch_plan(H, W, k) -> tuple[int, int]:
+    """uwie_dark_patch_plan: (tile_w, tile_h) of one workgroup of the patched transmission kernel.  Needs the library, not a device."""
+    tw, th = ctypes.c_int(), ctypes.c_int()
+    check(load().uwie_dark_patch_plan(int(H), int(W), int(k), ctypes.byref(tw), ctypes.byref(th)))
+    return tw.value, th.value
+
+
 # name -> argument types (return type is int unless listed in _RESTYPES)
 _VP, _SZ, _I, _D = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_double
 _PP = ctypes.POINTER(UwieParams)
@@ -118,6 +126,7 @@ SIGNATURES = {
     "uwie_guided_plan": [_I, _I, _I, _I, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
     "uwie_guided_fill": [_I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)],
     "uwie_clahe_plan": [_I, _I, _I, _I, _I, _D, _I, ctypes.POINTER(UwieClahePlan)],
+    "uwie_dark_patch_plan": [_I, _I, _I, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
     "uwie_enhance_u8": [_VP, _VP, _VP, _VP, _I, _I, _I, _PP, _VP, _SZ, _VP],
     "uwie_enhance_u8_f64": [_VP, _VP, _VP, _VP, _I, _I, _I, _PP, _VP, _SZ, _VP],
     "uwie_enhance_percentiles": [_VP, _VP, _SZ, _I, _I, _I, _PP, _VP, _VP],

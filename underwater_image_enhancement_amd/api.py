@@ -42,6 +42,13 @@ _F255 = np.float32(255.0)
 _ATTEN = np.float32(0.85)
 
 
+def _patch_needs_u8(frames, dark_patch):
+    """dark_patch > 1 is built for u8 frames: a float image (which no u8 entry point takes anyway) is named as unsupported."""
+    dtype = getattr(frames, "dtype", None)
+    if int(dark_patch) > 1 and dtype is not None and dtype not in (np.uint8, torch.uint8):
+        raise UnsupportedInputError(f"dark_patch > 1 takes uint8 frames or u8-derived float images, got {dtype}")
+
+
 def _as_batch_u8(frames, dev: Device):
     """numpy/torch, [H,W,3] or [B,H,W,3] uint8 -> (cuda uint8 [B,H,W,3], was_numpy, was_single)."""
     was_numpy = isinstance(frames, np.ndarray)
@@ -75,9 +82,11 @@ def enhance(frames, strategy: int = 2, cast_correct: bool = True, device: int | 
 
     ``frames``: uint8 ``[H,W,3]`` / ``[B,H,W,3]``, NumPy (copied to HBM and back) or a torch ROCm tensor (stays on
     the device).  ``strategy`` selects ``strategy1..6`` (default 2, medium dehazing).  ``overrides`` set
-    ``uwie_params`` fields (e.g. ``omega=0.6, gf_ksize=20``).
+    ``uwie_params`` fields (e.g. ``omega=0.6, gf_ksize=20``; ``dark_patch=15`` takes the dark channel over a 15 x 15 patch,
+    an extension without a reference counterpart: include/uwie.h).
     """
     dev = get_device(device)
+    _patch_needs_u8(frames, overrides.get("dark_patch", 1))
     batch, was_numpy, single = _as_batch_u8(frames, dev)
     p = dev.params(_lib.SURFACE_SIX, int(strategy), cast_correct=int(bool(cast_correct)), **overrides)
     out, outf = dev.enhance_u8(batch, p, want_float=return_float)
@@ -93,16 +102,17 @@ DRIVER_STRATEGIES = (
 CAST_NAMES = ("normal", "greenish", "bluish")
 
 
-def enhance_all(frames, cast_correct: bool = True, device: int | None = None):
+def enhance_all(frames, cast_correct: bool = True, device: int | None = None, dark_patch: int = 1):
     """All six strategies of every frame in one call: one cast detection and one atmospheric-light quadtree per frame
     (strategies 1-3 share it), like the inner loop of ``process_all_images_all_strategies`` (six_stadigy.py:398-431).
 
     Returns ``(outputs, image_types)``: ``outputs[name]`` is the uint8 batch of that strategy (keys in the driver's
     order, see ``DRIVER_STRATEGIES``), ``image_types`` the list of ``"normal" / "greenish" / "bluish"`` per frame.
+    ``dark_patch`` (default 1, the reference) applies to the dehazing strategies 1-3.
     """
     dev = get_device(device)
     batch, was_numpy, single = _as_batch_u8(frames, dev)
-    out, kind = dev.enhance_all_u8(batch, cast_correct)
+    out, kind = dev.enhance_all_u8(batch, cast_correct, dark_patch=dark_patch)
     types = [CAST_NAMES[int(k)] for k in kind.cpu().tolist()]
     outs = {name: _finish(out[i], was_numpy, single, dev) for i, (name, _) in enumerate(DRIVER_STRATEGIES)}
     return outs, types
@@ -1227,10 +1237,13 @@ def _dict_params(dev, name, params):
     if "tile_grid_size" in params:
         over["tiles_x"], over["tiles_y"] = (int(v) for v in params["tile_grid_size"])
     over["apply_gamma"] = int(bool(params.get("apply_gamma", False)))
+    if "dark_patch" in params:  # (no key of the reference's: uwie_params.dark_patch, the dehazing strategies read it)
+        over["dark_patch"] = int(params["dark_patch"])
     return dev.params(_lib.SURFACE_DICT, _lib.DICT_STRATEGIES[name], **over)
 
 
-def select_best(frames, strategies=None, weights=None, device: int | None = None, return_all: bool = False):
+def select_best(frames, strategies=None, weights=None, device: int | None = None, return_all: bool = False,
+                dark_patch: int | None = None):
     """The labelling loop of ``SelfSupervisedSystem.build_dataset`` (main.py:118-146) for one frame or a batch, in ONE device
     call: every entry of ``strategies`` (default ``Config.STRATEGIES``, config.py:28-75: ``{key: {'name': ..., params}}``) goes
     through ``apply_strategy``, ``comprehensive_assessment`` with ``weights`` (default ``Config.QUALITY_WEIGHTS``) scores each
@@ -1242,8 +1255,13 @@ def select_best(frames, strategies=None, weights=None, device: int | None = None
     ``return_all`` a fourth value ``{name: uint8 batch}`` holds every strategy's output.  A strategy the device cannot
     run fails the call: fall back to ``EnhancementStrategies.apply_strategy`` + ``QualityAssessment`` per strategy, whose
     ``try`` blocks give a failing strategy the score 0.0 like main.py:139-142.
+
+    ``dark_patch`` (optional): uwie_params.dark_patch of every dehazing entry whose own dict has no ``'dark_patch'`` key.
     """
     strategies = CONFIG_STRATEGIES if strategies is None else strategies
+    if dark_patch is not None:
+        strategies = {k: ({"dark_patch": int(dark_patch), **v} if _lib.DICT_STRATEGIES.get(k, 9) <= 2 else v)
+                      for k, v in strategies.items()}
     weights = CONFIG_QUALITY_WEIGHTS if weights is None else weights
     dev = get_device(device)
     batch, was_numpy, single = _as_batch_u8(frames, dev)
@@ -1598,11 +1616,15 @@ class SixStrategies:
     """Mirror of ``six_stadigy.EnhancementStrategies`` (strategy1..6: float32 HxWx3 in [0,1] -> float32 HxWx3)."""
 
     device: int | None = None
+    dark_patch: int = 1  # uwie_params.dark_patch of strategies 1-3 (no reference counterpart above 1); u8-derived images only
 
     @classmethod
     def _run(cls, number, img):
         dev = get_device(cls.device)
         what = _float_kind(img)
+        patch = int(cls.dark_patch) if number <= 3 else 1
+        if patch > 1 and what in ("float32", "float64"):
+            raise UnsupportedInputError("dark_patch > 1 is built for u8-derived images only: a general float image has no patched route")
         if what == "float32":  # general float image: strategyN(img) as it stands (no cast detection inside, S6:230-285)
             p = dev.params(_lib.SURFACE_SIX, number, cast_correct=0, forced_cast=-1)
             return dev.enhance_float(dev.tensor(np.ascontiguousarray(img)[None]), p)[1][0].cpu().numpy()
@@ -1611,7 +1633,7 @@ class SixStrategies:
                                         "is only supported on the dict surface (EnhancementStrategies.apply_strategy)")
         u8, kind = _recover_u8(img)
         # a colour-corrected input is replayed on the device from its u8 frame through a forced cast kind
-        p = dev.params(_lib.SURFACE_SIX, number, cast_correct=0, forced_cast=_lib.CAST_KINDS.index(kind) or -1)
+        p = dev.params(_lib.SURFACE_SIX, number, cast_correct=0, forced_cast=_lib.CAST_KINDS.index(kind) or -1, dark_patch=patch)
         _, outf = dev.enhance_u8(dev.tensor(u8[None]), p, want_float=True)
         return outf[0].cpu().numpy()
 
@@ -1677,6 +1699,9 @@ class EnhancementStrategies:
             except UnsupportedInputError:
                 pass
         p = _dict_params(dev, name, params)
+        if u8 is None and p.dark_patch > 1:
+            raise UnsupportedInputError("dark_patch > 1 is built for u8-derived float32 images (u8 / 255) only: a general float image "
+                                        "has no patched route")
         # float64 like the reference (ES:247,307,345): a caller's (enhanced * 255).astype(np.uint8) (main.py:155) then
         # truncates the same values as with the reference
         if u8 is not None:

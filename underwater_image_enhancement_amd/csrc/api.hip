@@ -136,7 +136,17 @@ bool dehazes(const uwie_params *p)
     return p->strategy >= UWIE_DICT_STRONG_DEHAZING && p->strategy <= UWIE_DICT_LIGHT_ENHANCEMENT;
 }
 
-// The guided filter of a u8 dehazing call: t0 comes from the frame (k_trans_init, or inside the fused kernel)
+// uwie_params.dark_patch as the kernels take it: 0 means 1 (a zero-filled struct keeps the per-pixel dark channel)
+int dark_patch_of(const uwie_params *p) { return p->dark_patch > 1 ? p->dark_patch : 1; }
+
+// t0 of a u8 frame: the per-pixel dark channel (k_trans_init) or the one over a dark_patch x dark_patch window (k_trans_patch)
+int launch_t0(const FuseT0Args &f, int patch, Shape s, float *d_t0, hipStream_t st)
+{
+    if (patch > 1) return launch_trans_patch(f.rgb, f.kind, f.A, s, patch, f.omega, f.norm_eps, f.pre_clip, d_t0, st);
+    return launch_trans_init(f.rgb, f.kind, f.A, s, f.omega, f.norm_eps, f.pre_clip, d_t0, st);
+}
+
+// The guided filter of a u8 dehazing call: t0 comes from the frame (k_trans_init / k_trans_patch, or inside the fused kernel)
 GuidedRequest u8_guided(const uwie_params *p)
 {
     const bool six = p->surface == UWIE_SURFACE_SIX;
@@ -145,7 +155,8 @@ GuidedRequest u8_guided(const uwie_params *p)
     r.fx = six && p->inter_dtype == UWIE_INTER_FX32;
     // (the three-digit key sweeps of tuning select_generic instantiate the restore for the float64 plane only: no float32 t there)
     r.f32_ok = six && p->inter_dtype == UWIE_INTER_F32T && !tune().select_generic;
-    r.t0_from_frame = true;
+    // a patched dark channel (dark_patch > 1) needs its neighbours' values: k_trans_patch writes the t0 plane, no route evaluates it
+    r.t0_from_frame = dark_patch_of(p) <= 1;
     return r;
 }
 
@@ -225,7 +236,7 @@ int stage_guided(const Pipe &P, Shape s, const uwie_params *p, const FuseT0Args 
     // the exact-order filter builds its planes in the scratch, where t0 lives otherwise (enhance_all runs each set's own plan
     // in one merged layout)
     UWIE_REQUIRE(!g.planes || (P.planes && P.t0 != P.scratch), "guided filter: the workspace layout has no planes for the exact-order filter");
-    if (g.t0) UWIE_TRY(launch_trans_init(frame.rgb, frame.kind, frame.A, s, frame.omega, frame.norm_eps, frame.pre_clip, P.t0, st));
+    if (g.t0) UWIE_TRY(launch_t0(frame, dark_patch_of(p), s, P.t0, st));
     UWIE_TRY(launch_guided_plan(g, s, P.gray, P.t0, P.t, P.scratch, st, &frame));
     if (t_is_f32) *t_is_f32 = g.t_f32;
     return UWIE_OK;
@@ -390,6 +401,7 @@ int check_params(const uwie_params *p)
         UWIE_REQUIRE(p->wb_percentile >= 0.0 && p->wb_percentile <= 100.0, "wb_percentile must be in [0, 100]");
     UWIE_REQUIRE(p->inter_dtype == UWIE_INTER_F64 || p->inter_dtype == UWIE_INTER_FX32 || p->inter_dtype == UWIE_INTER_F32T,
                  "unknown inter_dtype");
+    UWIE_REQUIRE(p->dark_patch >= 0 && p->dark_patch <= 31, "dark_patch must be 0 .. 31 (0 and 1: the per-pixel dark channel)");
     return UWIE_OK;
 }
 
@@ -787,6 +799,7 @@ int uwie_params_init(uwie_params *p, int surface, int strategy)
     p->wb_percentile = -1.0;
     p->gamma = 1.2;
     p->forced_cast = -1;
+    p->dark_patch = 1;
     if (surface == UWIE_SURFACE_SIX) {
         p->cast_correct = 1;
         switch (strategy) {  // six_stadigy.py:230-285
@@ -1006,6 +1019,7 @@ int uwie_enhance_f32(uwie_ctx *ctx, const float *d_img, uint8_t *d_out_u8, float
     UWIE_SCOPE(ctx);
     UWIE_CHECK_SHAPE(batch, H, W);
     UWIE_TRY(check_params(p));
+    UWIE_REQUIRE(p->dark_patch <= 1, "enhance_f32: dark_patch > 1 is built for u8 frames only (uwie_enhance_u8)");
     const Shape s{batch, H, W};
     Carver c(d_workspace);
     FloatPipe<float> P = carve_float<float>(c, s, p);
@@ -1025,6 +1039,7 @@ int uwie_enhance_f64(uwie_ctx *ctx, const double *d_img, uint8_t *d_out_u8, doub
     UWIE_CHECK_SHAPE(batch, H, W);
     UWIE_TRY(check_params(p));
     UWIE_REQUIRE(p->surface == UWIE_SURFACE_DICT, "enhance_f64: float64 images are the dict surface's (six_stadigy.py works on float32, S6:406)");
+    UWIE_REQUIRE(p->dark_patch <= 1, "enhance_f64: dark_patch > 1 is built for u8 frames only (uwie_enhance_u8_f64)");
     const Shape s{batch, H, W};
     Carver c(d_workspace);
     FloatPipe<double> P = carve_float<double>(c, s, p);
@@ -1943,7 +1958,9 @@ int uwie_transmission_init(uwie_ctx *ctx, const uint8_t *d_in, const int32_t *d_
     const Shape s{batch, H, W};
     hipStream_t st = (hipStream_t)stream;
     const bool six = p->surface == UWIE_SURFACE_SIX;
-    if (d_t0) UWIE_TRY(launch_trans_init(d_in, d_kind, d_A, s, (float)p->omega, six ? 1e-6f : 1e-10f, six ? 1 : 0, d_t0, st));
+    UWIE_REQUIRE(p->dark_patch >= 0 && p->dark_patch <= 31, "transmission_init: dark_patch must be 0 .. 31");
+    if (d_t0)
+        UWIE_TRY(launch_t0(FuseT0Args{d_in, d_kind, d_A, (float)p->omega, six ? 1e-6f : 1e-10f, six ? 1 : 0}, dark_patch_of(p), s, d_t0, st));
     if (d_gray) UWIE_TRY(launch_quant_gray(d_in, d_kind, d_gray, s, p->gray_shift, st));
     return UWIE_OK;
 }
@@ -1993,6 +2010,15 @@ int uwie_guided_fill(int batch, int H, int W, int ksize, long long *items)
     const Shape s{batch, H, W};
     const GuidedPlan g = plan_guided(s, {ksize, 1.0});
     *items = g.route == GF_SPLIT ? guided_items(s, g) : 0;
+    return UWIE_OK;
+}
+
+int uwie_dark_patch_plan(int H, int W, int k, int *tile_w, int *tile_h)
+{
+    UWIE_REQUIRE(tile_w && tile_h, "dark_patch_plan: NULL pointer");
+    UWIE_CHECK_SHAPE(1, H, W);
+    UWIE_REQUIRE(k >= 0 && k <= 31, "dark_patch_plan: dark_patch must be 0 .. 31");
+    dark_patch_tile(tile_w, tile_h);  // one tile for every patch and frame; k <= 1 launches k_trans_init, which has none
     return UWIE_OK;
 }
 

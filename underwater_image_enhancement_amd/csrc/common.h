@@ -269,6 +269,11 @@ size_t box_ws_bytes(Shape s);
 int launch_trans_init(const uint8_t *d_in, const int32_t *d_kind, const float *d_A, Shape s, float omega, float norm_eps,
                       int pre_clip, float *d_t0, hipStream_t st);
 int launch_box_filter_f64(const double *d_src, double *d_dst, Shape s, int k, void *ws, hipStream_t st);
+// k_dark_patch.hip: t0 with the dark channel taken over a k x k patch (uwie_params.dark_patch = k, 2 .. 31): cv2.erode's
+// rectangle, centre anchor and border between the channel minimum and 1 - omega * dark.  One launch, no workspace.
+int launch_trans_patch(const uint8_t *d_in, const int32_t *d_kind, const float *d_A, Shape s, int k, float omega, float norm_eps,
+                       int pre_clip, float *d_t0, hipStream_t st);
+void dark_patch_tile(int *tile_w, int *tile_h);  // the output tile of one block (uwie_dark_patch_plan)
 int launch_guided(const uint8_t *d_gray, const float *d_t0, Shape s, int k, double eps, double *d_t, void *ws,
                   hipStream_t st);
 int launch_guided_p64(const uint8_t *d_gray, const double *d_t0, Shape s, int k, double eps, double *d_t, void *ws, hipStream_t st);

@@ -235,13 +235,14 @@ class Device(_ClosedOnDel):
         check(self.lib.uwie_color_correct_f32(self._ctx, _ptr(img), _ptr(kind), _ptr(out), B, H, W, self.stream()))
         return out
 
-    def enhance_all_u8(self, frames, cast_correct: bool = True):
-        """frames: uint8 cuda tensor [B,H,W,3] -> (uint8 [6,B,H,W,3] = strategies 1..6, int32 [B] cast kinds)."""
+    def enhance_all_u8(self, frames, cast_correct: bool = True, dark_patch: int = 1):
+        """frames: uint8 cuda tensor [B,H,W,3] -> (uint8 [6,B,H,W,3] = strategies 1..6, int32 [B] cast kinds).
+        ``dark_patch``: uwie_params.dark_patch of the dehazing strategies 1-3 (4-6 have no dark channel)."""
         B, H, W = self._bhw(frames)
         assert frames.dtype == torch.uint8
         p6 = (UwieParams * 6)()
         for k in range(6):
-            p6[k] = self.params(_lib.SURFACE_SIX, k + 1, cast_correct=int(bool(cast_correct)))
+            p6[k] = self.params(_lib.SURFACE_SIX, k + 1, cast_correct=int(bool(cast_correct)), dark_patch=int(dark_patch) if k < 3 else 1)
         ws = self.workspace(self.lib.uwie_workspace_bytes_all(B, H, W, ctypes.cast(p6, ctypes.c_void_p)))
         out = self.empty((6, B, H, W, 3), torch.uint8)
         kind = self.empty((B,), torch.int32)
