@@ -102,6 +102,16 @@ def test_workspace_bytes_are_unchanged(lib):
             ref = ctypes.byref(p)
         got = tuple(lib.uwie_workspace_bytes(B, H, W, ref) for B, H, W in WS_SHAPES)
         assert got == want, f"{key}: {got}"
+    # the wider table (tests/workspace_cases.py): every dehazing set and a code-domain one per surface under each parameter
+    # variant that moves a buffer, a ragged batch, and the fan-out, selection and float-image sizing functions
+    import workspace_cases as wc
+
+    assert wc.SHAPES[:len(WS_SHAPES)] == WS_SHAPES
+    want, got = wc.recorded("no_context"), wc.cpu_sizes(lib)
+    assert sorted(got) == sorted(want)
+    assert len(got) == 8 * 11 + 2 + 2 + 4 and all(len(v) == len(wc.SHAPES) and min(v) > 0 for v in got.values())
+    wrong = {k: (got[k], want[k]) for k in got if got[k] != want[k]}
+    assert not wrong, wrong
 
 
 def test_null_arguments_are_rejected_without_a_gpu(lib):

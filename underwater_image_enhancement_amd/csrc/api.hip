@@ -1,5 +1,6 @@
 // C ABI of libuwie.so (include/uwie.h): context, parameter defaults, workspace sizing, the per-stage entry points
 // and the strategy pipelines.  Everything here only enqueues kernels on the caller's stream.
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -120,16 +121,6 @@ struct Pipe {
     int32_t *guess;   // ... and the cast kinds its gray plane was first written for
 };
 
-size_t max5(size_t a, size_t b, size_t c, size_t d, size_t e)
-{
-    size_t m = a;
-    if (b > m) m = b;
-    if (c > m) m = c;
-    if (d > m) m = d;
-    if (e > m) m = e;
-    return m;
-}
-
 bool dehazes(const uwie_params *p)
 {
     if (p->surface == UWIE_SURFACE_SIX) return p->strategy >= 1 && p->strategy <= 3;
@@ -146,21 +137,134 @@ int launch_t0(const FuseT0Args &f, int patch, Shape s, float *d_t0, hipStream_t 
     return launch_trans_init(f.rgb, f.kind, f.A, s, f.omega, f.norm_eps, f.pre_clip, d_t0, st);
 }
 
-// The guided filter of a u8 dehazing call: t0 comes from the frame (k_trans_init / k_trans_patch, or inside the fused kernel)
-GuidedRequest u8_guided(const uwie_params *p)
+// The plan of a u8 enhance call: plan_enhance is the one place that decides which pipeline runs a parameter set on a shape,
+// which routes its stages take and what they need of the workspace; carve_pipe lays a plan out and run_enhance runs one, and
+// neither decides anything.  tune() is read here (and in the planners this calls) and nowhere downstream: it is the calling
+// context's tuning inside an entry point and the default tuning in uwie_workspace_bytes, which has no context --
+// uwie_workspace_bytes_ctx answers for a context.
+enum EnhancePipeline {
+    EP_SIX_DEHAZE,   // six_stadigy strategies 1-3: cast, airlight, guided filter, restore, stretch, CLAHE / white balance
+    EP_SIX_CODES,    // six_stadigy strategies 4-6: cast, then per-image LUT chains (k_codes.hip)
+    EP_DICT_DEHAZE,  // strong / medium dehazing, light enhancement (ES:350-444) on the uncorrected frame
+    EP_DICT_CODES,   // clahe_enhancement, histogram_equalization
+};
+struct EnhancePlan {
+    EnhancePipeline pipeline;
+    bool dehaze;        // a dehazing pipeline: gray plane, t0 and t exist
+    GuidedPlan guided;  // ... and its guided filter, planned once: planes, t0 and t_f32 are read from here
+    int dark_patch;     // t0 of the frame: the per-pixel dark channel (1, k_trans_init) or k_trans_patch's window
+    // percentile selection and the restored image
+    bool generic;   // the three- / six-digit key sweeps (tuning select_generic); otherwise the linear first digit (select_lin_*)
+    bool store;     // the restored image is kept in planes; otherwise every sweep recomputes it from the frame and t
+    bool predict;   // linear route: target windows predicted from a sample of the image
+    bool rank;      // linear route: the rank-counting sweep (k_restore_rank) where the windows were predicted
+    bool F, F64;    // which image planes the layout has (F64 comes with pct64)
+    // cast detection's chunk pass feeding the quadtree (tuning entry_fuse)
+    bool qpart;      // it leaves the level-0 quadrant histograms in the scratch, at qoff
+    bool cast_gray;  // ... and writes the gray plane (entry_fuse = 2: the quadtree's pre-pass does, k_gray_strong)
+    size_t qoff;
+    int tx, ty;      // effective CLAHE tile grid
+    size_t scratch_bytes;
+    bool t0_in_scratch;
+};
+
+// The scratch of a layout: the largest share any of its stages takes.  The raw transmission lives from k_trans_init to the end
+// of the guided filter; the scratch is idle exactly then (the quadtree is done with it, the selection has not started), so t0
+// borrows its first 4 B/px -- unless the exact-order filter is on, whose six planes are IN the scratch while it reads t0.
+// The quadrant histograms sit behind what cast detection and the quadtree use: they are written before the quadtree starts and
+// read by its first launches.
+void size_scratch(EnhancePlan &e, Shape s)
 {
-    const bool six = p->surface == UWIE_SURFACE_SIX;
-    GuidedRequest r{p->gf_ksize, p->gf_eps, p->gf_exact != 0};
-    // fixed-point a/b ring: only with the pre-clipped transmission of the six_stadigy surface (0.1 <= t0 <= 1 bounds a, b)
-    r.fx = six && p->inter_dtype == UWIE_INTER_FX32;
-    // (the three-digit key sweeps of tuning select_generic instantiate the restore for the float64 plane only: no float32 t there)
-    r.f32_ok = six && p->inter_dtype == UWIE_INTER_F32T && !tune().select_generic;
-    // a patched dark channel (dark_patch > 1) needs its neighbours' values: k_trans_patch writes the t0 plane, no route evaluates it
-    r.t0_from_frame = dark_patch_of(p) <= 1;
-    return r;
+    const size_t none = 0, n = (size_t)s.B * s.npx();
+    e.t0_in_scratch = e.dehaze && !e.guided.planes;
+    e.scratch_bytes = std::max({cast_ws_bytes(s), e.dehaze ? airlight_ws_bytes(s) : none, e.guided.planes ? guided_ws_bytes(s) : none,
+                                select_ws_bytes(s), clahe_ws_bytes(s, e.tx, e.ty), codes_ws_bytes(s, e.tx, e.ty),
+                                e.t0_in_scratch ? n * sizeof(float) : none});
+    e.qoff = e.qpart ? (std::max(cast_ws_bytes(s), airlight_ws_bytes(s)) + 255) & ~size_t(255) : 0;
+    if (e.qpart) e.scratch_bytes = std::max(e.scratch_bytes, e.qoff + quad_part_bytes(s));
 }
 
-Pipe carve_pipe(Carver &c, Shape s, const uwie_params *p)
+// p == NULL: any stage entry point (they carve their own, smaller layouts from the same buffer) -- the most demanding layout.
+EnhancePlan plan_enhance(Shape s, const uwie_params *p)
+{
+    const Tuning &tu = tune();
+    EnhancePlan e{};
+    e.tx = p && p->tiles_x > 0 ? p->tiles_x : 8;
+    e.ty = p && p->tiles_y > 0 ? p->tiles_y : 8;
+    if (!p) {  // a dehazing call that stores float32 planes and filters in exact order
+        e.pipeline = EP_SIX_DEHAZE;
+        e.dehaze = e.store = e.F = e.guided.t0 = e.guided.planes = true;
+        size_scratch(e, s);
+        return e;
+    }
+    const bool six = p->surface == UWIE_SURFACE_SIX;
+    e.dehaze = dehazes(p);
+    e.pipeline = six ? (e.dehaze ? EP_SIX_DEHAZE : EP_SIX_CODES) : (e.dehaze ? EP_DICT_DEHAZE : EP_DICT_CODES);
+    if (e.dehaze) {
+        e.generic = tu.select_generic != 0;
+        // The guided filter of a u8 call: t0 comes from the frame (k_trans_init / k_trans_patch, or inside the fused kernel).
+        // The exact-order route materialises six float64 planes; the other routes keep everything on chip.
+        GuidedRequest r{p->gf_ksize, p->gf_eps, p->gf_exact != 0};
+        // fixed-point a/b ring: only with the pre-clipped transmission of the six_stadigy surface (0.1 <= t0 <= 1 bounds a, b)
+        r.fx = six && p->inter_dtype == UWIE_INTER_FX32;
+        // (the three-digit key sweeps of tuning select_generic instantiate the restore for the float64 plane only: no float32 t there)
+        r.f32_ok = six && p->inter_dtype == UWIE_INTER_F32T && !e.generic;
+        // a patched dark channel (dark_patch > 1) needs its neighbours' values: k_trans_patch writes the t0 plane, no route evaluates it
+        e.dark_patch = dark_patch_of(p);
+        r.t0_from_frame = e.dark_patch <= 1;
+        e.guided = plan_guided(s, r);
+        // Strategies 1 and 2 and the dict surface never store the restored image: the histogram sweep (which also files the
+        // elements of the predicted target bins, select_lin_begin), the collecting sweep and the stretch each recompute it from
+        // the frame and t (restore.h: 11 + 14 bytes per pixel instead of 23 + 15 in float32, and no collecting sweep; the
+        // float64 image would be 24 B/px); so do the key-digit passes of planes the selection flags and -- round 4 -- the
+        // selection's fallback.  Tuning restore_store keeps the stored planes (4K x 64: 17.9 vs 17.5 ms per step, round 2);
+        // the tests compare both modes.  Strategy 3's tail reads the planes and the key sweeps (select_generic) work on them.
+        const bool tail_reads_planes = six && p->strategy == 3;
+        e.store = e.generic || tu.restore_store || tail_reads_planes;
+        // The float32 planes (12 B/px) exist only where they are stored: a 4K x 64 strategy-2 call went 43 -> 31 B/px; the
+        // code-domain strategies never had a use for them.  The dict surface's float64 planes keep their place in the layout
+        // even when nothing is written to them: the sizes uwie_workspace_bytes answers are pinned.
+        e.F = six && e.store;
+        e.F64 = p->surface == UWIE_SURFACE_DICT;
+        // Strategy 3 keeps the planes, so the exact target bins can be collected from them by one streaming sweep: no predicted
+        // windows there -- its percentiles (20 / 85 / 2 / 98) sit where the bins are full and four windows made the restore
+        // sweep 2.9 ms at 4K x 16 against 0.65 + 0.35 for sweep + collection.  Tuning lin_predict3 brings the windows back.
+        e.predict = !tail_reads_planes || tu.lin_predict3;
+        // round 4: no histogram at all -- counts below the predicted windows + the windows' members (k_restore_rank).
+        // (small jobs keep the histogram sweep: at 1080p x 1 the rank-counting kernels' fixed costs -- wavefront-private queues,
+        // a window-wide list for the finish -- make them 54 + 20 us against 34 + 14; tuning rank_sweep = 2 forces them anyway)
+        const bool big = (size_t)s.B * s.npx() >= ((size_t)1 << 24) || tu.rank_sweep >= 2;
+        e.rank = six && !e.store && !e.guided.t_f32 && tu.rank_sweep && big && s.npx() >= 4;
+        // round 4: cast detection's chunk pass leaves the level-0 quadrant histograms of the quadtree behind (six_stadigy surface
+        // with cast detection on; frames entry_fuse_takes)
+        e.qpart = six && p->cast_correct && p->forced_cast < 0 && entry_fuse_takes(s, p->min_size);
+        e.cast_gray = e.qpart && tu.entry_fuse != 2;
+    }
+    size_scratch(e, s);
+    return e;
+}
+
+// The layout that holds every one of the six six_stadigy sets of uwie_enhance_all_u8, which runs them from one workspace: the
+// union of their plans (the stored planes if any set keeps them, the exact-order filter's planes if any dehazing set's plan
+// needs them, the largest CLAHE tile grid).  six[k]: each set's own plan, which its tail runs in this layout.
+EnhancePlan plan_enhance_all(Shape s, const uwie_params *p6, EnhancePlan *six)
+{
+    EnhancePlan u{};
+    u.pipeline = EP_SIX_DEHAZE;
+    u.dehaze = true;
+    for (int k = 0; k < 6; ++k) {
+        const EnhancePlan &e = six[k] = plan_enhance(s, &p6[k]);
+        u.F |= e.F;
+        u.guided.planes |= e.guided.planes;
+        u.qpart |= e.qpart;
+        u.tx = std::max(u.tx, e.tx);
+        u.ty = std::max(u.ty, e.ty);
+    }
+    size_scratch(u, s);
+    return u;
+}
+
+Pipe carve_pipe(Carver &c, Shape s, const EnhancePlan &e)
 {
     Pipe P{};
     const size_t n = (size_t)s.B * s.npx();
@@ -168,78 +272,34 @@ Pipe carve_pipe(Carver &c, Shape s, const uwie_params *p)
     P.A = c.take<float>((size_t)s.B * 3);
     P.pct = c.take<float>((size_t)s.B * 3 * kMaxPct);
     P.guess = c.take<int32_t>(s.B);
-    const bool dz = !p || dehazes(p);
-    const bool dict_dz = p && p->surface == UWIE_SURFACE_DICT && dz;
-    if (dict_dz) {
+    if (e.F64) {
         P.F64 = c.take<double>(n * 3);
         P.pct64 = c.take<double>((size_t)s.B * 3 * kMaxPct);
-    } else if (!p || (p->surface == UWIE_SURFACE_SIX && dz && (p->strategy == 3 || tune().restore_store || tune().select_generic))) {
-        // The float32 planes of the restored image (12 B/px): strategy 3's tail reads them, the stored-plane and key-sweep
-        // routes (tuning) work on them.  Strategies 1-2 recompute the image in every sweep and -- round 4 -- in the
-        // selection's fallback too, and the code-domain strategies never had a use for them: nothing reserved
-        // (a 4K x 64 strategy-2 call: 43 -> 31 B/px).  tune() is the calling context's tuning inside an entry point and the
-        // default tuning in uwie_workspace_bytes, which has no context: uwie_workspace_bytes_ctx answers for a context.
-        P.F = c.take<float>(n * 3);
     }
-    const int tx = p ? p->tiles_x : 8, ty = p ? p->tiles_y : 8;
-    // the exact-order guided filter materialises six float64 planes; the other routes keep everything on chip
-    const bool gf_planes = dz && (!p || plan_guided(s, u8_guided(p)).planes);
-    if (dz) {
+    if (e.F) P.F = c.take<float>(n * 3);
+    if (e.dehaze) {
         P.gray = c.take<uint8_t>(n);
-        // The raw transmission lives from k_trans_init to the end of the guided filter.  The scratch region is idle exactly then
-        // (the quadtree is done with it, the selection has not started), so t0 borrows its first 4 B/px -- unless the exact-order
-        // filter is on, whose six planes are IN the scratch while it reads t0.
-        if (gf_planes) P.t0 = c.take<float>(n);
+        if (!e.t0_in_scratch) P.t0 = c.take<float>(n);
         P.t = c.take<double>(n);
     }
-    P.scratch_bytes = max5(cast_ws_bytes(s), dz ? airlight_ws_bytes(s) : 0, gf_planes ? guided_ws_bytes(s) : 0,
-                           select_ws_bytes(s), clahe_ws_bytes(s, tx > 0 ? tx : 8, ty > 0 ? ty : 8));
-    const size_t cw = codes_ws_bytes(s, tx > 0 ? tx : 8, ty > 0 ? ty : 8);
-    if (cw > P.scratch_bytes) P.scratch_bytes = cw;
-    if (dz && !gf_planes && P.scratch_bytes < n * sizeof(float)) P.scratch_bytes = n * sizeof(float);
-    // round 4: cast detection's chunk pass leaves the level-0 quadrant histograms of the quadtree behind (six_stadigy surface with
-    // cast detection on; frames entry_fuse_takes).  They are written before the quadtree starts and read by its first launches.
-    size_t qoff = 0;
-    if (dz && p && p->surface == UWIE_SURFACE_SIX && p->cast_correct && p->forced_cast < 0 && entry_fuse_takes(s, p->min_size)) {
-        qoff = (std::max(cast_ws_bytes(s), airlight_ws_bytes(s)) + 255) & ~size_t(255);
-        if (P.scratch_bytes < qoff + quad_part_bytes(s)) P.scratch_bytes = qoff + quad_part_bytes(s);
-    }
+    P.scratch_bytes = e.scratch_bytes;
     P.scratch = c.take<char>(P.scratch_bytes);
-    P.planes = gf_planes;
-    if (dz && !gf_planes) P.t0 = static_cast<float *>(P.scratch);
-    if (qoff && P.scratch) P.qpart = reinterpret_cast<uint32_t *>(static_cast<char *>(P.scratch) + qoff);
+    P.planes = e.guided.planes;
+    if (e.t0_in_scratch) P.t0 = static_cast<float *>(P.scratch);
+    if (e.qpart && P.scratch) P.qpart = reinterpret_cast<uint32_t *>(static_cast<char *>(P.scratch) + e.qoff);
     return P;
 }
 
-// A parameter set whose carve_pipe layout holds every one of `n` six_stadigy sets (uwie_enhance_all_u8 runs them from
-// one workspace): dehazing layout, the exact-order guided filter's planes if any dehazing set's plan needs them, the largest
-// CLAHE tile grid.
-uwie_params merged_params(const uwie_params *ps, int n, Shape s)
+// The guided filter of a u8 dehazing call on P's buffers: t0 from `frame` (k_trans_init / k_trans_patch into P.t0, or inside
+// the fused kernel), then t (float32 data for t_f32 plans; everything downstream reads it through RestoreSrc::t32).
+int stage_guided(const Pipe &P, Shape s, const EnhancePlan &e, const FuseT0Args &frame, hipStream_t st)
 {
-    uwie_params m = ps[0];
-    m.surface = UWIE_SURFACE_SIX;
-    m.strategy = 2;
-    for (int i = 0; i < n; ++i) {
-        if (ps[i].surface == UWIE_SURFACE_SIX && ps[i].strategy == 3) m.strategy = 3;  // (its tail reads the stored planes)
-        if (ps[i].tiles_x > m.tiles_x) m.tiles_x = ps[i].tiles_x;
-        if (ps[i].tiles_y > m.tiles_y) m.tiles_y = ps[i].tiles_y;
-        if (ps[i].surface == UWIE_SURFACE_SIX && ps[i].strategy <= 3 && plan_guided(s, u8_guided(&ps[i])).planes) m.gf_exact = 1;
-    }
-    return m;
-}
-
-// The guided filter of a u8 dehazing call on P's buffers: t0 from `frame` (k_trans_init into P.t0, or inside the fused kernel),
-// then t.  *t_is_f32 (optional): t was written as float32; everything downstream reads it through RestoreSrc::t32.
-int stage_guided(const Pipe &P, Shape s, const uwie_params *p, const FuseT0Args &frame, hipStream_t st, int *t_is_f32 = nullptr)
-{
-    const GuidedPlan g = plan_guided(s, u8_guided(p));
+    const GuidedPlan &g = e.guided;
     // the exact-order filter builds its planes in the scratch, where t0 lives otherwise (enhance_all runs each set's own plan
     // in one merged layout)
     UWIE_REQUIRE(!g.planes || (P.planes && P.t0 != P.scratch), "guided filter: the workspace layout has no planes for the exact-order filter");
-    if (g.t0) UWIE_TRY(launch_t0(frame, dark_patch_of(p), s, P.t0, st));
-    UWIE_TRY(launch_guided_plan(g, s, P.gray, P.t0, P.t, P.scratch, st, &frame));
-    if (t_is_f32) *t_is_f32 = g.t_f32;
-    return UWIE_OK;
+    if (g.t0) UWIE_TRY(launch_t0(frame, e.dark_patch, s, P.t0, st));
+    return launch_guided_plan(g, s, P.gray, P.t0, P.t, P.scratch, st, &frame);
 }
 
 // enhance_contrast / white_balance (S6:191-199 / :211-219) of a float32 HWC image: two percentiles into pct [B][3][2], then
@@ -252,78 +312,55 @@ int stretch_f32(const float *img, float *out, Shape s, double lo, double hi, flo
 }
 
 // Cast detection (or the forced kind): what every six_stadigy strategy starts from.
-// then_airlight: six_airlight follows on the same Pipe -- the chunk pass may collect the level-0 quadrant histograms for it
-bool quad_from_cast(const uwie_params *p, const Pipe &P) { return P.qpart && p->forced_cast < 0 && p->cast_correct; }
-
-int six_cast(uwie_ctx *ctx, const uint8_t *d_in, Shape s, const uwie_params *p, const Pipe &P, const int32_t **kind,
-             hipStream_t st, bool then_airlight = false)
+int six_cast(uwie_ctx *ctx, const uint8_t *d_in, Shape s, const EnhancePlan &e, const uwie_params *p, const Pipe &P,
+             const int32_t **kind, hipStream_t st)
 {
     *kind = nullptr;
     if (p->forced_cast >= 0) {
         UWIE_TRY(launch_set_kind(P.kind, s.B, p->forced_cast, st));
         *kind = P.kind;
     } else if (p->cast_correct) {
-        // tuning entry_fuse = 2: histograms only, the gray plane comes out of the quadtree's pre-pass (k_gray_strong)
-        const EntryFuse ef{P.qpart, tune().entry_fuse == 2 ? nullptr : P.gray, P.guess, p->gray_shift};
-        UWIE_TRY(launch_cast_classify(ctx, d_in, s, P.kind, nullptr, P.scratch, st, then_airlight && quad_from_cast(p, P) ? &ef : nullptr));
+        const EntryFuse ef{P.qpart, e.cast_gray ? P.gray : nullptr, P.guess, p->gray_shift};
+        UWIE_TRY(launch_cast_classify(ctx, d_in, s, P.kind, nullptr, P.scratch, st, e.qpart ? &ef : nullptr));
         *kind = P.kind;
     }
     return UWIE_OK;
 }
 
 // Gray plane and atmospheric light: they depend on the (colour-corrected) frame only, so strategies 1-3 share them.
-int six_airlight(uwie_ctx *ctx, const uint8_t *d_in, const int32_t *kind, Shape s, const uwie_params *p, const Pipe &P,
-                 hipStream_t st, bool after_cast = false)
+int six_airlight(uwie_ctx *ctx, const uint8_t *d_in, const int32_t *kind, Shape s, const EnhancePlan &e, const uwie_params *p,
+                 const Pipe &P, hipStream_t st)
 {
-    const bool fused = after_cast && quad_from_cast(p, P);
     // (gray_shift 0: the plane is there already -- cast detection's chunk pass wrote it)
-    return launch_airlight(ctx, d_in, kind, P.gray, s, p->min_size, P.A, nullptr, P.scratch, st,
-                           fused && tune().entry_fuse != 2 ? 0 : p->gray_shift, fused ? P.qpart : nullptr);
+    return launch_airlight(ctx, d_in, kind, P.gray, s, p->min_size, P.A, nullptr, P.scratch, st, e.cast_gray ? 0 : p->gray_shift,
+                           e.qpart ? P.qpart : nullptr);
 }
 
 // Strategies 1-3 from (kind, gray, A) on: transmission -> guided filter -> restore -> stretch -> CLAHE / white balance.
-int six_dehaze_tail(uwie_ctx *ctx, const uint8_t *d_in, const int32_t *kind, Shape s, const uwie_params *p, const Pipe &P,
-                    uint8_t *d_out_u8, float *d_out_f32, hipStream_t st)
+int six_dehaze_tail(uwie_ctx *ctx, const uint8_t *d_in, const int32_t *kind, Shape s, const EnhancePlan &e, const uwie_params *p,
+                    const Pipe &P, uint8_t *d_out_u8, float *d_out_f32, hipStream_t st)
 {
     const float eps = 1e-6f;  // six_stadigy.py:198,218
-    const int k = p->strategy;
-    int t_is_f32 = 0;
-    UWIE_TRY(stage_guided(P, s, p, FuseT0Args{d_in, kind, P.A, (float)p->omega, 1e-6f, 1}, st, &t_is_f32));  // S6:170-180
-    // fused tail: restore writes the planar image into P.F and feeds the selection's first histogram sweep
+    const int k = p->strategy, nq = k == 3 ? 4 : 2, t_is_f32 = e.guided.t_f32;
+    UWIE_TRY(stage_guided(P, s, e, FuseT0Args{d_in, kind, P.A, (float)p->omega, 1e-6f, 1}, st));  // S6:170-180
+    // fused tail: restore feeds the selection's first histogram sweep (and writes the planar image into P.F where it is stored)
     SelectPlan plan;
     const double q[4] = {p->L_low, p->L_high, p->wb_percentile, 100 - p->wb_percentile};
-    // the restored image is clipped to [0, 1]: linear first digit, one collecting sweep (k_select.hip, select_lin_*);
-    // tuning select_generic keeps the three-digit key sweeps
     const RestoreSrc src{d_in, kind, P.A, P.t, t_is_f32};
-    bool recompute = false;
-    if (tune().select_generic) {
-        UWIE_TRY(select_begin<float>(s, q, k == 3 ? 4 : 2, P.scratch, st, &plan));
+    const RestoreSrc *recompute = e.store ? nullptr : &src;
+    if (e.generic) {
+        UWIE_TRY(select_begin<float>(s, q, nq, P.scratch, st, &plan));
         UWIE_TRY(launch_restore_planar_hist(d_in, kind, P.A, P.t, s, P.F, plan.ghist, st, false, nullptr, t_is_f32));
         UWIE_TRY(select_run(plan, P.F, 1, s, true, st));
     } else {
-        // Strategies 1 and 2 never store the restored image: the histogram sweep (which also files the elements of the
-        // predicted target bins, select_lin_begin) and the stretch each recompute it from the frame and t (restore.h:
-        // 11 + 14 bytes per pixel instead of 23 + 15, and no collecting sweep); so do the key-digit passes of planes the
-        // selection flags.  Tuning restore_store keeps the stored planes (4K x 64: 17.9 vs
-        // 17.5 ms per step, round 2); the tests compare both modes.
-        recompute = k != 3 && !tune().restore_store;
-        // Strategy 3 keeps the planes (its tail reads them), so the exact target bins can be collected from them by one
-        // streaming sweep: no predicted windows there -- its percentiles (20 / 85 / 2 / 98) sit where the bins are full and
-        // four windows made the restore sweep 2.9 ms at 4K x 16 against 0.65 + 0.35 for sweep + collection.
-        // Tuning lin_predict3 brings the windows back.
-        const bool predict = k != 3 || tune().lin_predict3;
-        UWIE_TRY(select_lin_begin<float>(s, q, k == 3 ? 4 : 2, P.scratch, st, &plan, predict ? &src : nullptr));
-        // (small jobs keep the histogram sweep: at 1080p x 1 the rank-counting kernels' fixed costs -- wavefront-private queues,
-        // a window-wide list for the finish -- make them 54 + 20 us against 34 + 14; tuning rank_sweep = 2 forces them anyway)
-        const bool big = (size_t)s.B * s.npx() >= ((size_t)1 << 24) || tune().rank_sweep >= 2;
-        if (recompute && plan.predicted && !t_is_f32 && tune().rank_sweep && big && s.npx() >= 4) {
-            // round 4: no histogram at all -- counts below the predicted windows + the windows' members (k_restore_rank)
+        // the restored image is clipped to [0, 1]: linear first digit, one collecting sweep (k_select.hip, select_lin_*)
+        UWIE_TRY(select_lin_begin<float>(s, q, nq, P.scratch, st, &plan, e.predict ? &src : nullptr));
+        if (e.rank && plan.predicted) {
             UWIE_TRY(launch_restore_rank(src, s, plan, st));
             UWIE_TRY(select_rank_run(plan, s, st, src));
         } else {
-            UWIE_TRY(launch_restore_planar_hist(d_in, kind, P.A, P.t, s, recompute ? nullptr : P.F, plan.ghist, st, true,
-                                                &plan, t_is_f32));
-            UWIE_TRY(select_lin_run(plan, P.F, s, st, recompute ? &src : nullptr));
+            UWIE_TRY(launch_restore_planar_hist(d_in, kind, P.A, P.t, s, e.store ? P.F : nullptr, plan.ghist, st, true, &plan, t_is_f32));
+            UWIE_TRY(select_lin_run(plan, P.F, s, st, recompute));
         }
     }
     if (k == 3) {
@@ -331,56 +368,54 @@ int six_dehaze_tail(uwie_ctx *ctx, const uint8_t *d_in, const int32_t *kind, Sha
         return launch_tail_plain(P.F, P.pct, 4, eps, 1, s, 0, 1.0, d_out_u8, d_out_f32, st);
     }
     UWIE_TRY(select_lerp(plan, s, P.pct, st));
-    return launch_tail_clahe(ctx, P.F, P.pct, 2, eps, 0, s, p->clip_limit, p->tiles_x, p->tiles_y, k == 1 ? 1 : 0,
-                             p->gamma, d_out_u8, d_out_f32, P.scratch, st, recompute ? &src : nullptr);
-}
-
-// Writes the strategy's float image to d_out_f32 and/or its (y*255).astype(u8) image to d_out_u8.
-int run_six(uwie_ctx *ctx, const uint8_t *d_in, Shape s, const uwie_params *p, const Pipe &P, uint8_t *d_out_u8,
-            float *d_out_f32, hipStream_t st)
-{
-    const int32_t *kind = nullptr;
-    const bool dz = p->strategy >= 1 && p->strategy <= 3;
-    UWIE_TRY(six_cast(ctx, d_in, s, p, P, &kind, st, dz));
-    if (dz) {
-        UWIE_TRY(six_airlight(ctx, d_in, kind, s, p, P, st, true));
-        return six_dehaze_tail(ctx, d_in, kind, s, p, P, d_out_u8, d_out_f32, st);
-    }
-    // strategies 4-6 never leave 8-bit data for long: evaluated as per-image LUT chains (k_codes.hip)
-    return launch_code_strategy(ctx, d_in, kind, s, p, d_out_u8, d_out_f32, P.scratch, st);
+    return launch_tail_clahe(ctx, P.F, P.pct, 2, eps, 0, s, p->clip_limit, e.tx, e.ty, k == 1 ? 1 : 0, p->gamma, d_out_u8, d_out_f32,
+                             P.scratch, st, recompute);
 }
 
 // enhancement_strategies.py apply_strong/medium/light (ES:350-444) on the uncorrected frame
 // have_airlight: P.gray and P.A already hold the gray plane and the atmospheric light of these frames (they depend on the
 // frame, min_size and gray_shift only: ES:353,379,425 all call estimate_atmospheric_light(img) -- uwie_select_best_u8 shares them)
-int run_dict_dehaze(uwie_ctx *ctx, const uint8_t *d_in, Shape s, const uwie_params *p, const Pipe &P, uint8_t *d_out_u8,
-                    float *d_out_f32, hipStream_t st, double *d_out_f64 = nullptr, bool have_airlight = false)
+int dict_dehaze(uwie_ctx *ctx, const uint8_t *d_in, Shape s, const EnhancePlan &e, const uwie_params *p, const Pipe &P,
+                uint8_t *d_out_u8, float *d_out_f32, double *d_out_f64, hipStream_t st, bool have_airlight)
 {
     if (!have_airlight)
         UWIE_TRY(launch_airlight(ctx, d_in, nullptr, P.gray, s, p->min_size, P.A, nullptr, P.scratch, st, p->gray_shift));
-    UWIE_TRY(stage_guided(P, s, p, FuseT0Args{d_in, nullptr, P.A, (float)p->omega, 1e-10f, 0}, st));  // ES:221-232
+    UWIE_TRY(stage_guided(P, s, e, FuseT0Args{d_in, nullptr, P.A, (float)p->omega, 1e-10f, 0}, st));  // ES:221-232
     SelectPlan plan;
     const double q[2] = {p->L_low, p->L_high};
-    // the recovered image is clipped to [0, 1]: linear first digit, one collecting sweep (select_lin_*<double>);
-    // tuning select_generic keeps the six-digit key sweeps
     const RestoreSrc src{d_in, nullptr, P.A, P.t};
-    bool recompute = false;
-    if (tune().select_generic) {
+    const RestoreSrc *recompute = e.store ? nullptr : &src;
+    if (e.generic) {
         UWIE_TRY(select_begin<double>(s, q, 2, P.scratch, st, &plan));
         UWIE_TRY(launch_recover64_planar_hist(d_in, P.A, P.t, s, P.F64, plan.ghist, st));
         UWIE_TRY(select_run(plan, P.F64, 1, s, true, st));
     } else {
-        // the float64 image (24 B/px) is not stored either: histogram sweep, collecting sweep and stretch recompute it
-        // from the frame and t (11 B/px each), and so do the key-digit passes of flagged planes.  Tuning restore_store keeps
-        // the stored planes.
-        recompute = !tune().restore_store;
+        // the recovered image is clipped to [0, 1]: linear first digit, one collecting sweep (select_lin_*<double>)
         UWIE_TRY(select_lin_begin<double>(s, q, 2, P.scratch, st, &plan, &src));
-        UWIE_TRY(launch_recover64_planar_hist(d_in, P.A, P.t, s, recompute ? nullptr : P.F64, plan.ghist, st, true, &plan));
-        UWIE_TRY(select_lin_run(plan, P.F64, s, st, recompute ? &src : nullptr));
+        UWIE_TRY(launch_recover64_planar_hist(d_in, P.A, P.t, s, e.store ? P.F64 : nullptr, plan.ghist, st, true, &plan));
+        UWIE_TRY(select_lin_run(plan, P.F64, s, st, recompute));
     }
     UWIE_TRY(select_lerp(plan, s, P.pct64, st));
-    return launch_tail_plain64(P.F64, P.pct64, s, p->apply_gamma, p->gamma, d_out_u8, d_out_f32, st, recompute ? &src : nullptr,
-                               d_out_f64);
+    return launch_tail_plain64(P.F64, P.pct64, s, p->apply_gamma, p->gamma, d_out_u8, d_out_f32, st, recompute, d_out_f64);
+}
+
+// Runs a u8 call as planned on P's buffers: the strategy's float image goes to d_out_f32 / d_out_f64 (dict surface) and / or
+// its (y*255).astype(u8) image to d_out_u8.  have_airlight: see dict_dehaze.
+int run_enhance(uwie_ctx *ctx, const uint8_t *d_in, Shape s, const EnhancePlan &e, const uwie_params *p, const Pipe &P,
+                uint8_t *d_out_u8, float *d_out_f32, double *d_out_f64, hipStream_t st, bool have_airlight = false)
+{
+    const int32_t *kind = nullptr;
+    switch (e.pipeline) {
+    case EP_SIX_DEHAZE:
+        UWIE_TRY(six_cast(ctx, d_in, s, e, p, P, &kind, st));
+        UWIE_TRY(six_airlight(ctx, d_in, kind, s, e, p, P, st));
+        return six_dehaze_tail(ctx, d_in, kind, s, e, p, P, d_out_u8, d_out_f32, st);
+    case EP_SIX_CODES:  // strategies 4-6 never leave 8-bit data for long: evaluated as per-image LUT chains (k_codes.hip)
+        UWIE_TRY(six_cast(ctx, d_in, s, e, p, P, &kind, st));
+        return launch_code_strategy(ctx, d_in, kind, s, p, d_out_u8, d_out_f32, P.scratch, st);
+    case EP_DICT_DEHAZE: return dict_dehaze(ctx, d_in, s, e, p, P, d_out_u8, d_out_f32, d_out_f64, st, have_airlight);
+    default: return launch_code_strategy(ctx, d_in, nullptr, s, p, d_out_u8, d_out_f32, P.scratch, st, d_out_f64);
+    }
 }
 
 int check_params(const uwie_params *p)
@@ -423,9 +458,6 @@ struct FloatPipe {
     double *F64;    // DICT: recovered image, planar
     void *scratch;
     size_t scratch_bytes;
-    uint32_t *qpart;  // level-0 quadrant shares of cast detection's chunks (tuning entry_fuse; inside the scratch, behind what cast
-                      // detection and the quadtree use), or nullptr
-    int32_t *guess;   // ... and the cast kinds its gray plane was first written for
 };
 
 template <class T>
@@ -452,8 +484,9 @@ FloatPipe<T> carve_float(Carver &c, Shape s, const uwie_params *p)
         P.F64 = c.take<double>(n * 3);
     }
     const int tx = p->tiles_x > 0 ? p->tiles_x : 8, ty = p->tiles_y > 0 ? p->tiles_y : 8;
-    P.scratch_bytes = max5(dz ? float_airlight_ws_bytes(s) : 0, dz ? guided_ws_bytes(s) : 0, select_ws_bytes(s), clahe_ws_bytes(s, tx, ty),
-                           codes_ws_bytes(s, tx, ty));
+    const size_t none = 0;
+    P.scratch_bytes = std::max({dz ? float_airlight_ws_bytes(s) : none, dz ? guided_ws_bytes(s) : none, select_ws_bytes(s),
+                                clahe_ws_bytes(s, tx, ty), codes_ws_bytes(s, tx, ty)});
     P.scratch = c.take<char>(P.scratch_bytes);
     return P;
 }
@@ -839,38 +872,58 @@ static int enhance_split(int batch)
     return batch >= n ? n : 1;
 }
 
+// The buffers of a uwie_enhance_u8 call that runs its batch as nsplit (1 .. 4, at most the batch) sub-batches: their counts and
+// first frames, and for each its own plan and its own slice of the workspace (256-byte aligned; `bytes` is where the last one ends).
+struct EnhanceLayout {
+    int nsplit;
+    int cnt[4], start[4];
+    EnhancePlan plan[4];
+    Pipe P[4];
+    size_t bytes;
+};
+
+static EnhanceLayout carve_enhance(void *d_workspace, Shape s, const uwie_params *p, int nsplit)
+{
+    EnhanceLayout L{};
+    L.nsplit = nsplit;
+    for (int i = 0, b0 = 0; i < nsplit; b0 += L.cnt[i++]) {
+        L.cnt[i] = s.B / nsplit + (i < s.B % nsplit ? 1 : 0);
+        L.start[i] = b0;
+        const Shape si{L.cnt[i], s.H, s.W};
+        Carver c(d_workspace ? static_cast<char *>(d_workspace) + L.bytes : nullptr);
+        L.plan[i] = plan_enhance(si, p);
+        L.P[i] = carve_pipe(c, si, L.plan[i]);
+        L.bytes += c.total();
+    }
+    return L;
+}
+
+// The layout of a call on this workspace: the whole batch in one Pipe, or -- tuning `streams`, may_split -- sub-batches, unless
+// the caller's buffer cannot hold their slices (a caller that sized for another parameter set).  uwie_enhance_percentiles finds
+// the last call's percentiles by the same carving, so the two cannot disagree.  *need: the single layout's bytes (what the call
+// requires of the workspace).
+static EnhanceLayout enhance_layout(void *d_workspace, size_t workspace_bytes, Shape s, const uwie_params *p, bool may_split, size_t *need)
+{
+    const EnhanceLayout whole = carve_enhance(d_workspace, s, p, 1);
+    *need = whole.bytes;
+    const int nsplit = may_split ? enhance_split(s.B) : 1;
+    if (nsplit < 2) return whole;
+    const EnhanceLayout split = carve_enhance(d_workspace, s, p, nsplit);
+    return split.bytes <= workspace_bytes ? split : whole;
+}
+
 size_t uwie_workspace_bytes(int batch, int H, int W, const uwie_params *p)
 {
     if (!shape_ok(batch, H, W)) return 0;
     const Shape s{batch, H, W};
-    Carver c(nullptr);
-    carve_pipe(c, s, p);
-    size_t pipe = c.total();
     // uwie_enhance_u8 may run the batch as up to four sub-batches on separate streams (tuning `streams`), each with its own
     // slice: sized for whichever split is the largest, so the answer does not depend on a context
-    for (int nsplit = 2; nsplit <= 4 && nsplit <= batch; ++nsplit) {
-        size_t off = 0;
-        for (int i = 0; i < nsplit; ++i) {
-            Carver ci(nullptr);
-            carve_pipe(ci, Shape{batch / nsplit + (i < batch % nsplit ? 1 : 0), H, W}, p);
-            off = (off + ci.total() + 255) & ~(size_t)255;
-        }
-        if (off > pipe) pipe = off;
-    }
+    size_t pipe = 0;
+    for (int nsplit = 1; nsplit <= 4 && nsplit <= batch; ++nsplit) pipe = std::max(pipe, carve_enhance(nullptr, s, p, nsplit).bytes);
     if (p) return pipe;  // a pipeline call with these parameters
     // p == NULL: any stage entry point; they carve their own (smaller) layouts from the same buffer
-    size_t stage = canny_ws_bytes(s) + (size_t)batch * sizeof(Region) + 256;
-    const size_t gf = guided_ws_bytes(s);
-    if (gf > stage) stage = gf;
-    const size_t ft = features_ws_bytes(s);
-    if (ft > stage) stage = ft;
-    const size_t qa = quality_ws_bytes(s);
-    if (qa > stage) stage = qa;
-    const size_t cl = clahe_ws_bytes(s, 8, 8);
-    if (cl > stage) stage = cl;
-    const size_t al = airlight_ws_bytes(s) + (size_t)batch * s.npx() + 256;
-    if (al > stage) stage = al;
-    return pipe > stage ? pipe : stage;
+    return std::max({pipe, canny_ws_bytes(s) + (size_t)batch * sizeof(Region) + 256, guided_ws_bytes(s), features_ws_bytes(s),
+                     quality_ws_bytes(s), clahe_ws_bytes(s, 8, 8), airlight_ws_bytes(s) + (size_t)batch * s.npx() + 256});
 }
 
 size_t uwie_workspace_bytes_ctx(uwie_ctx *ctx, int batch, int H, int W, const uwie_params *p)
@@ -889,49 +942,10 @@ size_t uwie_workspace_bytes_all(int batch, int H, int W, const uwie_params *p6)
         else if (uwie_params_init(&P6[k], UWIE_SURFACE_SIX, k + 1) != UWIE_OK) return 0;
     }
     const Shape s{batch, H, W};
-    const uwie_params Pm = merged_params(P6, 6, s);
+    EnhancePlan six[6];
     Carver c(nullptr);
-    carve_pipe(c, s, &Pm);
+    carve_pipe(c, s, plan_enhance_all(s, P6, six));
     return c.total();
-}
-
-// The buffers of a uwie_enhance_u8 call on this workspace: the whole batch in one Pipe (nsplit = 1), or -- tuning `streams`,
-// may_split -- up to four sub-batches, each with its own slice.  uwie_enhance_percentiles finds the last call's percentiles
-// by the same carving, so the two cannot disagree.  total: the single layout's bytes (what the call requires of the workspace).
-struct EnhanceLayout {
-    int nsplit;
-    int cnt[4], start[4];
-    Pipe P[4];
-    size_t total;
-};
-
-static EnhanceLayout carve_enhance(void *d_workspace, size_t workspace_bytes, Shape s, const uwie_params *p, bool may_split)
-{
-    EnhanceLayout L{};
-    Carver c(d_workspace);
-    L.P[0] = carve_pipe(c, s, p);
-    L.total = c.total();
-    L.nsplit = 1;
-    L.cnt[0] = s.B;
-    L.start[0] = 0;
-    const int nsplit = may_split ? enhance_split(s.B) : 1;
-    if (nsplit >= 2 && s.B >= nsplit) {
-        EnhanceLayout S = L;
-        size_t off = 0;
-        bool fits_ws = true;
-        for (int i = 0, b0 = 0; i < nsplit; ++i) {
-            S.cnt[i] = s.B / nsplit + (i < s.B % nsplit ? 1 : 0);
-            S.start[i] = b0;
-            b0 += S.cnt[i];
-            Carver ci(static_cast<char *>(d_workspace) + off);
-            S.P[i] = carve_pipe(ci, Shape{S.cnt[i], s.H, s.W}, p);
-            if (off + ci.total() > workspace_bytes) fits_ws = false;  // (a caller that sized for another parameter set)
-            off = (off + ci.total() + 255) & ~(size_t)255;
-        }
-        S.nsplit = nsplit;
-        if (fits_ws) L = S;
-    }
-    return L;
 }
 
 int uwie_enhance_u8(uwie_ctx *ctx, const uint8_t *d_in, uint8_t *d_out_u8, float *d_out_f32, int batch, int H, int W,
@@ -941,18 +955,16 @@ int uwie_enhance_u8(uwie_ctx *ctx, const uint8_t *d_in, uint8_t *d_out_u8, float
     UWIE_SCOPE(ctx);
     UWIE_CHECK_SHAPE(batch, H, W);
     UWIE_TRY(check_params(p));
-    const Shape s{batch, H, W};
-    const EnhanceLayout L = carve_enhance(d_workspace, workspace_bytes, s, p, true);
-    UWIE_CHECK_WS(L.total);
+    size_t need;
+    const EnhanceLayout L = enhance_layout(d_workspace, workspace_bytes, Shape{batch, H, W}, p, true, &need);
+    UWIE_CHECK_WS(need);
     ctx->last_enhance_f64 = false;
-    const Pipe &P = L.P[0];
     hipStream_t st = (hipStream_t)stream;
-    // Frames are independent, so the batch runs as sub-batches on separate streams: while one sits in an issue-bound
-    // stage (guided filter) another can be in a memory-bound one.  The caller's stream waits for all of them.
-    const int nsplit = L.nsplit;
-    if (nsplit >= 2) {
-        const int *cnt = L.cnt, *start = L.start;
-        const Pipe *Ps = L.P;
+    // Frames are independent, so the batch may run as sub-batches on separate streams: while one sits in an issue-bound
+    // stage (guided filter) another can be in a memory-bound one.  The caller's stream waits for all of them.  A single
+    // sub-batch runs on the caller's stream: no helper streams, no events.
+    const bool fork = L.nsplit >= 2;
+    if (fork) {
         if (!ctx->aux_ready) {
             for (int i = 0; i < 4; ++i) {
                 UWIE_HIP_CHECK(hipStreamCreateWithFlags(&ctx->aux[i], hipStreamNonBlocking));
@@ -962,29 +974,17 @@ int uwie_enhance_u8(uwie_ctx *ctx, const uint8_t *d_in, uint8_t *d_out_u8, float
             ctx->aux_ready = true;
         }
         UWIE_HIP_CHECK(hipEventRecord(ctx->fork, st));
-        const size_t px = (size_t)H * W;
-        for (int i = 0; i < nsplit; ++i) {
-            UWIE_HIP_CHECK(hipStreamWaitEvent(ctx->aux[i], ctx->fork, 0));
-            const size_t b0 = (size_t)start[i];
-            const Shape si{cnt[i], H, W};
-            const uint8_t *in_i = d_in + b0 * px * 3;
-            uint8_t *o8 = d_out_u8 ? d_out_u8 + b0 * px * 3 : nullptr;
-            float *of = d_out_f32 ? d_out_f32 + b0 * px * 3 : nullptr;
-            int rc;
-            if (p->surface == UWIE_SURFACE_SIX) rc = run_six(ctx, in_i, si, p, Ps[i], o8, of, ctx->aux[i]);
-            else if (!dehazes(p)) rc = launch_code_strategy(ctx, in_i, nullptr, si, p, o8, of, Ps[i].scratch, ctx->aux[i]);
-            else rc = run_dict_dehaze(ctx, in_i, si, p, Ps[i], o8, of, ctx->aux[i]);
-            if (rc != UWIE_OK) return rc;
-            UWIE_HIP_CHECK(hipEventRecord(ctx->join[i], ctx->aux[i]));
-        }
-        for (int i = 0; i < nsplit; ++i) UWIE_HIP_CHECK(hipStreamWaitEvent(st, ctx->join[i], 0));
-        return UWIE_OK;
     }
-    if (p->surface == UWIE_SURFACE_SIX) {
-        return run_six(ctx, d_in, s, p, P, d_out_u8, d_out_f32, st);
+    for (int i = 0; i < L.nsplit; ++i) {
+        hipStream_t sti = fork ? ctx->aux[i] : st;
+        if (fork) UWIE_HIP_CHECK(hipStreamWaitEvent(sti, ctx->fork, 0));
+        const size_t first = (size_t)L.start[i] * H * W * 3;
+        UWIE_TRY(run_enhance(ctx, d_in + first, Shape{L.cnt[i], H, W}, L.plan[i], p, L.P[i], d_out_u8 ? d_out_u8 + first : nullptr,
+                             d_out_f32 ? d_out_f32 + first : nullptr, nullptr, sti));
+        if (fork) UWIE_HIP_CHECK(hipEventRecord(ctx->join[i], sti));
     }
-    if (!dehazes(p)) return launch_code_strategy(ctx, d_in, nullptr, s, p, d_out_u8, d_out_f32, P.scratch, st);
-    return run_dict_dehaze(ctx, d_in, s, p, P, d_out_u8, d_out_f32, st);
+    for (int i = 0; fork && i < L.nsplit; ++i) UWIE_HIP_CHECK(hipStreamWaitEvent(st, ctx->join[i], 0));
+    return UWIE_OK;
 }
 
 int uwie_enhance_u8_f64(uwie_ctx *ctx, const uint8_t *d_in, uint8_t *d_out_u8, double *d_out_f64, int batch, int H, int W,
@@ -995,16 +995,12 @@ int uwie_enhance_u8_f64(uwie_ctx *ctx, const uint8_t *d_in, uint8_t *d_out_u8, d
     UWIE_CHECK_SHAPE(batch, H, W);
     UWIE_TRY(check_params(p));
     UWIE_REQUIRE(p->surface == UWIE_SURFACE_DICT, "enhance_f64: float64 images are the dict surface's (ES:247,307,345)");
-    const Shape s{batch, H, W};
-    Carver c(d_workspace);
-    Pipe P = carve_pipe(c, s, p);
-    UWIE_CHECK_WS(c.total());
+    size_t need;
+    const EnhanceLayout L = enhance_layout(d_workspace, workspace_bytes, Shape{batch, H, W}, p, false, &need);
+    UWIE_CHECK_WS(need);
     ctx->last_enhance_f64 = true;  // (the whole batch in one layout: uwie_enhance_percentiles reads that one)
-    hipStream_t st = (hipStream_t)stream;
-    if (!dehazes(p)) return launch_code_strategy(ctx, d_in, nullptr, s, p, d_out_u8, nullptr, P.scratch, st, d_out_f64);
-    return run_dict_dehaze(ctx, d_in, s, p, P, d_out_u8, nullptr, st, d_out_f64);
+    return run_enhance(ctx, d_in, Shape{batch, H, W}, L.plan[0], p, L.P[0], d_out_u8, nullptr, d_out_f64, (hipStream_t)stream);
 }
-
 
 size_t uwie_workspace_bytes_float(int batch, int H, int W, const uwie_params *p, int elem_bytes)
 {
@@ -1081,21 +1077,21 @@ int uwie_enhance_all_u8(uwie_ctx *ctx, const uint8_t *d_in, uint8_t *d_out_u8, i
     }
     const Shape s{batch, H, W};
     Carver c(d_workspace);
-    const uwie_params Pm = merged_params(P6, 6, s);
-    Pipe P = carve_pipe(c, s, &Pm);  // a dehazing layout sized for the most demanding of the six sets
+    EnhancePlan six[6];
+    const Pipe P = carve_pipe(c, s, plan_enhance_all(s, P6, six));  // a dehazing layout sized for the most demanding of the six sets
     UWIE_CHECK_WS(c.total());
     hipStream_t st = (hipStream_t)stream;
     const int32_t *kind = nullptr;
-    UWIE_TRY(six_cast(ctx, d_in, s, &P6[0], P, &kind, st, true));
+    UWIE_TRY(six_cast(ctx, d_in, s, six[0], &P6[0], P, &kind, st));
     if (d_kind) {
         if (kind) UWIE_HIP_CHECK(hipMemcpyAsync(d_kind, kind, sizeof(int32_t) * batch, hipMemcpyDeviceToDevice, st));
         else UWIE_HIP_CHECK(hipMemsetAsync(d_kind, 0, sizeof(int32_t) * batch, st));
     }
-    UWIE_TRY(six_airlight(ctx, d_in, kind, s, &P6[0], P, st, true));
+    UWIE_TRY(six_airlight(ctx, d_in, kind, s, six[0], &P6[0], P, st));
     const size_t out_stride = (size_t)batch * H * W * 3;
     for (int k = 0; k < 6; ++k) {
         uint8_t *out = d_out_u8 + (size_t)k * out_stride;
-        if (k < 3) UWIE_TRY(six_dehaze_tail(ctx, d_in, kind, s, &P6[k], P, out, nullptr, st));
+        if (k < 3) UWIE_TRY(six_dehaze_tail(ctx, d_in, kind, s, six[k], &P6[k], P, out, nullptr, st));
         else UWIE_TRY(launch_code_strategy(ctx, d_in, kind, s, &P6[k], out, nullptr, P.scratch, st));
     }
     return UWIE_OK;
@@ -1115,7 +1111,7 @@ SelectBufs carve_select(Carver &c, Shape s, const uwie_params *ps, int n, bool o
     SelectBufs b{};
     for (int k = 0; k < n; ++k) {
         Carver ck(nullptr);
-        carve_pipe(ck, s, &ps[k]);
+        carve_pipe(ck, s, plan_enhance(s, &ps[k]));
         if (ck.total() > b.pipe_bytes) b.pipe_bytes = ck.total();
     }
     b.pipe = c.take<char>(b.pipe_bytes);
@@ -1155,21 +1151,15 @@ int uwie_select_best_u8(uwie_ctx *ctx, const uint8_t *d_in, int batch, int H, in
     for (int k = 0; k < n; ++k) {
         const uwie_params *p = &ps[k];
         Carver ck(sb.pipe);
-        Pipe P = carve_pipe(ck, s, p);
+        const EnhancePlan e = plan_enhance(s, p);
+        const Pipe P = carve_pipe(ck, s, e);
         uint8_t *out = all + (size_t)k * frame_set;
-        if (p->surface == UWIE_SURFACE_SIX) {
-            UWIE_TRY(run_six(ctx, d_in, s, p, P, out, sb.f32, st));
-            shared_with = -1;
-        } else if (!dehazes(p)) {
-            UWIE_TRY(launch_code_strategy(ctx, d_in, nullptr, s, p, out, sb.f32, P.scratch, st));
-            shared_with = -1;
-        } else {
-            // one quadtree for all the dehazing sets that follow each other with the same leaf size and gray coefficients
-            const bool have = shared_with >= 0 && ps[shared_with].min_size == p->min_size && ps[shared_with].gray_shift == p->gray_shift &&
-                              ps[shared_with].gf_exact == p->gf_exact;
-            UWIE_TRY(run_dict_dehaze(ctx, d_in, s, p, P, out, sb.f32, st, nullptr, have));
-            if (!have) shared_with = k;
-        }
+        // one quadtree for all the dict dehazing sets that follow each other with the same leaf size and gray coefficients
+        const bool have = e.pipeline == EP_DICT_DEHAZE && shared_with >= 0 && ps[shared_with].min_size == p->min_size &&
+                          ps[shared_with].gray_shift == p->gray_shift && ps[shared_with].gf_exact == p->gf_exact;
+        UWIE_TRY(run_enhance(ctx, d_in, s, e, p, P, out, sb.f32, nullptr, st, have));
+        if (e.pipeline != EP_DICT_DEHAZE) shared_with = -1;
+        else if (!have) shared_with = k;
         // (img * 255).astype(uint8) is what every score but colourfulness starts from; that one takes the float image
         UWIE_TRY(launch_quality_scores(ctx, out, sb.f32, s, p->gray_shift, weights8 ? weights8 : kDefault,
                                        d_scores + (size_t)k * batch * 9, sb.qa, st));
@@ -2072,8 +2062,9 @@ int uwie_enhance_percentiles(uwie_ctx *ctx, const void *d_workspace, size_t work
     UWIE_TRY(check_params(p));
     UWIE_REQUIRE(dehazes(p), "enhance_percentiles: only the dehazing strategies select percentiles in the workspace");
     const Shape s{batch, H, W};
-    const EnhanceLayout L = carve_enhance(const_cast<void *>(d_workspace), workspace_bytes, s, p, !ctx->last_enhance_f64);
-    UWIE_CHECK_WS(L.total);
+    size_t need;
+    const EnhanceLayout L = enhance_layout(const_cast<void *>(d_workspace), workspace_bytes, s, p, !ctx->last_enhance_f64, &need);
+    UWIE_CHECK_WS(need);
     hipStream_t st = (hipStream_t)stream;
     const bool dict = p->surface == UWIE_SURFACE_DICT;
     const size_t per = (!dict && p->strategy == 3) ? 4 : 2;  // values per (image, channel)
