@@ -625,6 +625,59 @@ int uwie_select_best_u8(uwie_ctx *ctx, const uint8_t *d_in, int batch, int H, in
                         const double *weights8, uint8_t *d_best_u8, int32_t *d_best, double *d_scores, uint8_t *d_all_u8,
                         void *d_workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * UCIQE and UIQM, the two no-reference metrics the underwater-enhancement literature reports, in a fixed form.  An extension
+ * without a reference counterpart (like uwie_params.dark_patch): this comment is the contract, tests/uw_quality_ref.py restates
+ * it in NumPy.  The papers' PLIP operators and image-dependent block counts are left out on purpose: 8 x 8 blocks, plain
+ * arithmetic, so that almost everything is a function of integer histograms and integer block extrema.
+ *
+ * Input: a u8 RGB frame, H x W, n = H * W pixels.  All arithmetic not marked integer is float64.
+ *   UCIQE  (L8, a8, b8) = the 8-bit LAB triple of uwie_rgb2lab_u8; da = a8 - 128, db = b8 - 128; C = sqrt(da^2 + db^2) / 255.
+ *          sigma_c = population standard deviation of C over the frame.
+ *          con_l   = (L8 sorted ascending at index min(99 * n / 100, n - 1)  -  L8 sorted ascending at index n / 100) / 255
+ *                    (integer divisions).
+ *          mu_s    = mean over all n pixels of sqrt(da^2 + db^2) / L8 where L8 > 0, and of 0 where L8 = 0.
+ *          UCIQE   = 0.4680 * sigma_c + 0.2745 * con_l + 0.2576 * mu_s.
+ *   UIQM   = 0.0282 * UICM + 0.2953 * UISM + 3.5753 * UIConM.  The 8 x 8 blocks below are the (H / 8) x (W / 8) full blocks counted
+ *          from the top left corner; remainder rows and columns are ignored; with no block (H < 8 or W < 8) UISM = UIConM = 0.
+ *          UICM    RG = R - G (integer, -255 .. 255) and YB2 = R + G - 2 B (integer, -510 .. 510).  Of each plane, sorted
+ *                  ascending, the t = n / 10 smallest and the t largest values are dropped; m = n - 2 t >= 1 remain; mu = their mean,
+ *                  var = the mean of (x - mu)^2 over them.  mu_YB = mu_YB2 / 2, var_YB = var_YB2 / 4.
+ *                  UICM = -0.0268 * sqrt(mu_RG^2 + mu_YB^2) + 0.1586 * sqrt(var_RG + var_YB).
+ *          UISM    per channel c: gx, gy = the 3 x 3 Sobel responses (-1 0 1 / -2 0 2 / -1 0 1 and its transpose) of the channel's
+ *                  bytes, BORDER_REFLECT_101 at the frame's border; q = min(gx^2 + gy^2, 65025) * c^2 with c the pixel's byte
+ *                  (an integer <= 65025^2 < 2^32).  A block's term is ln(q_max / q_min) over its 64 pixels if q_min > 0, else 0;
+ *                  EME_c = the mean of the terms over the blocks; UISM = 0.299 * EME_R + 0.587 * EME_G + 0.114 * EME_B.
+ *                  (The EME of the map edge magnitude x channel; the ratio of two products is taken on their exact squares.)
+ *          UIConM  g = the gray byte (uwie_rgb2gray_u8 with gray_shift); per block M, m = its extrema, r = (M - m) / (M + m);
+ *                  the block's term is r * ln r if M > m, else 0; UIConM = minus the mean of the terms.
+ * A frame of one gray level scores 0 in all eight; the sign of a zero is not part of the contract.
+ *
+ * d_scores: [batch][UWIE_UW_SCORES] float64 = sigma_c, con_l, mu_s, UCIQE, UICM, UISM, UIConM, UIQM.
+ * Exact: con_l, UICM's moments (integer sums from the 256-, 511- and 1021-bin histograms up to the last divisions), every block's
+ * extrema and branch.  sigma_c and mu_s are float64 sums over the pixels; against the float64 evaluation every score is held
+ * to 1e-9 (tests/test_gpu_uw_quality.py).  Deterministic as uwie_quality_scores: a frame's eight numbers are the same bits in
+ * every run and at every position of every batch (integer atomics, float64 partials per block and per tile added in their
+ * order; the grids depend on H and W only).  A fixed number of launches, no host read.  batch <= 65535.
+ * uwie_underwater_plan: the tile (*tile_w x *tile_h pixels, multiples of 8, anchored at the frame's top left corner) that one
+ * workgroup of the block pass stages with a one-pixel halo: the launcher runs on these numbers, so a test can aim at the seams.
+ * Workspace: uwie_workspace_bytes_underwater(batch, H, W) (7 KB per frame plus at most 48 bytes per 1024 pixels).
+ */
+#define UWIE_UW_SCORES 8
+size_t uwie_workspace_bytes_underwater(int batch, int H, int W);
+int uwie_underwater_plan(int H, int W, int *tile_w, int *tile_h);
+int uwie_underwater_scores_u8(uwie_ctx *ctx, const uint8_t *d_u8, int batch, int H, int W, int gray_shift, double *d_scores,
+                              void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * best[b] = the FIRST maximum over the n sets, in their order, of d_scores[k][b][col] (d_scores: [n][batch][ncols] float64; the
+ * pick of uwie_select_best_u8 generalised over the column).  With d_all_u8 [n][batch][H][W][3] and d_best_u8 [batch][H][W][3]
+ * (both optional, given together) the winner's frame is gathered: d_best_u8[b] = d_all_u8[best[b]][b].  Without them H and W
+ * are not read.  n: 1 .. 65535; a NaN never beats the running maximum.
+ */
+int uwie_pick_best_u8(uwie_ctx *ctx, const double *d_scores, int n, int batch, int ncols, int col, const uint8_t *d_all_u8, int H,
+                      int W, int32_t *d_best, uint8_t *d_best_u8, void *stream);
+
 /* ---------------- strategy classifier: main.py:398-433 (predict) ---------------- */
 
 /*

@@ -1284,6 +1284,77 @@ def select_best(frames, strategies=None, weights=None, device: int | None = None
     return out
 
 
+# include/uwie.h uwie_underwater_scores_u8: the columns of a row of underwater scores
+UNDERWATER_SCORE_NAMES = ("sigma_c", "con_l", "mu_s", "uciqe", "uicm", "uism", "uiconm", "uiqm")
+
+
+def underwater_scores(frames, device: int | None = None):
+    """UCIQE, UIQM and their parts in the fixed form include/uwie.h states (an extension without a reference counterpart), on
+    the device: uint8 ``[H,W,3]`` / ``[B,H,W,3]``, NumPy or a torch ROCm tensor -> float64 ``(8,)`` / ``(B, 8)`` of the same
+    kind, columns in ``UNDERWATER_SCORE_NAMES`` order."""
+    dev = get_device(device)
+    batch, was_numpy, single = _as_batch_u8(frames, dev)
+    return _finish(dev.underwater_scores(batch), was_numpy, single, dev)
+
+
+class UnderwaterQuality:
+    """UCIQE / UIQM of one image: a uint8 RGB frame, or a float image in [0, 1] quantised with ``(x * 255).astype(uint8)``
+    like every score of ``QualityAssessment``."""
+
+    device: int | None = None
+
+    @classmethod
+    def scores(cls, img) -> dict:
+        """``{name: value}`` for every entry of ``UNDERWATER_SCORE_NAMES``."""
+        x = np.asarray(img.cpu() if hasattr(img, "data_ptr") else img)
+        if x.ndim != 3 or x.shape[2] != 3:
+            raise ValueError(f"expected an HxWx3 image, got {x.shape}")
+        u8 = x if x.dtype == np.uint8 else (x * 255).astype(np.uint8)
+        row = underwater_scores(np.ascontiguousarray(u8), device=cls.device)
+        return {k: float(row[i]) for i, k in enumerate(UNDERWATER_SCORE_NAMES)}
+
+    @classmethod
+    def uciqe(cls, img) -> float:
+        return cls.scores(img)["uciqe"]
+
+    @classmethod
+    def uiqm(cls, img) -> float:
+        return cls.scores(img)["uiqm"]
+
+
+def select_best_underwater(frames, strategies=None, metric: str = "uiqm", device: int | None = None, return_all: bool = False):
+    """``select_best``'s labelling loop with the winner picked by an underwater metric instead of the weighted total: every
+    entry of ``strategies`` (default ``Config.STRATEGIES``; a dict like ``select_best``'s, or a list of ``(key, params)`` pairs,
+    which can name a key more than once) is applied to the frames (uwie_select_best_u8 with its outputs kept), the n * B results are scored in one uwie_underwater_scores_u8 call, and per frame the first maximum of ``metric``
+    (``"uiqm"`` or ``"uciqe"``) in the strategies' order wins (uwie_pick_best_u8).  Nothing comes back to the host in between.
+
+    Returns ``(best_names, best_images, scores)``: the winner's ``'name'`` per frame (a string for a single frame), its uint8
+    image, and ``scores`` shaped ``(n, B, 8)`` (B = 1 for a single frame) in ``UNDERWATER_SCORE_NAMES`` order, the sets in
+    ``strategies``' order; with ``return_all`` a fourth value ``{name: uint8 batch}`` holds every strategy's output."""
+    if metric not in ("uiqm", "uciqe"):
+        raise ValueError(f"metric must be 'uiqm' or 'uciqe', got {metric!r}")
+    strategies = CONFIG_STRATEGIES if strategies is None else strategies
+    sets = list(strategies.items()) if isinstance(strategies, dict) else [(k, dict(v)) for k, v in strategies]
+    dev = get_device(device)
+    batch, was_numpy, single = _as_batch_u8(frames, dev)
+    for k, _ in sets:
+        if k not in _lib.DICT_STRATEGIES:
+            raise ValueError(f"未知策略: {k}")
+    plist = [_dict_params(dev, k, v) for k, v in sets]
+    names = [v.get("name", k) for k, v in sets]
+    _, _, _, every = dev.select_best_u8(batch, plist, None, want_all=True)
+    n, B, H, W = (int(v) for v in every.shape[:4])
+    scores = dev.underwater_scores(every.view(n * B, H, W, 3), gray_shift=plist[0].gray_shift).view(n, B, len(UNDERWATER_SCORE_NAMES))
+    best, img = dev.pick_best_u8(scores, UNDERWATER_SCORE_NAMES.index(metric), every)
+    best_h = best.cpu().tolist()
+    dev.check_status()
+    best_names = [names[i] for i in best_h]
+    out = (best_names[0] if single else best_names, _finish(img, was_numpy, single), scores.cpu().numpy() if was_numpy else scores)
+    if return_all:
+        out = out + ({names[k]: _finish(every[k], was_numpy, single) for k in range(len(sets))},)
+    return out
+
+
 def extract_all_features(img, device: int | None = None):
     """``vgg_16_UIE.extract_all_features(img)`` (vgg_16_UIE.py:435-466) for a uint8 RGB frame ``[H,W,3]`` (returns the
     reference's ``(79,)`` float32 vector) or a batch ``[B,H,W,3]`` (returns ``(B, 79)``).  Float inputs of the reference

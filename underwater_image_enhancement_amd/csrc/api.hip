@@ -1164,7 +1164,7 @@ int uwie_select_best_u8(uwie_ctx *ctx, const uint8_t *d_in, int batch, int H, in
         UWIE_TRY(launch_quality_scores(ctx, out, sb.f32, s, p->gray_shift, weights8 ? weights8 : kDefault,
                                        d_scores + (size_t)k * batch * 9, sb.qa, st));
     }
-    return launch_pick_best(d_scores, n, s, all, d_best, d_best_u8, st);
+    return launch_pick_best(d_scores, n, s, 9, 8, all, d_best, d_best_u8, st);
 }
 
 // The two enhancement modules (k_diffenh.hip): map is UWIE_LOSS_VGG (vgg_16_UIE.DifferentiableEnhancement) or
@@ -1766,6 +1766,51 @@ int uwie_quality_scores(uwie_ctx *ctx, const uint8_t *d_u8, const float *d_f32, 
     UWIE_CHECK_WS(quality_ws_bytes(s));
     return launch_quality_scores(ctx, d_u8, d_f32, s, gray_shift, weights8 ? weights8 : kDefault, d_scores, d_workspace,
                                  (hipStream_t)stream);
+}
+
+size_t uwie_workspace_bytes_underwater(int batch, int H, int W)
+{
+    if (!shape_ok(batch, H, W) || batch > 65535) return 0;
+    return underwater_ws_bytes(Shape{batch, H, W});
+}
+
+int uwie_underwater_plan(int H, int W, int *tile_w, int *tile_h)
+{
+    UWIE_REQUIRE(tile_w && tile_h, "underwater_plan: NULL pointer");
+    UWIE_CHECK_SHAPE(1, H, W);
+    underwater_tile(tile_w, tile_h);  // one tile for every frame
+    return UWIE_OK;
+}
+
+int uwie_underwater_scores_u8(uwie_ctx *ctx, const uint8_t *d_u8, int batch, int H, int W, int gray_shift, double *d_scores,
+                              void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE(ctx && d_u8 && d_scores, "underwater_scores: NULL pointer");
+    UWIE_SCOPE(ctx);
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_REQUIRE(batch <= 65535, "underwater_scores: batch must be <= 65535");
+    UWIE_REQUIRE(gray_shift == 14 || gray_shift == 15, "gray_shift must be 14 or 15");
+    const Shape s{batch, H, W};
+    UWIE_CHECK_WS(underwater_ws_bytes(s));
+    return launch_underwater_scores(ctx, d_u8, s, gray_shift, d_scores, d_workspace, (hipStream_t)stream);
+}
+
+int uwie_pick_best_u8(uwie_ctx *ctx, const double *d_scores, int n, int batch, int ncols, int col, const uint8_t *d_all_u8, int H,
+                      int W, int32_t *d_best, uint8_t *d_best_u8, void *stream)
+{
+    UWIE_REQUIRE(ctx && d_scores && d_best, "pick_best: NULL pointer");
+    UWIE_REQUIRE((d_all_u8 == nullptr) == (d_best_u8 == nullptr), "pick_best: d_all_u8 and d_best_u8 are given together");
+    UWIE_SCOPE(ctx);
+    UWIE_REQUIRE(n >= 1 && n <= 65535, "pick_best: 1 .. 65535 sets");
+    UWIE_REQUIRE(ncols >= 1 && col >= 0 && col < ncols, "pick_best: column out of range");
+    if (d_all_u8) {
+        UWIE_CHECK_SHAPE(batch, H, W);
+        UWIE_REQUIRE(batch <= 65535, "pick_best: batch must be <= 65535 to gather");
+    } else {
+        UWIE_REQUIRE(batch >= 1, "pick_best: batch must be >= 1");
+        H = W = 1;
+    }
+    return launch_pick_best(d_scores, n, Shape{batch, H, W}, ncols, col, d_all_u8, d_best, d_best_u8, (hipStream_t)stream);
 }
 
 int uwie_feature_extractor_count(int H, int W)

@@ -260,8 +260,15 @@ ClsModel classify_pack(const uwie_model_desc *d, void *host_blob, const void *de
 int launch_classify(const ClsModel &m, const double *d_rows, int B, int32_t *d_label, double *d_proba, uint32_t *d_status,
                     hipStream_t st);
 
-// best[b] = first argmax over the n strategies of scores[k][b][8]; d_out (optional) [B][H][W][3] = d_all[best[b]][b]
-int launch_pick_best(const double *d_scores, int n, Shape s, const uint8_t *d_all, int32_t *d_best, uint8_t *d_out, hipStream_t st);
+// best[b] = first argmax over the n sets of scores[k][b][col] (rows of ncols); d_out (optional) [B][H][W][3] = d_all[best[b]][b]
+int launch_pick_best(const double *d_scores, int n, Shape s, int ncols, int col, const uint8_t *d_all, int32_t *d_best, uint8_t *d_out,
+                     hipStream_t st);
+
+// k_uw_quality.hip: UCIQE / UIQM and their parts (include/uwie.h uwie_underwater_scores_u8), [B][kUwScores] float64
+constexpr int kUwScores = UWIE_UW_SCORES;
+size_t underwater_ws_bytes(Shape s);
+void underwater_tile(int *tile_w, int *tile_h);  // the tile of one block of the block pass (uwie_underwater_plan)
+int launch_underwater_scores(uwie_ctx *ctx, const uint8_t *d_u8, Shape s, int gray_shift, double *d_scores, void *ws, hipStream_t st);
 
 // k_guided.hip
 size_t guided_ws_bytes(Shape s);

@@ -357,6 +357,18 @@ __device__ __forceinline__ double wave_sum_f64(double v)
     for (int o = 32; o > 0; o >>= 1) v += __longlong_as_double((long long)shfl_xor_u64((uint64_t)__double_as_longlong(v), o));
     return v;
 }
+// sum((x - m)^2) / n of integers x with sum s1 and sum of squares s2, without the cancellation of s2 / n - (s1 / n)^2:
+// m = floor(s1 / n) is an integer, so the shifted sums stay exact integers and the correction (r / n)^2 is below 1.
+__device__ __forceinline__ double int_variance(long long s1, long long s2, long long n)
+{
+    long long m = s1 / n;
+    if (s1 - m * n < 0) --m;
+    const long long r = s1 - m * n;  // 0 <= r < n
+    const long long t = s2 - 2 * m * s1 + n * m * m;  // sum((x - m)^2) >= 0
+    const double rn = (double)r / (double)n;
+    return fmax((double)t / (double)n - rn * rn, 0.0);
+}
+
 // inclusive scan over a block of 256 threads; wsum: four words of LDS
 __device__ __forceinline__ uint32_t block_incl_scan_256(uint32_t v, uint32_t *wsum)
 {

@@ -129,18 +129,6 @@ __global__ void __launch_bounds__(256) k_qa_lap(const uint8_t *__restrict__ gray
 // np.clip(v, 0, 100): a NaN stays a NaN (fmin / fmax alone would turn it into 0)
 __device__ __forceinline__ double clip100(double v) { return v != v ? v : fmin(fmax(v, 0.0), 100.0); }
 
-// sum((x - m)^2) / n of integers x with sum s1 and sum of squares s2, without the cancellation of s2 / n - (s1 / n)^2:
-// m = floor(s1 / n) is an integer, so the shifted sums stay exact integers and the correction (r / n)^2 is below 1.
-__device__ __forceinline__ double int_variance(long long s1, long long s2, long long n)
-{
-    long long m = s1 / n;
-    if (s1 - m * n < 0) --m;
-    const long long r = s1 - m * n;  // 0 <= r < n
-    const long long t = s2 - 2 * m * s1 + n * m * m;  // sum((x - m)^2) >= 0
-    const double rn = (double)r / (double)n;
-    return fmax((double)t / (double)n - rn * rn, 0.0);
-}
-
 // grid B, block 64: the wave adds the blocks' colourfulness rows (lane l takes rows l, l + 64, ... in that order, then a
 // fixed butterfly), lane 0 evaluates the scores.  nblk == 0: the integer sums of a u8 frame are in isum instead.
 __global__ void __launch_bounds__(64) k_qa_finish(const uint32_t *__restrict__ hist, const double *__restrict__ cpart, int nblk,
@@ -237,15 +225,15 @@ QaBufs carve_qa(Carver &c, Shape s)
 }
 
 // main.py:145: best_strategy = max(strategy_scores, key=strategy_scores.get) -- the first maximum in the strategies' order.
-// scores: [n][B][9] (the weighted total is entry 8)
-__global__ void k_pick_best(const double *__restrict__ scores, int n, int B, int32_t *__restrict__ best)
+// scores: [n][B][ncols], compared on column col (uwie_select_best_u8: 9 columns, the weighted total is entry 8)
+__global__ void k_pick_best(const double *__restrict__ scores, int n, int B, int ncols, int col, int32_t *__restrict__ best)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     int k = 0;
-    double top = scores[(size_t)b * 9 + 8];
+    double top = scores[(size_t)b * ncols + col];
     for (int i = 1; i < n; ++i) {
-        const double v = scores[((size_t)i * B + b) * 9 + 8];
+        const double v = scores[((size_t)i * B + b) * ncols + col];
         if (v > top) { top = v; k = i; }
     }
     best[b] = k;
@@ -266,9 +254,10 @@ __global__ void __launch_bounds__(256) k_gather_best(const uint8_t *__restrict__
 
 }  // namespace
 
-int launch_pick_best(const double *d_scores, int n, Shape s, const uint8_t *d_all, int32_t *d_best, uint8_t *d_out, hipStream_t st)
+int launch_pick_best(const double *d_scores, int n, Shape s, int ncols, int col, const uint8_t *d_all, int32_t *d_best, uint8_t *d_out,
+                     hipStream_t st)
 {
-    UWIE_LAUNCH(k_pick_best, dim3(cdiv(s.B, 64)), dim3(64), 0, st, d_scores, n, s.B, d_best);
+    UWIE_LAUNCH(k_pick_best, dim3(cdiv(s.B, 64)), dim3(64), 0, st, d_scores, n, s.B, ncols, col, d_best);
     UWIE_LAUNCH_CHECK();
     if (d_out) {
         UWIE_LAUNCH(k_gather_best, dim3(grid_for(s.npx() * 3 / 16 + 1, 1024), s.B), dim3(256), 0, st, d_all, d_best, s.npx() * 3, s.B, d_out);

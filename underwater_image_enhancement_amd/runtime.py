@@ -687,6 +687,32 @@ class Device(_ClosedOnDel):
                                            _ptr(every), _ptr(ws), ws.numel(), self.stream()))
         return best, img, scores, every
 
+    def underwater_scores(self, frames_u8, gray_shift: int = 15):
+        """UCIQE / UIQM and their parts (uwie_underwater_scores_u8): frames uint8 cuda [B,H,W,3] -> float64 [B,8] in
+        include/uwie.h's order (sigma_c, con_l, mu_s, UCIQE, UICM, UISM, UIConM, UIQM)."""
+        B, H, W = self._bhw(frames_u8)
+        assert frames_u8.dtype == torch.uint8
+        ws = self._sized_workspace(self.lib.uwie_workspace_bytes_underwater(B, H, W), "underwater_scores: batch/H/W out of range")
+        out = self.empty((B, _lib.UW_SCORES), torch.float64)
+        check(self.lib.uwie_underwater_scores_u8(self._ctx, _ptr(frames_u8), B, H, W, int(gray_shift), _ptr(out), _ptr(ws),
+                                                 ws.numel(), self.stream()))
+        return out
+
+    def pick_best_u8(self, scores, col: int, every=None):
+        """uwie_pick_best_u8: scores float64 cuda [n,B,ncols] -> (first argmax over the sets of column ``col`` as int32 [B],
+        the winners' frames [B,H,W,3] gathered from ``every`` [n,B,H,W,3], or None without it)."""
+        assert scores.dtype == torch.float64 and scores.dim() == 3 and scores.is_contiguous()
+        n, B, ncols = (int(v) for v in scores.shape)
+        best = self.empty((B,), torch.int32)
+        img, H, W = None, 0, 0
+        if every is not None:
+            assert every.dtype == torch.uint8 and every.is_contiguous() and every.dim() == 5 and tuple(every.shape[:2]) == (n, B)
+            H, W = int(every.shape[2]), int(every.shape[3])
+            img = self.empty((B, H, W, 3), torch.uint8)
+        check(self.lib.uwie_pick_best_u8(self._ctx, _ptr(scores), n, B, ncols, int(col), _ptr(every), H, W, _ptr(best), _ptr(img),
+                                         self.stream()))
+        return best, img
+
     # ------------------------------------------------------------------ stages
     def cast_classify(self, frames):
         B, H, W = self._bhw(frames)
