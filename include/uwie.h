@@ -678,6 +678,57 @@ int uwie_underwater_scores_u8(uwie_ctx *ctx, const uint8_t *d_u8, int batch, int
 int uwie_pick_best_u8(uwie_ctx *ctx, const double *d_scores, int n, int batch, int ncols, int col, const uint8_t *d_all_u8, int H,
                       int W, int32_t *d_best, uint8_t *d_best_u8, void *stream);
 
+/*
+ * Full-reference quality of a result against its ground truth: mean absolute error, mean squared error, PSNR and SSIM (Wang et
+ * al. 2004; the definition of MATLAB's ssim.m and of scikit-image's structural_similarity(gaussian_weights=True,
+ * use_sample_covariance=False, data_range=255)).  An extension without a reference counterpart: this comment is the contract,
+ * tests/ref_quality_ref.py restates it in NumPy.
+ *
+ * Input: two u8 RGB frames of the same H x W, the result x and the reference y; n = H * W.  All arithmetic not marked integer
+ * is float64.
+ *   mae   = (integer sum of |x - y| over all 3 n bytes) / (3 n).
+ *   mse   = (integer sum of (x - y)^2 over all 3 n bytes) / (3 n).  Both sums are exact integers below 2^53: each column is one
+ *           correctly rounded division.
+ *   psnr  = 10 * log10(65025 / mse); +inf where mse = 0.
+ *   SSIM of a plane pair (px, py) of bytes:
+ *           window   11 x 11 Gaussian, sigma = 1.5, separable: the 1-D taps are w[k] = exp(-(k - 5)^2 / 4.5), k = 0 .. 10, divided
+ *                    by their float64 sum taken in index order.
+ *           C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2.
+ *           Windows lie wholly inside the frame ("valid"): the map has (H - 10) x (W - 10) points, point (i, j) covering rows
+ *           i .. i + 10 and columns j .. j + 10.  No border rule exists.
+ *           Five window sums per point, of x, y, x * x, y * y and x * y (the products are exact integers).  Order of summation:
+ *           along the row first, the 11 taps added in index order (r[j] = w[0] v[j] + w[1] v[j + 1] + ... from the left), then
+ *           down the column in index order.  (The device adds down the column in this order; along the row it first adds the
+ *           two values that share a tap, w[k] = w[10 - k], as exact integers; it uses fused multiply-adds.  See the tolerance.)
+ *           mu_x = sum w x, mu_y = sum w y; population form: var_x = sum w x^2 - mu_x^2, var_y likewise, cov = sum w x y - mu_x mu_y.
+ *           s = (2 mu_x mu_y + C1) (2 cov + C2) / ((mu_x^2 + mu_y^2 + C1) (var_x + var_y + C2)).
+ *           The plane's SSIM is the mean of s over the map.
+ *   ssim_y          SSIM of the gray bytes (uwie_rgb2gray_u8 with gray_shift) of the two frames.
+ *   ssim_r, _g, _b  SSIM of the channel bytes.
+ *   ssim_rgb        (ssim_r + ssim_g + ssim_b) / 3, added in that order.
+ *   With H < 11 or W < 11 there is no window and the five SSIM columns are NaN (uwie_pick_best_u8 never lets a NaN win).
+ * Two identical frames score mae = mse = 0, psnr = +inf and every SSIM exactly 1.0: the x and the y side are computed by the
+ * same operations in the same order, so numerator and denominator of every s are the same bits.  Part of the contract.
+ *
+ * d_scores: [batch][UWIE_REF_SCORES] float64 = mae, mse, psnr, ssim_y, ssim_r, ssim_g, ssim_b, ssim_rgb.
+ * Frame i of d_u8 [batch][H][W][3] is compared with frame i % ref_batch of d_ref_u8 [ref_batch][H][W][3]; 1 <= ref_batch <= batch
+ * and batch % ref_batch == 0, so the outputs of n strategies [n * B] share B references without copies.
+ * Exact: mae and mse (integer sums up to the division).  psnr is held to 1e-9 relative and every SSIM column to 1e-9 absolute
+ * against the float64 evaluation (tests/test_gpu_ref_quality.py): window sums of values <= 65025 carry a few 1e-11 of absolute
+ * error in any order of summation, both factors of the denominator are at least C1 and C2, and a mean does not amplify.
+ * Deterministic as uwie_underwater_scores_u8: integer partials per block, one float64 partial per tile and plane, added in
+ * their order; the grids depend on H and W only, so a frame's eight numbers are the same bits in every run and at every
+ * position of every batch.  Three launches (two without a window), no memset, no host read.  batch <= 65535.
+ * uwie_reference_plan: the tile of map points (*tile_w x *tile_h, anchored at the map's top left corner) that one workgroup of
+ * the SSIM pass produces from a (*tile_h + 10) x (*tile_w + 10) patch of both frames; the launcher runs on these numbers, so a
+ * test can aim at the seams.  Workspace: uwie_workspace_bytes_reference(batch, H, W) (at most 4 KB per frame plus 32 bytes per tile).
+ */
+#define UWIE_REF_SCORES 8
+size_t uwie_workspace_bytes_reference(int batch, int H, int W);
+int uwie_reference_plan(int H, int W, int *tile_w, int *tile_h);
+int uwie_reference_scores_u8(uwie_ctx *ctx, const uint8_t *d_u8, const uint8_t *d_ref_u8, int batch, int ref_batch, int H, int W,
+                             int gray_shift, double *d_scores, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------- strategy classifier: main.py:398-433 (predict) ---------------- */
 
 /*

@@ -107,6 +107,16 @@ def underwater_plan(H, W) -> tuple[int, int]:
     return tw.value, th.value
 
 
+REF_SCORES = 8  # include/uwie.h UWIE_REF_SCORES
+
+
+def reference_plan(H, W) -> tuple[int, int]:
+    """uwie_reference_plan: (tile_w, tile_h) in map points of one workgroup of the reference scores' SSIM pass.  Needs the library, not a device."""
+    tw, th = ctypes.c_int(), ctypes.c_int()
+    check(load().uwie_reference_plan(int(H), int(W), ctypes.byref(tw), ctypes.byref(th)))
+    return tw.value, th.value
+
+
 # name -> argument types (return type is int unless listed in _RESTYPES)
 _VP, _SZ, _I, _D = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_double
 _PP = ctypes.POINTER(UwieParams)
@@ -146,6 +156,9 @@ SIGNATURES = {
     "uwie_workspace_bytes_underwater": [_I, _I, _I],
     "uwie_underwater_plan": [_I, _I, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
     "uwie_underwater_scores_u8": [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _SZ, _VP],
+    "uwie_workspace_bytes_reference": [_I, _I, _I],
+    "uwie_reference_plan": [_I, _I, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
+    "uwie_reference_scores_u8": [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _SZ, _VP],
     "uwie_pick_best_u8": [_VP, _VP, _I, _I, _I, _I, _VP, _I, _I, _VP, _VP, _VP],
     "uwie_diff_enhance_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _SZ, _VP],
     "uwie_diff_enhance_save_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _SZ, _VP],
@@ -230,6 +243,7 @@ _RESTYPES = {
     "uwie_workspace_bytes_float": ctypes.c_size_t,
     "uwie_workspace_bytes_select": ctypes.c_size_t,
     "uwie_workspace_bytes_underwater": ctypes.c_size_t,
+    "uwie_workspace_bytes_reference": ctypes.c_size_t,
     "uwie_diff_enhance_bwd_workspace_bytes": ctypes.c_size_t,
     "uwie_workspace_bytes_diff_u8": ctypes.c_size_t,
     "uwie_diff_gated_bwd_workspace_bytes": ctypes.c_size_t,

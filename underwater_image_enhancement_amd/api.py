@@ -1355,6 +1355,95 @@ def select_best_underwater(frames, strategies=None, metric: str = "uiqm", device
     return out
 
 
+# include/uwie.h uwie_reference_scores_u8: the columns of a row of full-reference scores
+REFERENCE_SCORE_NAMES = ("mae", "mse", "psnr", "ssim_y", "ssim_r", "ssim_g", "ssim_b", "ssim_rgb")
+
+
+def _refs_for(refs, batch, dev: Device):
+    """The references of a batch [B,H,W,3] on the device: B of them, or one (a frame or a batch of 1) for all."""
+    r, _, _ = _as_batch_u8(refs, dev)
+    if tuple(r.shape[1:]) != tuple(batch.shape[1:]):
+        raise ValueError(f"references are {tuple(r.shape[1:])}, frames {tuple(batch.shape[1:])}")
+    if r.shape[0] not in (1, batch.shape[0]):
+        raise ValueError(f"{r.shape[0]} references for {batch.shape[0]} frames: give one per frame, or one for all")
+    return r
+
+
+def reference_scores(frames, refs, device: int | None = None):
+    """MAE, MSE, PSNR and SSIM (11 x 11 Gaussian window, valid windows; include/uwie.h states the definition) of results against
+    their references, on the device: uint8 ``[H,W,3]`` / ``[B,H,W,3]``, NumPy or a torch ROCm tensor; ``refs`` of the same
+    shape, or a single frame / a batch of 1 compared with every frame -> float64 ``(8,)`` / ``(B, 8)`` of the same kind as
+    ``frames``, columns in ``REFERENCE_SCORE_NAMES`` order.  Frames below 11 x 11 have no window: their SSIM columns are NaN."""
+    dev = get_device(device)
+    batch, was_numpy, single = _as_batch_u8(frames, dev)
+    return _finish(dev.reference_scores(batch, _refs_for(refs, batch, dev)), was_numpy, single, dev)
+
+
+class ReferenceQuality:
+    """PSNR / SSIM of one image against its reference: uint8 RGB frames, or float images in [0, 1] quantised with
+    ``(x * 255).astype(uint8)`` like ``UnderwaterQuality``."""
+
+    device: int | None = None
+
+    @staticmethod
+    def _u8(img):
+        x = np.asarray(img.cpu() if hasattr(img, "data_ptr") else img)
+        if x.ndim != 3 or x.shape[2] != 3:
+            raise ValueError(f"expected an HxWx3 image, got {x.shape}")
+        return np.ascontiguousarray(x if x.dtype == np.uint8 else (x * 255).astype(np.uint8))
+
+    @classmethod
+    def scores(cls, img, ref) -> dict:
+        """``{name: value}`` for every entry of ``REFERENCE_SCORE_NAMES``."""
+        row = reference_scores(cls._u8(img), cls._u8(ref), device=cls.device)
+        return {k: float(row[i]) for i, k in enumerate(REFERENCE_SCORE_NAMES)}
+
+    @classmethod
+    def psnr(cls, img, ref) -> float:
+        return cls.scores(img, ref)["psnr"]
+
+    @classmethod
+    def ssim(cls, img, ref, channels: str = "y") -> float:
+        """SSIM of the gray planes (``"y"``) or the mean of the three channels' (``"rgb"``)."""
+        if channels not in ("y", "rgb"):
+            raise ValueError(f"channels must be 'y' or 'rgb', got {channels!r}")
+        return cls.scores(img, ref)["ssim_" + channels]
+
+
+def select_best_reference(frames, refs, strategies=None, metric: str = "ssim_y", device: int | None = None, return_all: bool = False):
+    """``select_best_underwater``'s labelling loop with the winner picked by closeness to a ground truth: every entry of
+    ``strategies`` (default ``Config.STRATEGIES``; a dict, or a list of ``(key, params)`` pairs) is applied to the frames, the
+    n * B results are scored against the B references in one uwie_reference_scores_u8 call (``ref_batch = B``: no copies of
+    the references), and per frame the first maximum of ``metric`` (``"psnr"``, ``"ssim_y"`` or ``"ssim_rgb"``, the columns
+    where larger is better) in the strategies' order wins (uwie_pick_best_u8).  ``refs``: one reference per frame, or one for all.
+
+    Returns ``(best_names, best_images, scores)`` like ``select_best_underwater``, ``scores`` shaped ``(n, B, 8)`` in
+    ``REFERENCE_SCORE_NAMES`` order; with ``return_all`` a fourth value ``{name: uint8 batch}`` holds every strategy's output."""
+    if metric not in ("psnr", "ssim_y", "ssim_rgb"):
+        raise ValueError(f"metric must be 'psnr', 'ssim_y' or 'ssim_rgb', got {metric!r}")
+    strategies = CONFIG_STRATEGIES if strategies is None else strategies
+    sets = list(strategies.items()) if isinstance(strategies, dict) else [(k, dict(v)) for k, v in strategies]
+    dev = get_device(device)
+    batch, was_numpy, single = _as_batch_u8(frames, dev)
+    r = _refs_for(refs, batch, dev)
+    for k, _ in sets:
+        if k not in _lib.DICT_STRATEGIES:
+            raise ValueError(f"未知策略: {k}")
+    plist = [_dict_params(dev, k, v) for k, v in sets]
+    names = [v.get("name", k) for k, v in sets]
+    _, _, _, every = dev.select_best_u8(batch, plist, None, want_all=True)
+    n, B, H, W = (int(v) for v in every.shape[:4])
+    scores = dev.reference_scores(every.view(n * B, H, W, 3), r, gray_shift=plist[0].gray_shift).view(n, B, len(REFERENCE_SCORE_NAMES))
+    best, img = dev.pick_best_u8(scores, REFERENCE_SCORE_NAMES.index(metric), every)
+    best_h = best.cpu().tolist()
+    dev.check_status()
+    best_names = [names[i] for i in best_h]
+    out = (best_names[0] if single else best_names, _finish(img, was_numpy, single), scores.cpu().numpy() if was_numpy else scores)
+    if return_all:
+        out = out + ({names[k]: _finish(every[k], was_numpy, single) for k in range(len(sets))},)
+    return out
+
+
 def extract_all_features(img, device: int | None = None):
     """``vgg_16_UIE.extract_all_features(img)`` (vgg_16_UIE.py:435-466) for a uint8 RGB frame ``[H,W,3]`` (returns the
     reference's ``(79,)`` float32 vector) or a batch ``[B,H,W,3]`` (returns ``(B, 79)``).  Float inputs of the reference

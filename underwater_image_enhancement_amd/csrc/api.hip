@@ -1795,6 +1795,34 @@ int uwie_underwater_scores_u8(uwie_ctx *ctx, const uint8_t *d_u8, int batch, int
     return launch_underwater_scores(ctx, d_u8, s, gray_shift, d_scores, d_workspace, (hipStream_t)stream);
 }
 
+size_t uwie_workspace_bytes_reference(int batch, int H, int W)
+{
+    if (!shape_ok(batch, H, W) || batch > 65535) return 0;
+    return reference_ws_bytes(Shape{batch, H, W});
+}
+
+int uwie_reference_plan(int H, int W, int *tile_w, int *tile_h)
+{
+    UWIE_REQUIRE(tile_w && tile_h, "reference_plan: NULL pointer");
+    UWIE_CHECK_SHAPE(1, H, W);
+    reference_tile(tile_w, tile_h);  // one tile for every frame
+    return UWIE_OK;
+}
+
+int uwie_reference_scores_u8(uwie_ctx *ctx, const uint8_t *d_u8, const uint8_t *d_ref_u8, int batch, int ref_batch, int H, int W,
+                             int gray_shift, double *d_scores, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    UWIE_REQUIRE(ctx && d_u8 && d_ref_u8 && d_scores, "reference_scores: NULL pointer");
+    UWIE_SCOPE(ctx);
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_REQUIRE(batch <= 65535, "reference_scores: batch must be <= 65535");
+    UWIE_REQUIRE(ref_batch >= 1 && ref_batch <= batch && batch % ref_batch == 0, "reference_scores: ref_batch must divide batch");
+    UWIE_REQUIRE(gray_shift == 14 || gray_shift == 15, "gray_shift must be 14 or 15");
+    const Shape s{batch, H, W};
+    UWIE_CHECK_WS(reference_ws_bytes(s));
+    return launch_reference_scores(d_u8, d_ref_u8, s, ref_batch, gray_shift, d_scores, d_workspace, (hipStream_t)stream);
+}
+
 int uwie_pick_best_u8(uwie_ctx *ctx, const double *d_scores, int n, int batch, int ncols, int col, const uint8_t *d_all_u8, int H,
                       int W, int32_t *d_best, uint8_t *d_best_u8, void *stream)
 {

@@ -270,6 +270,14 @@ size_t underwater_ws_bytes(Shape s);
 void underwater_tile(int *tile_w, int *tile_h);  // the tile of one block of the block pass (uwie_underwater_plan)
 int launch_underwater_scores(uwie_ctx *ctx, const uint8_t *d_u8, Shape s, int gray_shift, double *d_scores, void *ws, hipStream_t st);
 
+// k_ref_quality.hip: MAE, MSE, PSNR and SSIM against a reference (include/uwie.h uwie_reference_scores_u8), [B][kRefScores]
+// float64; frame i is compared with reference i % ref_batch
+constexpr int kRefScores = UWIE_REF_SCORES;
+size_t reference_ws_bytes(Shape s);
+void reference_tile(int *tile_w, int *tile_h);  // the map points of one workgroup of the SSIM pass (uwie_reference_plan)
+int launch_reference_scores(const uint8_t *d_u8, const uint8_t *d_ref_u8, Shape s, int ref_batch, int gray_shift, double *d_scores,
+                            void *ws, hipStream_t st);
+
 // k_guided.hip
 size_t guided_ws_bytes(Shape s);
 size_t box_ws_bytes(Shape s);

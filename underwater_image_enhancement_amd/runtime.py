@@ -698,6 +698,23 @@ class Device(_ClosedOnDel):
                                                  ws.numel(), self.stream()))
         return out
 
+    def reference_scores(self, frames_u8, refs_u8, gray_shift: int = 15):
+        """MAE, MSE, PSNR and SSIM against a reference (uwie_reference_scores_u8): frames uint8 cuda [B,H,W,3], refs uint8 cuda
+        [R,H,W,3] with R dividing B (frame i is compared with reference i % R) -> float64 [B,8] in include/uwie.h's order
+        (mae, mse, psnr, ssim_y, ssim_r, ssim_g, ssim_b, ssim_rgb)."""
+        B, H, W = self._bhw(frames_u8)
+        R = int(refs_u8.shape[0])
+        assert frames_u8.dtype == torch.uint8 and refs_u8.dtype == torch.uint8 and refs_u8.is_contiguous()
+        if tuple(refs_u8.shape[1:]) != (H, W, 3):
+            raise ValueError(f"reference_scores: references are {tuple(refs_u8.shape[1:])}, frames {(H, W, 3)}")
+        if R < 1 or B % R:
+            raise ValueError(f"reference_scores: {R} references do not divide {B} frames")
+        ws = self._sized_workspace(self.lib.uwie_workspace_bytes_reference(B, H, W), "reference_scores: batch/H/W out of range")
+        out = self.empty((B, _lib.REF_SCORES), torch.float64)
+        check(self.lib.uwie_reference_scores_u8(self._ctx, _ptr(frames_u8), _ptr(refs_u8), B, R, H, W, int(gray_shift), _ptr(out),
+                                                _ptr(ws), ws.numel(), self.stream()))
+        return out
+
     def pick_best_u8(self, scores, col: int, every=None):
         """uwie_pick_best_u8: scores float64 cuda [n,B,ncols] -> (first argmax over the sets of column ``col`` as int32 [B],
         the winners' frames [B,H,W,3] gathered from ``every`` [n,B,H,W,3], or None without it)."""
