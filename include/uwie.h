@@ -729,6 +729,55 @@ int uwie_reference_plan(int H, int W, int *tile_w, int *tile_h);
 int uwie_reference_scores_u8(uwie_ctx *ctx, const uint8_t *d_u8, const uint8_t *d_ref_u8, int batch, int ref_batch, int H, int W,
                              int gray_shift, double *d_scores, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Gray-world white balance with red-channel compensation, the pre-pass of the underwater literature: Ancuti et al. 2018, "Color
+ * Balance and Fusion for Underwater Image Enhancement", eq. 4-5, followed by gray-world (Buchsbaum), in byte units.  An
+ * extension without a reference counterpart (the reference's white_balance is a percentile stretch, its cast handling a fixed
+ * x 0.85; both stay what they are): this comment is the contract, tests/gray_world_ref.py restates it in NumPy.
+ *
+ * Input: a u8 RGB frame, H x W, n = H * W pixels with bytes (r, g, b).  Parameters red, blue, max_gain: 0 <= red, blue <= 1 (the
+ * papers' alpha), max_gain = 0 (no bound) or >= 1.  Anything marked integer is exact integer arithmetic.  Everything else is
+ * float64, each operation rounded once, no fused multiply-add.  Integers are converted exactly; all of them are below 2^53.
+ *
+ *   S_r = sum r   S_g = sum g   S_b = sum b   S_rg = sum r * g   S_bg = sum b * g          (integer, over the n pixels)
+ *   N = n         mean_r = S_r / N   mean_g = S_g / N   mean_b = S_b / N
+ *   k_r = (red  * max(mean_g - mean_r, 0)) / 65025        k_b = (blue * max(mean_g - mean_b, 0)) / 65025
+ *      compensated value of a pixel, real-valued:  r' = r + k_r * (255 - r) * g,  g' = g,  b' = b + k_b * (255 - b) * g
+ *      (I_rc = I_r + alpha (mean(I_g) - mean(I_r)) (1 - I_r) I_g with I = byte / 255; compensation never darkens: the max)
+ *   m_r = (S_r + k_r * (255 * S_g - S_rg)) / N      m_g = mean_g      m_b = (S_b + k_b * (255 * S_g - S_bg)) / N
+ *      (255 * S_g - S_rg is one exact integer; m_c is the mean of the compensated channel, in closed form)
+ *   gray = ((m_r + m_g) + m_b) / 3
+ *   s_c  = gray / m_c  if m_c > 0,  else 1 ;   if max_gain > 0:  s_c = min(s_c, max_gain)
+ *   c_r  = s_r * k_r        c_b = s_b * k_b
+ *   w_r  = s_r * r + c_r * ((255 - r) * g)          (integer product, two multiplications, one addition)
+ *   w_g  = s_g * g
+ *   w_b  = s_b * b + c_b * ((255 - b) * g)
+ *   out_c = rint(min(w_c, 255))                     (round half to even; w_c >= 0 always, NaN cannot arise)
+ *
+ * Fixed by this: a frame of one gray level, and a black frame, come back unchanged with gains exactly 1; with red = blue = 0 the
+ * stage is plain gray-world; with alpha <= 1 a compensated value never exceeds 255 before the gain.
+ *
+ * d_stats: [batch][UWIE_GW_STATS] float64 = mean_r, mean_g, mean_b, k_r, k_b, m_r, m_g, m_b, gray, s_r, s_g, s_b.  Each frame of a
+ * batch has its own sums and gains.  d_out [batch][H][W][3] and d_stats are each optional, not both NULL; with d_out == NULL
+ * only the sum pass and the coefficients run.  d_out == d_in (exactly; a partial overlap is an error) is allowed.  d_in and d_out
+ * are 4-byte aligned, d_stats 8-byte; a frame inside a batch starts wherever 3 * H * W puts it.  batch <= 65535.
+ * Out-of-range or non-finite parameters are UWIE_E_INVALID with a message naming the field, a short or NULL workspace
+ * UWIE_E_WORKSPACE; every check runs before the context is touched.
+ * Exact: every byte and every stat equals the float64 evaluation above bit for bit (tests/test_gpu_gray_world.py): the sums are
+ * integers, so no order of summation enters.  At most three launches (two without d_out), no atomics, no memset, no host read;
+ * the grids depend on H and W only, so a frame's results are the same bits in every run and at every position of every batch.
+ * uwie_gray_world_plan: *block_px = the pixels one workgroup of the sum pass adds into 32-bit integers (65025 * *block_px < 2^32),
+ * *thread_px = the pixels one thread of the apply pass takes per step; a frame's last n % *thread_px pixels go byte by byte.  The
+ * launchers run on these numbers, so a test can aim at the seams.
+ * Workspace: uwie_workspace_bytes_gray_world(batch, H, W) (per frame 32 bytes per started *block_px pixels and 96 bytes of stats, each of the two
+ * arrays rounded up to 256 bytes).
+ */
+#define UWIE_GW_STATS 12
+size_t uwie_workspace_bytes_gray_world(int batch, int H, int W);
+int uwie_gray_world_plan(int H, int W, int *block_px, int *thread_px);
+int uwie_gray_world_u8(uwie_ctx *ctx, const uint8_t *d_in, int batch, int H, int W, double red, double blue, double max_gain,
+                       uint8_t *d_out, double *d_stats, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------- strategy classifier: main.py:398-433 (predict) ---------------- */
 
 /*

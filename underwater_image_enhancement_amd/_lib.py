@@ -117,6 +117,17 @@ def reference_plan(H, W) -> tuple[int, int]:
     return tw.value, th.value
 
 
+GW_STATS = 12  # include/uwie.h UWIE_GW_STATS
+
+
+def gray_world_plan(H, W) -> tuple[int, int]:
+    """uwie_gray_world_plan: (block_px, thread_px), the pixels per workgroup of the sum pass and per thread of the apply pass.
+    Needs the library, not a device."""
+    bp, tp = ctypes.c_int(), ctypes.c_int()
+    check(load().uwie_gray_world_plan(int(H), int(W), ctypes.byref(bp), ctypes.byref(tp)))
+    return bp.value, tp.value
+
+
 # name -> argument types (return type is int unless listed in _RESTYPES)
 _VP, _SZ, _I, _D = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_double
 _PP = ctypes.POINTER(UwieParams)
@@ -159,6 +170,9 @@ SIGNATURES = {
     "uwie_workspace_bytes_reference": [_I, _I, _I],
     "uwie_reference_plan": [_I, _I, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
     "uwie_reference_scores_u8": [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _SZ, _VP],
+    "uwie_workspace_bytes_gray_world": [_I, _I, _I],
+    "uwie_gray_world_plan": [_I, _I, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
+    "uwie_gray_world_u8": [_VP, _VP, _I, _I, _I, _D, _D, _D, _VP, _VP, _VP, _SZ, _VP],
     "uwie_pick_best_u8": [_VP, _VP, _I, _I, _I, _I, _VP, _I, _I, _VP, _VP, _VP],
     "uwie_diff_enhance_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _SZ, _VP],
     "uwie_diff_enhance_save_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _SZ, _VP],
@@ -244,6 +258,7 @@ _RESTYPES = {
     "uwie_workspace_bytes_select": ctypes.c_size_t,
     "uwie_workspace_bytes_underwater": ctypes.c_size_t,
     "uwie_workspace_bytes_reference": ctypes.c_size_t,
+    "uwie_workspace_bytes_gray_world": ctypes.c_size_t,
     "uwie_diff_enhance_bwd_workspace_bytes": ctypes.c_size_t,
     "uwie_workspace_bytes_diff_u8": ctypes.c_size_t,
     "uwie_diff_gated_bwd_workspace_bytes": ctypes.c_size_t,

@@ -65,6 +65,44 @@ def _as_batch_u8(frames, dev: Device):
     return t.to(dev.torch_device).contiguous(), was_numpy, single
 
 
+# include/uwie.h uwie_gray_world_u8: the columns of a row of its stats
+GRAY_WORLD_STAT_NAMES = ("mean_r", "mean_g", "mean_b", "k_r", "k_b", "m_r", "m_g", "m_b", "gray", "s_r", "s_g", "s_b")
+_GRAY_WORLD_KEYS = ("red", "blue", "max_gain")
+
+
+def _gray_world_args(gray_world):
+    """The ``gray_world=`` keyword of the enhance / select entry points -> None (no pre-pass) or the keyword arguments of
+    ``gray_world()``: ``True`` means the defaults, a dict gives ``red`` / ``blue`` / ``max_gain``."""
+    if gray_world is None or gray_world is False:
+        return None
+    if gray_world is True:
+        return {}
+    if isinstance(gray_world, dict):
+        unknown = sorted(set(gray_world) - set(_GRAY_WORLD_KEYS))
+        if unknown:
+            raise KeyError(f"gray_world: unknown key(s) {unknown}; it takes {list(_GRAY_WORLD_KEYS)}")
+        return {k: float(v) for k, v in gray_world.items()}
+    raise TypeError(f"gray_world must be None, True or a dict of red / blue / max_gain, got {type(gray_world).__name__}")
+
+
+def _gray_world_needs_u8(frames):
+    dtype = getattr(frames, "dtype", None)
+    if dtype is not None and dtype not in (np.uint8, torch.uint8):
+        raise UnsupportedInputError(f"gray_world takes uint8 frames, got {dtype}")
+
+
+def _as_balanced_batch_u8(frames, dev: Device, gray_world=None):
+    """``_as_batch_u8`` with the gray-world pre-pass composed in front: ``f(x, gray_world=g) == f(gray_world(x, **g))`` bit for
+    bit, for every caller.  ``gray_world=None`` is ``_as_batch_u8`` itself: no launch, no buffer."""
+    g = _gray_world_args(gray_world)
+    if g is not None:
+        _gray_world_needs_u8(frames)
+    batch, was_numpy, single = _as_batch_u8(frames, dev)
+    if g is not None:
+        batch, _ = dev.gray_world(batch, **g)  # a new tensor: the caller's frames stay as they are
+    return batch, was_numpy, single
+
+
 def _finish(t, was_numpy, single, dev: Device | None = None):
     if single:
         t = t[0]
@@ -76,18 +114,38 @@ def _finish(t, was_numpy, single, dev: Device | None = None):
     return out
 
 
+def gray_world(frames, red: float = 1.0, blue: float = 0.0, max_gain: float = 0.0, device: int | None = None,
+               return_stats: bool = False):
+    """Gray-world white balance with red-channel compensation (Ancuti et al. 2018 eq. 4-5, then Buchsbaum's gray world) in the
+    fixed form include/uwie.h states (uwie_gray_world_u8; an extension without a reference counterpart), on the device: uint8
+    ``[H,W,3]`` / ``[B,H,W,3]``, NumPy or a torch ROCm tensor -> the balanced frames, of the same kind.  ``red`` / ``blue``: how
+    much of the green mean's lead the red / blue channel is given before the balance (the papers' alpha, 0 .. 1; 0 / 0 is plain
+    gray-world); ``max_gain``: upper bound of the three channel gains (0: none, else >= 1).  Every frame of a batch has its own
+    gains.  With ``return_stats`` the result is ``(out, stats)``, stats float64 ``(12,)`` / ``(B, 12)`` in
+    ``GRAY_WORLD_STAT_NAMES`` order."""
+    _gray_world_needs_u8(frames)
+    dev = get_device(device)
+    batch, was_numpy, single = _as_batch_u8(frames, dev)
+    out, stats = dev.gray_world(batch, red=red, blue=blue, max_gain=max_gain, want_stats=return_stats)
+    if not return_stats:
+        return _finish(out, was_numpy, single, dev)
+    return _finish(out, was_numpy, single, dev), _finish(stats, was_numpy, single)
+
+
 def enhance(frames, strategy: int = 2, cast_correct: bool = True, device: int | None = None, return_float: bool = False,
-            **overrides):
+            gray_world=None, **overrides):
     """Canonical ``enhance(u8 RGB) -> u8 RGB`` (six_stadigy.py:406-431) for one frame or a batch.
 
     ``frames``: uint8 ``[H,W,3]`` / ``[B,H,W,3]``, NumPy (copied to HBM and back) or a torch ROCm tensor (stays on
     the device).  ``strategy`` selects ``strategy1..6`` (default 2, medium dehazing).  ``overrides`` set
     ``uwie_params`` fields (e.g. ``omega=0.6, gf_ksize=20``; ``dark_patch=15`` takes the dark channel over a 15 x 15 patch,
-    an extension without a reference counterpart: include/uwie.h).
+    an extension without a reference counterpart: include/uwie.h).  ``gray_world`` (``True`` or a dict of ``red`` / ``blue`` /
+    ``max_gain``; default ``None``: nothing changes) balances the frames first: ``enhance(x, gray_world=g, ...)`` is
+    ``enhance(gray_world(x, **g), ...)``, so cast detection sees the balanced frame.
     """
     dev = get_device(device)
     _patch_needs_u8(frames, overrides.get("dark_patch", 1))
-    batch, was_numpy, single = _as_batch_u8(frames, dev)
+    batch, was_numpy, single = _as_balanced_batch_u8(frames, dev, gray_world)
     p = dev.params(_lib.SURFACE_SIX, int(strategy), cast_correct=int(bool(cast_correct)), **overrides)
     out, outf = dev.enhance_u8(batch, p, want_float=return_float)
     return _finish(outf if return_float else out, was_numpy, single, dev)
@@ -102,16 +160,16 @@ DRIVER_STRATEGIES = (
 CAST_NAMES = ("normal", "greenish", "bluish")
 
 
-def enhance_all(frames, cast_correct: bool = True, device: int | None = None, dark_patch: int = 1):
+def enhance_all(frames, cast_correct: bool = True, device: int | None = None, dark_patch: int = 1, gray_world=None):
     """All six strategies of every frame in one call: one cast detection and one atmospheric-light quadtree per frame
     (strategies 1-3 share it), like the inner loop of ``process_all_images_all_strategies`` (six_stadigy.py:398-431).
 
     Returns ``(outputs, image_types)``: ``outputs[name]`` is the uint8 batch of that strategy (keys in the driver's
     order, see ``DRIVER_STRATEGIES``), ``image_types`` the list of ``"normal" / "greenish" / "bluish"`` per frame.
-    ``dark_patch`` (default 1, the reference) applies to the dehazing strategies 1-3.
+    ``dark_patch`` (default 1, the reference) applies to the dehazing strategies 1-3.  ``gray_world``: as for ``enhance``.
     """
     dev = get_device(device)
-    batch, was_numpy, single = _as_batch_u8(frames, dev)
+    batch, was_numpy, single = _as_balanced_batch_u8(frames, dev, gray_world)
     out, kind = dev.enhance_all_u8(batch, cast_correct, dark_patch=dark_patch)
     types = [CAST_NAMES[int(k)] for k in kind.cpu().tolist()]
     outs = {name: _finish(out[i], was_numpy, single, dev) for i, (name, _) in enumerate(DRIVER_STRATEGIES)}
@@ -1243,7 +1301,7 @@ def _dict_params(dev, name, params):
 
 
 def select_best(frames, strategies=None, weights=None, device: int | None = None, return_all: bool = False,
-                dark_patch: int | None = None):
+                dark_patch: int | None = None, gray_world=None):
     """The labelling loop of ``SelfSupervisedSystem.build_dataset`` (main.py:118-146) for one frame or a batch, in ONE device
     call: every entry of ``strategies`` (default ``Config.STRATEGIES``, config.py:28-75: ``{key: {'name': ..., params}}``) goes
     through ``apply_strategy``, ``comprehensive_assessment`` with ``weights`` (default ``Config.QUALITY_WEIGHTS``) scores each
@@ -1257,6 +1315,7 @@ def select_best(frames, strategies=None, weights=None, device: int | None = None
     ``try`` blocks give a failing strategy the score 0.0 like main.py:139-142.
 
     ``dark_patch`` (optional): uwie_params.dark_patch of every dehazing entry whose own dict has no ``'dark_patch'`` key.
+    ``gray_world`` (``True`` or a dict of ``red`` / ``blue`` / ``max_gain``): every strategy starts from ``gray_world(frames)``.
     """
     strategies = CONFIG_STRATEGIES if strategies is None else strategies
     if dark_patch is not None:
@@ -1264,7 +1323,7 @@ def select_best(frames, strategies=None, weights=None, device: int | None = None
                       for k, v in strategies.items()}
     weights = CONFIG_QUALITY_WEIGHTS if weights is None else weights
     dev = get_device(device)
-    batch, was_numpy, single = _as_batch_u8(frames, dev)
+    batch, was_numpy, single = _as_balanced_batch_u8(frames, dev, gray_world)
     keys = list(strategies)
     for k in keys:
         if k not in _lib.DICT_STRATEGIES:
@@ -1322,7 +1381,8 @@ class UnderwaterQuality:
         return cls.scores(img)["uiqm"]
 
 
-def select_best_underwater(frames, strategies=None, metric: str = "uiqm", device: int | None = None, return_all: bool = False):
+def select_best_underwater(frames, strategies=None, metric: str = "uiqm", device: int | None = None, return_all: bool = False,
+                           gray_world=None):
     """``select_best``'s labelling loop with the winner picked by an underwater metric instead of the weighted total: every
     entry of ``strategies`` (default ``Config.STRATEGIES``; a dict like ``select_best``'s, or a list of ``(key, params)`` pairs,
     which can name a key more than once) is applied to the frames (uwie_select_best_u8 with its outputs kept), the n * B results are scored in one uwie_underwater_scores_u8 call, and per frame the first maximum of ``metric``
@@ -1330,13 +1390,14 @@ def select_best_underwater(frames, strategies=None, metric: str = "uiqm", device
 
     Returns ``(best_names, best_images, scores)``: the winner's ``'name'`` per frame (a string for a single frame), its uint8
     image, and ``scores`` shaped ``(n, B, 8)`` (B = 1 for a single frame) in ``UNDERWATER_SCORE_NAMES`` order, the sets in
-    ``strategies``' order; with ``return_all`` a fourth value ``{name: uint8 batch}`` holds every strategy's output."""
+    ``strategies``' order; with ``return_all`` a fourth value ``{name: uint8 batch}`` holds every strategy's output.
+    ``gray_world``: as for ``select_best``."""
     if metric not in ("uiqm", "uciqe"):
         raise ValueError(f"metric must be 'uiqm' or 'uciqe', got {metric!r}")
     strategies = CONFIG_STRATEGIES if strategies is None else strategies
     sets = list(strategies.items()) if isinstance(strategies, dict) else [(k, dict(v)) for k, v in strategies]
     dev = get_device(device)
-    batch, was_numpy, single = _as_batch_u8(frames, dev)
+    batch, was_numpy, single = _as_balanced_batch_u8(frames, dev, gray_world)
     for k, _ in sets:
         if k not in _lib.DICT_STRATEGIES:
             raise ValueError(f"未知策略: {k}")
@@ -1410,7 +1471,8 @@ class ReferenceQuality:
         return cls.scores(img, ref)["ssim_" + channels]
 
 
-def select_best_reference(frames, refs, strategies=None, metric: str = "ssim_y", device: int | None = None, return_all: bool = False):
+def select_best_reference(frames, refs, strategies=None, metric: str = "ssim_y", device: int | None = None, return_all: bool = False,
+                          gray_world=None):
     """``select_best_underwater``'s labelling loop with the winner picked by closeness to a ground truth: every entry of
     ``strategies`` (default ``Config.STRATEGIES``; a dict, or a list of ``(key, params)`` pairs) is applied to the frames, the
     n * B results are scored against the B references in one uwie_reference_scores_u8 call (``ref_batch = B``: no copies of
@@ -1418,13 +1480,14 @@ def select_best_reference(frames, refs, strategies=None, metric: str = "ssim_y",
     where larger is better) in the strategies' order wins (uwie_pick_best_u8).  ``refs``: one reference per frame, or one for all.
 
     Returns ``(best_names, best_images, scores)`` like ``select_best_underwater``, ``scores`` shaped ``(n, B, 8)`` in
-    ``REFERENCE_SCORE_NAMES`` order; with ``return_all`` a fourth value ``{name: uint8 batch}`` holds every strategy's output."""
+    ``REFERENCE_SCORE_NAMES`` order; with ``return_all`` a fourth value ``{name: uint8 batch}`` holds every strategy's output.
+    ``gray_world``: as for ``select_best`` (the frames are balanced, the references are not)."""
     if metric not in ("psnr", "ssim_y", "ssim_rgb"):
         raise ValueError(f"metric must be 'psnr', 'ssim_y' or 'ssim_rgb', got {metric!r}")
     strategies = CONFIG_STRATEGIES if strategies is None else strategies
     sets = list(strategies.items()) if isinstance(strategies, dict) else [(k, dict(v)) for k, v in strategies]
     dev = get_device(device)
-    batch, was_numpy, single = _as_batch_u8(frames, dev)
+    batch, was_numpy, single = _as_balanced_batch_u8(frames, dev, gray_world)
     r = _refs_for(refs, batch, dev)
     for k, _ in sets:
         if k not in _lib.DICT_STRATEGIES:

@@ -1,6 +1,7 @@
 // C ABI of libuwie.so (include/uwie.h): context, parameter defaults, workspace sizing, the per-stage entry points
 // and the strategy pipelines.  Everything here only enqueues kernels on the caller's stream.
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -1821,6 +1822,42 @@ int uwie_reference_scores_u8(uwie_ctx *ctx, const uint8_t *d_u8, const uint8_t *
     const Shape s{batch, H, W};
     UWIE_CHECK_WS(reference_ws_bytes(s));
     return launch_reference_scores(d_u8, d_ref_u8, s, ref_batch, gray_shift, d_scores, d_workspace, (hipStream_t)stream);
+}
+
+size_t uwie_workspace_bytes_gray_world(int batch, int H, int W)
+{
+    if (!shape_ok(batch, H, W) || batch > 65535) return 0;
+    return gray_world_ws_bytes(Shape{batch, H, W});
+}
+
+int uwie_gray_world_plan(int H, int W, int *block_px, int *thread_px)
+{
+    UWIE_REQUIRE(block_px && thread_px, "gray_world_plan: NULL pointer");
+    UWIE_CHECK_SHAPE(1, H, W);
+    gray_world_plan(block_px, thread_px);  // one pair for every frame
+    return UWIE_OK;
+}
+
+int uwie_gray_world_u8(uwie_ctx *ctx, const uint8_t *d_in, int batch, int H, int W, double red, double blue, double max_gain,
+                       uint8_t *d_out, double *d_stats, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    // every check comes before the context is touched
+    UWIE_REQUIRE(ctx && d_in, "gray_world: NULL context or d_in");
+    UWIE_REQUIRE(d_out || d_stats, "gray_world: d_out and d_stats are both NULL");
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_REQUIRE(batch <= 65535, "gray_world: batch must be <= 65535");
+    UWIE_REQUIRE(red >= 0.0 && red <= 1.0, "gray_world: red must be in [0, 1]");  // (false for NaN)
+    UWIE_REQUIRE(blue >= 0.0 && blue <= 1.0, "gray_world: blue must be in [0, 1]");
+    UWIE_REQUIRE(max_gain == 0.0 || (max_gain >= 1.0 && max_gain < HUGE_VAL), "gray_world: max_gain must be 0 (no bound) or finite and >= 1");
+    UWIE_REQUIRE(((uintptr_t)d_in & 3) == 0 && ((uintptr_t)d_out & 3) == 0 && ((uintptr_t)d_stats & 7) == 0,
+                 "gray_world: d_in and d_out must be 4-byte aligned, d_stats 8-byte aligned");
+    const Shape s{batch, H, W};
+    const size_t bytes = (size_t)batch * s.npx() * 3;
+    UWIE_REQUIRE(!d_out || d_out == d_in || d_out + bytes <= d_in || d_in + bytes <= d_out,
+                 "gray_world: d_out overlaps d_in partially (d_out == d_in is allowed)");
+    UWIE_CHECK_WS(gray_world_ws_bytes(s));
+    UWIE_SCOPE(ctx);
+    return launch_gray_world(d_in, s, red, blue, max_gain, d_out, d_stats, d_workspace, (hipStream_t)stream);
 }
 
 int uwie_pick_best_u8(uwie_ctx *ctx, const double *d_scores, int n, int batch, int ncols, int col, const uint8_t *d_all_u8, int H,

@@ -278,6 +278,13 @@ void reference_tile(int *tile_w, int *tile_h);  // the map points of one workgro
 int launch_reference_scores(const uint8_t *d_u8, const uint8_t *d_ref_u8, Shape s, int ref_batch, int gray_shift, double *d_scores,
                             void *ws, hipStream_t st);
 
+// k_gray_world.hip: gray-world white balance with red-channel compensation (include/uwie.h uwie_gray_world_u8); d_out / d_stats
+// optional (at least one), d_out == d_in allowed, ws: gray_world_ws_bytes
+size_t gray_world_ws_bytes(Shape s);
+void gray_world_plan(int *block_px, int *thread_px);  // pixels per workgroup of the sum pass, per thread of the apply pass
+int launch_gray_world(const uint8_t *d_in, Shape s, double red, double blue, double max_gain, uint8_t *d_out, double *d_stats, void *ws,
+                      hipStream_t st);
+
 // k_guided.hip
 size_t guided_ws_bytes(Shape s);
 size_t box_ws_bytes(Shape s);

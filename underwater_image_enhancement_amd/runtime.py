@@ -715,6 +715,25 @@ class Device(_ClosedOnDel):
                                                 _ptr(ws), ws.numel(), self.stream()))
         return out
 
+    def gray_world(self, frames_u8, red: float = 1.0, blue: float = 0.0, max_gain: float = 0.0, want_out: bool = True,
+                   want_stats: bool = False, out=None):
+        """Gray-world white balance with red-channel compensation (uwie_gray_world_u8): frames uint8 cuda [B,H,W,3] ->
+        (balanced uint8 [B,H,W,3] or None, stats float64 [B,12] in include/uwie.h's order or None).  ``out``: where the bytes go
+        (``frames_u8`` itself for in place; default a new tensor); without ``want_out`` and ``out`` only the stats are computed."""
+        B, H, W = self._bhw(frames_u8)
+        assert frames_u8.dtype == torch.uint8
+        if out is not None:
+            assert out.dtype == torch.uint8 and tuple(out.shape) == (B, H, W, 3) and out.is_contiguous()
+        elif want_out:
+            out = self.empty((B, H, W, 3), torch.uint8)
+        if out is None and not want_stats:
+            raise ValueError("gray_world: nothing asked for (want_out, want_stats or out)")
+        ws = self._sized_workspace(self.lib.uwie_workspace_bytes_gray_world(B, H, W), "gray_world: batch/H/W out of range")
+        stats = self.empty((B, _lib.GW_STATS), torch.float64) if want_stats else None
+        check(self.lib.uwie_gray_world_u8(self._ctx, _ptr(frames_u8), B, H, W, float(red), float(blue), float(max_gain), _ptr(out),
+                                          _ptr(stats), _ptr(ws), ws.numel(), self.stream()))
+        return out, stats
+
     def pick_best_u8(self, scores, col: int, every=None):
         """uwie_pick_best_u8: scores float64 cuda [n,B,ncols] -> (first argmax over the sets of column ``col`` as int32 [B],
         the winners' frames [B,H,W,3] gathered from ``every`` [n,B,H,W,3], or None without it)."""
