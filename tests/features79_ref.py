@@ -300,6 +300,120 @@ def features79(img):
     return np.concatenate(parts).astype(np.float64)
 
 
+# ------------------------------------------------------------------------------- the same definitions in float64
+# features79_f64 states what features79 states with every sum, mean, standard deviation and moment in float64, over the element
+# values the reference holds: the integer LAB / HSV / gray / Sobel / Laplacian planes, float32(u8) / 255 lifted to float64 for
+# the planes the reference normalises, the float32 values of a general float image.  Unchanged: the order statistics (NumPy's
+# float32 'linear' rule), SciPy's NaN rule for skew / kurtosis on float32 planes (m2 <= (eps32 * mean)^2), and the DCT block,
+# which takes dct2's values.
+F64_GROUPS = ("color", "texture", "frequency", "edge", "quality")
+_EPS32 = float(np.finfo(np.float32).eps)
+
+
+def moments_f64(ch):
+    """mean, std, skew, kurtosis (Fisher) of a plane in float64, with SciPy's float32 NaN rule."""
+    x = np.asarray(ch, dtype=np.float64).ravel()
+    m = x.mean()
+    d = x - m
+    d2 = d * d
+    m2, m3, m4 = d2.mean(), (d2 * d).mean(), (d2 * d2).mean()
+    if m2 <= (_EPS32 * m) ** 2:
+        return m, np.sqrt(m2), np.nan, np.nan
+    return m, np.sqrt(m2), m3 / (m2 * np.sqrt(m2)), m4 / (m2 * m2) - 3.0
+
+
+def mean_std_f64(ch):
+    x = np.asarray(ch, dtype=np.float64).ravel()
+    m = x.mean()
+    return m, np.sqrt(((x - m) ** 2).mean())
+
+
+def color_f64(lab, hsv, img_f32):
+    """indices 0-34 from the integer LAB / HSV planes and the float32 image."""
+    lab = np.asarray(lab, dtype=np.float64)
+    f = []
+    for c in range(3):
+        f += list(moments_f64(lab[:, :, c]))
+    for c in range(3):
+        f += list(mean_std_f64(hsv[:, :, c]))
+    a, b = lab[:, :, 1], lab[:, :, 2]
+    ma, mb = a.mean(), b.mean()
+    M = np.sqrt(ma ** 2 + mb ** 2)
+    D = np.sqrt(np.abs(a - ma).mean() ** 2 + np.abs(b - mb).mean() ** 2)
+    f += [M / (D + 1e-10), M, D, ma, mb]
+    img_f32 = np.asarray(img_f32, dtype=np.float32)
+    for c in range(3):
+        ch = img_f32[:, :, c]
+        f += list(mean_std_f64(ch)) + [float(ch.min()), float(ch.max())]
+    return np.array(f, dtype=np.float64)
+
+
+def dct_values(d):
+    """indices 57-61 from a coefficient plane, sums in float64."""
+    d = np.asarray(d, dtype=np.float64)
+    h, w = d.shape[-2:]
+    e = d * d
+    total = e.sum(axis=(-2, -1))
+    ad = np.abs(d)
+    n = float(h * w)
+    ma = ad.sum(axis=(-2, -1)) / n
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.stack([e[..., :h // 4, :w // 4].sum(axis=(-2, -1)) / total,
+                         e[..., h // 4:h // 2, w // 4:w // 2].sum(axis=(-2, -1)) / total,
+                         e[..., h // 2:, w // 2:].sum(axis=(-2, -1)) / total, ma,
+                         np.sqrt(((ad - ma[..., None, None]) ** 2).sum(axis=(-2, -1)) / n)], axis=-1)
+
+
+def edge_f64(g, with_canny=True):
+    gx, gy = sobel_int(g)
+    mag = np.sqrt((gx * gx + gy * gy).astype(np.float64)) / 255.0
+    lap = laplacian3(g)
+    density = np.sum(canny(g, 50, 150) > 0) / g.size if with_canny else np.nan
+    mm, ms = mean_std_f64(mag)
+    lm, ls = mean_std_f64(lap)
+    return np.array([mm, ms, mag.max(), density, np.abs(lap).mean(), ls, ((lap - lm) ** 2).mean()])
+
+
+def quality_f64(g8, sat_u8):
+    g = g8.astype(np.float32) / np.float32(255.0)
+    m, s = mean_std_f64(g)
+    sm, ss = mean_std_f64(sat_u8.astype(np.float32) / np.float32(255.0))
+    return np.array([s, shannon_entropy(g), m, np.median(g), np.percentile(g, 25), np.percentile(g, 75),
+                     np.max(g) - np.min(g), sm, ss, s], dtype=np.float64)
+
+
+def features79_f64(frame, groups=F64_GROUPS, with_canny=True):
+    """The row of features79 in float64.  ``frame``: a u8 frame (the float image is then float32(u8) / 255) or a float32
+    image in [0, 1].  ``groups``: the blocks to evaluate, in layout order (the cube needs only colour and quality, and the
+    Python LBP over it would take minutes); ``with_canny=False`` leaves index 65 NaN."""
+    x = np.asarray(frame)
+    if x.dtype == np.uint8:
+        u8, img = x, x.astype(np.float32) / np.float32(255.0)
+    else:
+        img = np.asarray(x, dtype=np.float32)
+        u8 = _u8(img)
+    g = orc.cv_rgb2gray_u8(u8)
+    hsv = orc.cv_rgb2hsv_u8(u8)
+    parts = []
+    for name in F64_GROUPS:
+        if name not in groups:
+            continue
+        if name == "color":
+            parts.append(color_f64(orc.cv_rgb2lab_u8(u8), hsv, img))
+        elif name == "texture":
+            parts.append(extract_texture_features(img).astype(np.float64))  # counts and float64 sums already
+        elif name == "frequency":
+            try:
+                parts.append(dct_values(dct2(g.astype(np.float32))))
+            except OddSizeDCT:
+                pass
+        elif name == "edge":
+            parts.append(edge_f64(g, with_canny))
+        else:
+            parts.append(quality_f64(g, hsv[:, :, 1]))
+    return np.concatenate(parts)
+
+
 def feature_count(H: int, W: int) -> int:
     return 79 if all(n == 1 or n % 2 == 0 for n in (H, W)) else 74
 
