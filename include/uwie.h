@@ -778,6 +778,77 @@ int uwie_gray_world_plan(int H, int W, int *block_px, int *thread_px);
 int uwie_gray_world_u8(uwie_ctx *ctx, const uint8_t *d_in, int batch, int H, int W, double red, double blue, double max_gain,
                        uint8_t *d_out, double *d_stats, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Multi-scale fusion, the second half of Ancuti et al. 2018, "Color Balance and Fusion for Underwater Image Enhancement" (the
+ * gray-world pre-pass above is its first): from the balanced frame a gamma-corrected and a sharpened input are derived, each
+ * gets a weight from Laplacian contrast, saliency and saturation, and the two are blended over a Laplacian pyramid.  An
+ * extension without a reference counterpart: this comment is the contract, tests/fusion_ref.py restates it in NumPy.
+ *
+ * Input: a u8 RGB frame x, H x W, n = H * W pixels; the caller has balanced it already.  Parameters: gamma, finite,
+ * 0 < gamma <= 8; levels L, 1 <= L <= 8; gray_shift, 14 or 15.  "Integer" is exact integer arithmetic.  Everything else is
+ * float64, each operation rounded once, in the order written, no fused multiply-add; integers are converted exactly.  Every
+ * out-of-range index is clamped to the plane (BORDER_REPLICATE), so every size from 1 x 1 is valid at every L.
+ *
+ * The 5-tap rule along an axis:  T(v)[j] = ((v[j-2] + v[j+2]) + 4 * (v[j-1] + v[j+1])) + 6 * v[j].
+ *   B(p) = T along the row, then T down the column (the taps of the 5 x 5 binomial, summing to 256).
+ *
+ * The two inputs (integer, bytes):
+ *   I1_c = G[x_c],  G[v] = rint(255 * (v / 255)^gamma): a 256-entry byte table built on the host with C pow();
+ *          uwie_fusion_table(gamma, table) returns it (host only, no context, no device).
+ *   I2_c = clamp((512 * x_c - B(x_c) + 128) >> 8, 0, 255)     (>> is the arithmetic shift: floor)
+ *          an unsharp mask of amount 1 over the binomial blur, x + (x - blur(x)).  The paper's normalising stretch is replaced
+ *          by the clamp, on purpose: the input is a byte and needs no second global pass.
+ *
+ * The weight of input k (k = 1, 2), per pixel, with (r, g, b) the bytes of I_k:
+ *   Y    = the gray byte of I_k (the rule of uwie_rgb2gray_u8 with gray_shift)
+ *   lap  = |4 * Y - Y(up) - Y(down) - Y(left) - Y(right)|   (integer)          wl = lap / 255
+ *   S_c  = the sum of I_k's channel c over the frame (integer)                  mu_c = S_c / n
+ *   d_c  = mu_c - B(I_k,c) * 2^-8        (B is an integer, the scaling exact)
+ *   sal  = ((0 + d_r * d_r) + d_g * d_g) + d_b * d_b                            ws = sal / 65025
+ *          (the saliency of Achanta et al. -- distance of the blurred pixel from the frame's mean -- on the RGB bytes, not Lab)
+ *   q    = (r - Y)^2 + (g - Y)^2 + (b - Y)^2                (integer)          wsat = sqrt(q / 3) / 255
+ *   W_k  = (wl + ws) + wsat
+ * The normalised weight of input 1:   a = W_1 + 0.1     Wn = a / (a + (W_2 + 0.1))
+ *   Input 2's weight is 1 - Wn at every level: reduce() below maps a constant plane to itself exactly, so the Gaussian
+ *   pyramid of 1 - Wn is one minus that of Wn.
+ *
+ * The pyramid.  A level has ceil(h / 2) x ceil(w / 2) points of the h x w level above it.
+ *   reduce(p):  T along the row, T down the column, times 2^-8, sampled at the even indices.
+ *   expand(p) to a given finer size, along the row and then down the column; with k = i / 2 (integer):
+ *       even i:  ((p[k-1] + p[k+1]) + 6 * p[k]) * 0.125          odd i:  (p[k] + p[k+1]) * 0.5
+ *
+ * The fusion, per channel:
+ *   D = I1 - I2  (integer)      GW_0 = Wn    GD_0 = D     GW_l = reduce(GW_l-1)    GD_l = reduce(GD_l-1)
+ *   acc_L-1 = GW_L-1 * GD_L-1
+ *   for l = L-2 .. 0:   acc_l = GW_l * (GD_l - expand(GD_l+1)) + expand(acc_l+1)
+ *   out = rint(min(max(I2 + acc_0, 0), 255))                                    (round half to even)
+ * Two inputs whose weights sum to one give  sum_k G_l(Wn_k) * L_l(I_k) = L_l(I2) + G_l(Wn_1) * L_l(I1 - I2), and the collapse is
+ * linear: this is the paper's multi-scale fusion with one weight pyramid and one pyramid of the difference instead of two and
+ * two.  That is the definition, not an optimisation behind it.
+ *
+ * Fixed by this: a frame of one level v comes back as rint((G[v] + v) / 2) at every L (Wn = 0.5 exactly; 77 at gamma 2.2 gives
+ * 48 from 47.5); L = 1 is the per-pixel blend I2 + Wn * D.
+ *
+ * d_out [batch][H][W][3].  Optional outputs, NULL to skip: d_in1, d_in2 ([batch][H][W][3], the two inputs) and d_weight
+ * ([batch][H][W] float64, Wn, 8-byte aligned), so that a wrong byte can be traced to a stage.  d_out == d_in is allowed; any
+ * other overlap among d_in, d_out, d_in1, d_in2 is an error.  No alignment is asked of the byte planes; a frame inside a batch
+ * starts wherever 3 * H * W puts it.  batch <= 65535.  Out-of-range or non-finite parameters are UWIE_E_INVALID with a message
+ * naming the field, a short or NULL workspace UWIE_E_WORKSPACE; every check runs before the context is touched.
+ * Exact: every byte of d_out, d_in1, d_in2 and every bit of d_weight equals the float64 evaluation above
+ * (tests/test_gpu_fusion.py).  2 * L + 2 launches whatever H and W, no atomics, no memset, no host read; the grids come from H,
+ * W and L only, so a frame's results are the same bits in every run and at every position of every batch.
+ * uwie_fusion_plan: *tile_w x *tile_h = the level-0 tile one workgroup stages with its 2-pixel halo; the launchers run on these
+ * numbers, so a test can aim at the seams.
+ * Workspace: uwie_workspace_bytes_fusion(batch, H, W, levels): per pixel 3 bytes of I2, 8 of Wn and 6 of D, per point of each
+ * coarser level 56 bytes (GW, GD, acc in float64), 32 bytes per level-0 tile and 64 per frame.
+ */
+size_t uwie_workspace_bytes_fusion(int batch, int H, int W, int levels);
+int uwie_fusion_plan(int H, int W, int levels, int *tile_w, int *tile_h);
+int uwie_fusion_table(double gamma, uint8_t *table256); /* host only */
+int uwie_fusion_u8(uwie_ctx *ctx, const uint8_t *d_in, int batch, int H, int W, double gamma, int levels, int gray_shift,
+                   uint8_t *d_out, uint8_t *d_in1, uint8_t *d_in2, double *d_weight, void *d_workspace, size_t workspace_bytes,
+                   void *stream);
+
 /* ---------------- strategy classifier: main.py:398-433 (predict) ---------------- */
 
 /*

@@ -9,10 +9,10 @@ from .api import (CONFIG_QUALITY_WEIGHTS, CONFIG_STRATEGIES, DRIVER_STRATEGIES, 
                   select_best, training_batch, vgg_input,
                   UNDERWATER_SCORE_NAMES, UnderwaterQuality, select_best_underwater, underwater_scores,
                   REFERENCE_SCORE_NAMES, ReferenceQuality, reference_scores, select_best_reference,
-                  GRAY_WORLD_STAT_NAMES, gray_world)
+                  GRAY_WORLD_STAT_NAMES, gray_world, fusion, fusion_levels)
 from .classifier import StrategyClassifier  # noqa: F401
 from .runtime import Device, get_device  # noqa: F401
 from .streaming import StreamEnhancer  # noqa: F401
 
-__all__ = ["enhance", "enhance_all", "gray_world", "GRAY_WORLD_STAT_NAMES", "reference_scores", "REFERENCE_SCORE_NAMES", "ReferenceQuality", "select_best_reference", "underwater_scores", "UNDERWATER_SCORE_NAMES", "UnderwaterQuality", "select_best_underwater","process_batch", "extract_all_features", "QualityAssessment", "quality_scores", "QUALITY_KEYS", "DRIVER_STRATEGIES", "select_best", "CONFIG_STRATEGIES", "CONFIG_QUALITY_WEIGHTS", "DifferentiableEnhancement", "DiffEnhanceFunction", "GatedDifferentiableEnhancement", "GatedDiffEnhanceFunction", "ReferenceLoss", "RefLossFunction", "PerceptualLoss", "PerceptualFunction", "CombinedLoss", "vgg16_features16", "VGGParameterNet", "EnhancementPredictor", "ParameterPredictor", "GatedEnhancementPredictor", "EndToEndTrainer", "GATED_PARAM_KEYS", "param_net_torch", "param_net_layout", "PARAM_KEYS", "DiffEnhanceLossFunction", "GatedDiffEnhanceLossFunction", "FeatureExtractor", "FEATURE_EXTRACTOR_KEYS", "feature_extractor_rows", "feature_extractor_keys", "resize_frames", "image_tensor", "training_batch", "vgg_input", "SixStrategies", "EnhancementStrategies", "StrategyClassifier", "detect_image_type", "color_correction", "Device",
+__all__ = ["enhance", "enhance_all", "fusion", "fusion_levels", "gray_world", "GRAY_WORLD_STAT_NAMES", "reference_scores", "REFERENCE_SCORE_NAMES", "ReferenceQuality", "select_best_reference", "underwater_scores", "UNDERWATER_SCORE_NAMES", "UnderwaterQuality", "select_best_underwater","process_batch", "extract_all_features", "QualityAssessment", "quality_scores", "QUALITY_KEYS", "DRIVER_STRATEGIES", "select_best", "CONFIG_STRATEGIES", "CONFIG_QUALITY_WEIGHTS", "DifferentiableEnhancement", "DiffEnhanceFunction", "GatedDifferentiableEnhancement", "GatedDiffEnhanceFunction", "ReferenceLoss", "RefLossFunction", "PerceptualLoss", "PerceptualFunction", "CombinedLoss", "vgg16_features16", "VGGParameterNet", "EnhancementPredictor", "ParameterPredictor", "GatedEnhancementPredictor", "EndToEndTrainer", "GATED_PARAM_KEYS", "param_net_torch", "param_net_layout", "PARAM_KEYS", "DiffEnhanceLossFunction", "GatedDiffEnhanceLossFunction", "FeatureExtractor", "FEATURE_EXTRACTOR_KEYS", "feature_extractor_rows", "feature_extractor_keys", "resize_frames", "image_tensor", "training_batch", "vgg_input", "SixStrategies", "EnhancementStrategies", "StrategyClassifier", "detect_image_type", "color_correction", "Device",
            "get_device", "StreamEnhancer", "UwieError", "UnsupportedInputError", "UwieParams", "build", "load"]

@@ -128,6 +128,22 @@ def gray_world_plan(H, W) -> tuple[int, int]:
     return bp.value, tp.value
 
 
+def fusion_plan(H, W, levels=1) -> tuple[int, int]:
+    """uwie_fusion_plan: (tile_w, tile_h), the level-0 tile one workgroup stages with its halo.  Needs the library, not a device."""
+    tw, th = ctypes.c_int(), ctypes.c_int()
+    check(load().uwie_fusion_plan(int(H), int(W), int(levels), ctypes.byref(tw), ctypes.byref(th)))
+    return tw.value, th.value
+
+
+def fusion_table(gamma):
+    """uwie_fusion_table: G[v] = rint(255 (v / 255)^gamma) as 256 bytes (NumPy uint8).  Needs the library, not a device."""
+    import numpy as np
+
+    buf = (ctypes.c_uint8 * 256)()
+    check(load().uwie_fusion_table(float(gamma), buf))
+    return np.frombuffer(bytes(buf), dtype=np.uint8).copy()
+
+
 # name -> argument types (return type is int unless listed in _RESTYPES)
 _VP, _SZ, _I, _D = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_double
 _PP = ctypes.POINTER(UwieParams)
@@ -173,6 +189,10 @@ SIGNATURES = {
     "uwie_workspace_bytes_gray_world": [_I, _I, _I],
     "uwie_gray_world_plan": [_I, _I, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
     "uwie_gray_world_u8": [_VP, _VP, _I, _I, _I, _D, _D, _D, _VP, _VP, _VP, _SZ, _VP],
+    "uwie_workspace_bytes_fusion": [_I, _I, _I, _I],
+    "uwie_fusion_plan": [_I, _I, _I, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
+    "uwie_fusion_table": [_D, ctypes.POINTER(ctypes.c_uint8)],
+    "uwie_fusion_u8": [_VP, _VP, _I, _I, _I, _D, _I, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP],
     "uwie_pick_best_u8": [_VP, _VP, _I, _I, _I, _I, _VP, _I, _I, _VP, _VP, _VP],
     "uwie_diff_enhance_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _SZ, _VP],
     "uwie_diff_enhance_save_f32": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _SZ, _VP],
@@ -259,6 +279,7 @@ _RESTYPES = {
     "uwie_workspace_bytes_underwater": ctypes.c_size_t,
     "uwie_workspace_bytes_reference": ctypes.c_size_t,
     "uwie_workspace_bytes_gray_world": ctypes.c_size_t,
+    "uwie_workspace_bytes_fusion": ctypes.c_size_t,
     "uwie_diff_enhance_bwd_workspace_bytes": ctypes.c_size_t,
     "uwie_workspace_bytes_diff_u8": ctypes.c_size_t,
     "uwie_diff_gated_bwd_workspace_bytes": ctypes.c_size_t,

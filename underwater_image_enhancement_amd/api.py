@@ -132,6 +132,32 @@ def gray_world(frames, red: float = 1.0, blue: float = 0.0, max_gain: float = 0.
     return _finish(out, was_numpy, single, dev), _finish(stats, was_numpy, single)
 
 
+def fusion_levels(H: int, W: int) -> int:
+    """What ``fusion(levels=None)`` uses: min(6, max(1, floor(log2(min(H, W))) - 2)), a coarsest level of at least 4 points."""
+    return min(6, max(1, int(min(H, W)).bit_length() - 3))
+
+
+def fusion(frames, gamma: float = 2.2, levels: int | None = None, gray_world=True, return_parts: bool = False,
+           device: int | None = None):
+    """Ancuti et al. 2018's colour balance and multi-scale fusion in the fixed form include/uwie.h states (uwie_fusion_u8; an
+    extension without a reference counterpart), on the device: uint8 ``[H,W,3]`` / ``[B,H,W,3]``, NumPy or a torch ROCm tensor
+    -> the fused frames, of the same kind.  The frames are balanced by ``gray_world`` first (``True``, the default and the
+    paper's pipeline, or a dict of ``red`` / ``blue`` / ``max_gain``; ``None`` fuses the frames as given):
+    ``fusion(x, gray_world=g)`` is ``fusion(gray_world(x, **g), gray_world=None)``.  From the balanced frame a gamma-corrected
+    input (``gamma``, 0 < gamma <= 8) and a sharpened one are blended over a Laplacian pyramid of ``levels`` levels (1 .. 8;
+    ``None``: ``fusion_levels(H, W)``) with weights from Laplacian contrast, saliency and saturation.  With ``return_parts``
+    the result is ``(out, (in1, in2, weight))``: the two inputs and the float64 normalised weight of the first."""
+    _gray_world_needs_u8(frames)
+    dev = get_device(device)
+    batch, was_numpy, single = _as_balanced_batch_u8(frames, dev, gray_world)
+    if levels is None:
+        levels = fusion_levels(batch.shape[1], batch.shape[2])
+    out, parts = dev.fusion(batch, gamma=gamma, levels=levels, want_parts=return_parts)
+    if not return_parts:
+        return _finish(out, was_numpy, single, dev)
+    return _finish(out, was_numpy, single, dev), tuple(_finish(t, was_numpy, single, dev if t.dtype == torch.uint8 else None) for t in parts)
+
+
 def enhance(frames, strategy: int = 2, cast_correct: bool = True, device: int | None = None, return_float: bool = False,
             gray_world=None, **overrides):
     """Canonical ``enhance(u8 RGB) -> u8 RGB`` (six_stadigy.py:406-431) for one frame or a batch.

@@ -1860,6 +1860,53 @@ int uwie_gray_world_u8(uwie_ctx *ctx, const uint8_t *d_in, int batch, int H, int
     return launch_gray_world(d_in, s, red, blue, max_gain, d_out, d_stats, d_workspace, (hipStream_t)stream);
 }
 
+size_t uwie_workspace_bytes_fusion(int batch, int H, int W, int levels)
+{
+    if (!shape_ok(batch, H, W) || batch > 65535 || levels < 1 || levels > 8) return 0;
+    return fusion_ws_bytes(Shape{batch, H, W}, levels);
+}
+
+int uwie_fusion_plan(int H, int W, int levels, int *tile_w, int *tile_h)
+{
+    UWIE_REQUIRE(tile_w && tile_h, "fusion_plan: NULL pointer");
+    UWIE_CHECK_SHAPE(1, H, W);
+    UWIE_REQUIRE(levels >= 1 && levels <= 8, "fusion_plan: levels must be in 1 .. 8");
+    fusion_tile(tile_w, tile_h);  // one tile for every frame and every levels
+    return UWIE_OK;
+}
+
+int uwie_fusion_table(double gamma, uint8_t *table256)
+{
+    UWIE_REQUIRE(table256, "fusion_table: NULL table");
+    UWIE_REQUIRE(gamma > 0.0 && gamma <= 8.0, "fusion_table: gamma must be finite, 0 < gamma <= 8");  // (false for NaN)
+    fusion_table(gamma, table256);
+    return UWIE_OK;
+}
+
+int uwie_fusion_u8(uwie_ctx *ctx, const uint8_t *d_in, int batch, int H, int W, double gamma, int levels, int gray_shift, uint8_t *d_out,
+                   uint8_t *d_in1, uint8_t *d_in2, double *d_weight, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    // every check comes before the context is touched
+    UWIE_REQUIRE(ctx && d_in && d_out, "fusion: NULL context, d_in or d_out");
+    UWIE_CHECK_SHAPE(batch, H, W);
+    UWIE_REQUIRE(batch <= 65535, "fusion: batch must be <= 65535");
+    UWIE_REQUIRE(gamma > 0.0 && gamma <= 8.0, "fusion: gamma must be finite, 0 < gamma <= 8");  // (false for NaN)
+    UWIE_REQUIRE(levels >= 1 && levels <= 8, "fusion: levels must be in 1 .. 8");
+    UWIE_REQUIRE(gray_shift == 14 || gray_shift == 15, "fusion: gray_shift must be 14 or 15");
+    UWIE_REQUIRE(((uintptr_t)d_weight & 7) == 0, "fusion: d_weight must be 8-byte aligned");
+    const Shape s{batch, H, W};
+    const size_t bytes = (size_t)batch * s.npx() * 3;
+    const uint8_t *planes[4] = {d_in, d_out, d_in1, d_in2};  // d_out == d_in is the one overlap allowed
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j)
+            UWIE_REQUIRE(!planes[i] || !planes[j] || (i == 0 && j == 1 && d_out == d_in) || planes[i] + bytes <= planes[j] ||
+                             planes[j] + bytes <= planes[i],
+                         "fusion: d_in, d_out, d_in1 and d_in2 overlap (only d_out == d_in is allowed)");
+    UWIE_CHECK_WS(fusion_ws_bytes(s, levels));
+    UWIE_SCOPE(ctx);
+    return launch_fusion(d_in, s, gamma, levels, gray_shift, d_out, d_in1, d_in2, d_weight, d_workspace, (hipStream_t)stream);
+}
+
 int uwie_pick_best_u8(uwie_ctx *ctx, const double *d_scores, int n, int batch, int ncols, int col, const uint8_t *d_all_u8, int H,
                       int W, int32_t *d_best, uint8_t *d_best_u8, void *stream)
 {

@@ -285,6 +285,14 @@ void gray_world_plan(int *block_px, int *thread_px);  // pixels per workgroup of
 int launch_gray_world(const uint8_t *d_in, Shape s, double red, double blue, double max_gain, uint8_t *d_out, double *d_stats, void *ws,
                       hipStream_t st);
 
+// k_fusion.hip: multi-scale fusion of a gamma-corrected and a sharpened input (include/uwie.h uwie_fusion_u8); d_in1 / d_in2 /
+// d_weight optional, ws: fusion_ws_bytes
+size_t fusion_ws_bytes(Shape s, int levels);
+void fusion_tile(int *tile_w, int *tile_h);             // the level-0 tile one workgroup stages with its halo
+void fusion_table(double gamma, uint8_t *table256);     // G of the contract, on the host
+int launch_fusion(const uint8_t *d_in, Shape s, double gamma, int levels, int gray_shift, uint8_t *d_out, uint8_t *d_in1, uint8_t *d_in2,
+                  double *d_weight, void *ws, hipStream_t st);
+
 // k_guided.hip
 size_t guided_ws_bytes(Shape s);
 size_t box_ws_bytes(Shape s);

@@ -734,6 +734,22 @@ class Device(_ClosedOnDel):
                                           _ptr(stats), _ptr(ws), ws.numel(), self.stream()))
         return out, stats
 
+    def fusion(self, frames_u8, gamma: float = 2.2, levels: int = 1, gray_shift: int = 15, want_parts: bool = False):
+        """Multi-scale fusion of a gamma-corrected and a sharpened input (uwie_fusion_u8): balanced frames uint8 cuda [B,H,W,3]
+        -> (fused uint8 [B,H,W,3], parts); parts is None, or with ``want_parts`` (in1 uint8 [B,H,W,3], in2 uint8 [B,H,W,3],
+        weight float64 [B,H,W] = the normalised weight of input 1)."""
+        B, H, W = self._bhw(frames_u8)
+        assert frames_u8.dtype == torch.uint8
+        ws = self._sized_workspace(self.lib.uwie_workspace_bytes_fusion(B, H, W, int(levels)), "fusion: batch/H/W/levels out of range")
+        out = self.empty((B, H, W, 3), torch.uint8)
+        parts = None
+        if want_parts:
+            parts = (self.empty((B, H, W, 3), torch.uint8), self.empty((B, H, W, 3), torch.uint8), self.empty((B, H, W), torch.float64))
+        in1, in2, weight = parts if parts else (None, None, None)
+        check(self.lib.uwie_fusion_u8(self._ctx, _ptr(frames_u8), B, H, W, float(gamma), int(levels), int(gray_shift), _ptr(out), _ptr(in1),
+                                      _ptr(in2), _ptr(weight), _ptr(ws), ws.numel(), self.stream()))
+        return out, parts
+
     def pick_best_u8(self, scores, col: int, every=None):
         """uwie_pick_best_u8: scores float64 cuda [n,B,ncols] -> (first argmax over the sets of column ``col`` as int32 [B],
         the winners' frames [B,H,W,3] gathered from ``every`` [n,B,H,W,3], or None without it)."""
