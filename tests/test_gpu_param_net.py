@@ -95,6 +95,25 @@ def test_batch_rows_do_not_depend_on_the_batch(dev, nets):
         assert np.array_equal(one, whole[b:b + 1])
 
 
+@pytest.mark.parametrize("B", [8, 17, 33])
+def test_linear_layers_staging_passes(dev, nets, B):
+    """k_pn_linear stages 8192 // span batch rows per pass: 7 (fusion layer with features), 8 (without), 32 (the heads' first
+    layers) and 16 (their last).  B = 8, 17 and 33 are one past a pass of 7, of 8 and 16, and of 32: on 8 x 8 frames every
+    batch row equals its single call bit for bit, and the parameters stay within 1e-5 of their range of the float64 net."""
+    seed, _ = golden()
+    rng = np.random.default_rng(100 + B)
+    img = rng.standard_normal((B, 3, 8, 8)).astype(np.float32)
+    feats = rng.random((B, 79), dtype=np.float32)
+    for uf in (True, False):
+        f = feats if uf else None
+        pooled, whole = run(dev, nets[uf], img, f)
+        for b in range(B):
+            p1, one = run(dev, nets[uf], img[b:b + 1], None if f is None else f[b:b + 1])
+            assert np.array_equal(one, whole[b:b + 1]) and np.array_equal(p1, pooled[b:b + 1]), (uf, b)
+        _, q64 = PN.forward(PN.seeded_state(seed, uf), img, f, uf)
+        params_within(whole, q64, 1e-5, f"B={B} use_features={uf}")
+
+
 def test_errors_before_any_launch(dev, nets):
     import torch
 
